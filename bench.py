@@ -6,16 +6,23 @@ K = 64 segments) + matrix-Fisher base, forward log_prob only, 2^20 uniform-SO(3)
 A "step" = one fused density evaluation of the whole per-GPU batch (inputs resident in HBM) + the mean-NLL reduction (on N > 1 GPUs: one
 RCCL all-reduce of {sum log p, count}).  Weak scaling: every rank evaluates its own 2^20 shard.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4|C5|C5u] [--batch-log2 B]
-                    [--no-cpu-baseline] [--no-secondary] [--no-configs] [--no-pmc]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4|C5|C5u] [--batch-log2 B] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-secondary] [--no-configs] [--no-pmc]]
 
-ONE JSON line on rank 0.  At N = 1 with the default workload the line also carries (round 4):
+ONE JSON line on rank 0.  A plain run does only what its headline figure needs: it sets up the workload, lets the clock settle, warms up,
+times the K steps (`ms_per_step`, `value`, `mean_nll`, the roofline of those steps' HIP-event time) and prints the line.
+--dump-outputs DIR then writes what the last timed step returned to its caller (per-rotation log p and the {sum log p, count} pair of the
+forward workloads; rotations, log p and pose estimates of the inverse ones) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a
+fixed seeded sample of rows beyond that).  Inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Everything else moves behind --full.  At N = 1 with the default workload the --full line also carries (round 4):
   * `value_fp32_exact` / `ms_per_step_fp32_exact`: the same workload on the exact fp32-input MFMA kernels (the unconditional number; `value`
     is the default split-precision arithmetic -- fp32 operands carried as fp16 hi+lo pairs, fp32 accumulate);
   * `configs`: every other BASELINE.json config on the same clock -- C1, C3 (its 2^22 rotations on this one GPU), C4, C5, C5u -- each with
     value, ms_per_step, both arithmetics, roofline (frac, kernel list, HBM traffic, VALU-issue and matrix-pipe fractions), parity against the
     fp64 oracle with the reference-fp32 arithmetic's own error beside it, and a CPU baseline; plus `configs.train`: one training iteration
     of the reference's recipe, eager with torch's default Adam, as the unedited driver runs it;
+  * parity against the fp64 oracle, the CPU baseline (`vs_cpu_baseline`) and the device state (power, clock) under the workload;
   * `roofline.traffic` and the binding fractions MEASURED IN THIS RUN: before this process touches the GPU it runs three short
     `rocprofv3 --pmc <group> --kernel-trace -- python3 bench.py --pmc-child ...` children (FETCH_SIZE, WRITE_SIZE and the SQ/GRBM group each in
     its own pass, as MI355X_MICROARCH.md prescribes; FETCH_SIZE x 2 x 1024, WRITE_SIZE x 1024) over the same workloads of the same library.
@@ -23,7 +30,8 @@ ONE JSON line on rank 0.  At N = 1 with the default workload the line also carri
 
 --config C3 (BASELINE.json configs[2]) is the STRONG-scaling workload: one global batch of 2^22 rotations split contiguously over the N
 ranks (2^19 per GPU at N = 8, all 2^22 on one GPU at N = 1), uniform base, one all-reduce of {sum log p, count}; every other config is weak
-scaling (2^20 rotations per GPU).  An explicit --config runs that workload alone (no `configs` object).
+scaling (2^20 rotations per GPU).  An explicit --config runs that workload alone (no `configs` object; with --full its own secondary
+legs, parity, CPU baseline and, for C2t / C4t, the timed inverse pass).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its N ranks itself (`python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ...` as a CHILD process, before this process touches the GPU) and relays the child's JSON line
@@ -101,6 +109,9 @@ PMC_GROUPS = {
 }
 PMC_EVALS = 2                             # profiled evaluations per workload and arithmetic in a --pmc-child pass (behind one warm-up)
 MARKER = "FillFunctor<short>"             # an int16 fill: a kernel nothing else launches, separates the sections of a --pmc-child pass
+DUMP_LIMIT = 64 << 20                     # bytes of --dump-outputs in all
+DUMP_SEED = 7                             # the row sample of --dump-outputs beyond DUMP_LIMIT
+INPUT_SEED = 2024                         # torch's default generator (+ rank): the keys of the inverse workloads' base samples
 
 
 def self_launch(args, argv):
@@ -275,10 +286,14 @@ class Workload:
                 full = torch.randn(((skip + self.n) // per, self.feat_dim), generator=gen, device=device, dtype=torch.float32)
                 self.feat = full[skip // per:].contiguous()
 
-    def evaluate(self):
+    def evaluate(self, keep=False):
+        """One step -> its {sum log p, count}.  keep: also hold what the step hands its caller in `self.outputs` (device tensors)."""
         import torch
         if self.wl["direction"] == "forward":
-            return self.fl.log_prob(self.R, self.feat, base=self.base, feature_repeat=self.queries)["sum"]
+            res = self.fl.log_prob(self.R, self.feat, base=self.base, feature_repeat=self.queries)
+            if keep:
+                self.outputs = {"logp": res["logp"]}
+            return res["sum"]
         # eval.py:327-347: base samples + their log-density, inverse pass, log p = base - ldj
         z = self.base._sample(self.n).reshape(-1, 3, 3)
         lp = self.base._log_prob(z)
@@ -287,11 +302,16 @@ class Workload:
         if self.queries:                                      # agent.py:264-283: the most likely of each image's samples is the pose estimate
             best = lp.view(-1, self.queries).argmax(dim=1)
             self.estimate = rot.view(-1, self.queries, 3, 3)[torch.arange(best.numel(), device=best.device), best]
+        if keep:
+            self.outputs = {"rotation": rot, "logp": lp}
+            if self.queries:
+                self.outputs["estimate"] = self.estimate
         lp = lp.double()
         return torch.stack((lp.sum(), torch.tensor(float(self.n), dtype=torch.float64, device=self.device)))
 
     def timed(self, steps, warmup, settle, dist=None):
-        """-> (elapsed s over `steps` (max over ranks), mean HIP-event ms of the library calls, last {sum, count})."""
+        """-> (elapsed s over `steps` (max over ranks), mean HIP-event ms of the library calls, last {sum, count}).  The last step's
+        outputs stay in `self.outputs`."""
         import numpy as np
         import torch
         from rotationnormflow_amd.dist import all_reduce_nll
@@ -312,7 +332,7 @@ class Workload:
             t0 = time.perf_counter()
             for i in range(steps):
                 ev[i][0].record()                              # the library launches on torch's current stream: these events bracket its kernels
-                part = self.evaluate()
+                part = self.evaluate(keep=i == steps - 1)
                 ev[i][1].record()
                 tot = all_reduce_nll(part) if distributed else part
             torch.cuda.synchronize()
@@ -667,11 +687,32 @@ def device_state(w, seconds=1.2):
         return {"workload": w.name, "error": repr(exc)}
 
 
-def measure(w, args, dist, pmc, steps, warmup, want_secondary, want_parity, cpu_sizes, cpu_budget, blocks=1):
+def dump_outputs(outputs, tot, dirname):
+    """--dump-outputs: the last timed step's outputs (device tensors) and its {sum log p, count} as DIR/<name>.npy, float32 or float64.
+    Beyond DUMP_LIMIT bytes the batch-sized arrays keep the same fixed seeded sample of rows (sorted), the others stay whole."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() for k, v in outputs.items()}
+    arrays["sum_count"] = np.asarray(tot, dtype=np.float64)
+    arrays = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False) for k, a in arrays.items()}
+    rows = max(a.shape[0] for a in arrays.values() if a.ndim)
+    batched = [k for k, a in arrays.items() if a.ndim and a.shape[0] == rows]
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT - 256 * len(arrays)                   # (room for the .npy headers)
+    if total > budget:
+        per_row = sum(arrays[k].nbytes for k in batched) / rows
+        keep = int((budget - (total - per_row * rows)) // per_row)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+        arrays.update({k: np.ascontiguousarray(arrays[k][pick]) for k in batched})
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+
+
+def measure(w, args, dist, pmc, steps, warmup, want_secondary, want_parity, cpu_sizes, cpu_budget, blocks=1, dump_dir=None):
     """One workload -> its record (rank 0 fills the host-side legs).  blocks: the K timed steps are measured this many times and the
     fastest block is kept.  The headline leg (`value`) is ALWAYS one block, as the bench contract says; the `configs` entries and the
     exact-fp32 legs use two (one sweep of round 4 caught a leg whose eight launches ran at half clock: 8.7 ms per step for a kernel that
-    takes 4.7 before and after)."""
+    takes 4.7 before and after).  dump_dir: write the outputs of the last timed step there (dump_outputs) before any other leg runs."""
     import torch
     from rotationnormflow_amd import get_precision, set_precision
     rank0 = dist is None or dist.get_rank() == 0
@@ -686,6 +727,8 @@ def measure(w, args, dist, pmc, steps, warmup, want_secondary, want_parity, cpu_
                 best = again
         return best
     elapsed, kernel_ms, tot = timed(steps, warmup, CLOCK_SETTLE_LAUNCHES, blocks)
+    if dump_dir:
+        dump_outputs(w.outputs, tot, dump_dir)
     used = w.fl._packed(w.device, w.feat).precision      # "fp32" when a weight left the fp16 range and the packer fell back
     rec = {"workload": f"{w.name} -- {w.wl['text']}", "value": w.n_global * steps / elapsed, "unit": "rotations/s", "steps": steps, "warmup": warmup,
            "timed_blocks": blocks, "ms_per_step": elapsed / steps * 1e3,
@@ -696,7 +739,7 @@ def measure(w, args, dist, pmc, steps, warmup, want_secondary, want_parity, cpu_
                    "frac": w.wl["bytes"] * w.n / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, "algorithmic_bytes_per_rotation": w.wl["bytes"]}}
     if w.weights_path:
         rec["weights"] = os.path.basename(w.weights_path)
-    if w.wl.get("also_inverse"):                             # the inverse pass of the same flow on the same rows (root-finder passes depend on the weights)
+    if w.wl.get("also_inverse") and args.full:               # the inverse pass of the same flow on the same rows (root-finder passes depend on the weights)
         with torch.no_grad():
             for _ in range(3):
                 w.fl.inverse(w.R, w.feat)
@@ -930,12 +973,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--config", default=None, choices=sorted(WORKLOADS), help="run this workload alone (default: C2 headline + every other config)")
+    ap.add_argument("--config", default=None, choices=sorted(WORKLOADS), help="run this workload alone (default: the C2 headline; with --full also every other config)")
     ap.add_argument("--batch-log2", type=int, default=None, help="log2 of the batch: per GPU (weak-scaling configs, default 20) or global (C3, default 22)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the host-side legs (CPU baseline and the oracle parity block)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the exact-fp32 leg")
-    ap.add_argument("--no-configs", action="store_true", help="headline workload only")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 counter passes")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure too: the exact-fp32 and strict legs, parity "
+                    "against the fp64 oracle, the CPU baseline, live rocprofv3 counter passes, the device state, every other config and the "
+                    "training iteration (the --no-* switches below trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-side legs (CPU baseline and the oracle parity block)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the exact-fp32 and strict legs")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: headline workload only")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the live rocprofv3 counter passes")
     ap.add_argument("--save-pmc", default=None, metavar="DIR", help="also write the live PMC summary to DIR/pmc_live.json (profiles/<round>/)")
     ap.add_argument("--weights", default=None, metavar="CKPT", help="load the headline workload's flow from this checkpoint (Agent.save_ckpt "
                     "layout, e.g. tests/golden/trained_c2.pth) instead of the recipe weights")
@@ -948,6 +995,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.pmc_child:
         return pmc_child(args)
 
@@ -973,14 +1022,14 @@ def main():
         faulthandler.dump_traceback_later(int(os.environ["RNF_BENCH_HANG_DUMP"]), exit=True)
 
     headline = args.config or "C2"
-    full = args.config is None and not args.no_configs and not distributed
-    others = [c for c in ALL_CONFIGS if c != headline] if full else []
+    sweep = args.full and args.config is None and not args.no_configs and not distributed
+    others = [c for c in ALL_CONFIGS if c != headline] if sweep else []
 
     import torch                                              # (importing torch and counting devices does not initialise the GPU)
 
     # live counter passes: children under rocprofv3, BEFORE this process touches the GPU (only in the single-process run)
     pmc = None
-    if not distributed and not args.no_pmc:
+    if args.full and not distributed and not args.no_pmc:
         if torch.cuda.device_count() < 1:
             print("bench.py: no GPU visible", file=sys.stderr)
             sys.exit(2)
@@ -1006,15 +1055,16 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
+    torch.manual_seed(INPUT_SEED + rank)
 
-    want_host = world == 1 and not args.no_cpu_baseline
+    want_host = args.full and world == 1 and not args.no_cpu_baseline
     w = Workload(headline, device, args.batch_log2, rank, world, weights_path=args.weights)
     if w.feat is not None and distributed:
         from rotationnormflow_amd.dist import calibrate_feature_scale
         calibrate_feature_scale(w.fl, w.feat)                 # one calibration for all ranks: identical packed images (dist.py)
-    head = measure(w, args, dist, pmc, args.steps, args.warmup, not args.no_secondary, want_host,
-                   (4096, 65536) if want_host else None, 36.0)
-    state = device_state(w) if (rank == 0 and world == 1) else None
+    head = measure(w, args, dist, pmc, args.steps, args.warmup, args.full and not args.no_secondary, want_host,
+                   (4096, 65536) if want_host else None, 36.0, dump_dir=args.dump_outputs if rank == 0 else None)
+    state = device_state(w) if (args.full and rank == 0 and world == 1) else None
     configs = {}
     prev = w
     for name in others:
@@ -1027,7 +1077,7 @@ def main():
         sizes = ((4096,) if w.wl["direction"] == "forward" else (1024,)) if want_host else None
         second = not args.no_secondary and not w.weights_path      # (the trained-weights entries: default arithmetic, both directions)
         configs[name] = measure(w, args, None, pmc, c_steps, 3, second, want_host, sizes, 10.0, blocks=2)
-    if full and rank == 0:
+    if sweep and rank == 0:
         w.R = w.feat = None
         torch.cuda.empty_cache()
         configs["train"] = measure_training(device)           # the reference's training step, on the driver's clock too
@@ -1042,7 +1092,7 @@ def main():
         assert ranks_seen == dist.get_world_size() == world, (ranks_seen, dist.get_world_size(), world)
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world > 1 and not args.no_cpu_baseline:
         # N > 1: a short CPU baseline and the parity block of rank 0's shard, after the timed region and after the collectives
         host_legs(w, head, True, (4096,), 8.0)
     if rank == 0:

@@ -5,13 +5,14 @@ Every reference entry point that loads a checkpoint (eval.py:23, eval_unconditio
 ``optim.Adam(self.flow.parameters())``.  tests/agent_replay.py replays those statements.  Covered here, both directions:
   (a) a checkpoint the REFERENCE wrote (tests/golden/traj_c1_step10.pth: its own Flow + Adam, per-tensor optimizer state, written by
       make_trained.py with Agent.save_ckpt's statements) loads into the drop-in agent and is written back entry for entry;
-  (b) a checkpoint the DROP-IN agent writes loads into a per-tensor implementation -- this repo's ``Flow(config)`` always, the reference's
-      own ``flow.flow.Flow`` when /root/reference is present -- and the next Adam step is the same arithmetic on both sides.
+  (b) a checkpoint the DROP-IN agent writes loads into a per-tensor implementation -- this repo's ``Flow(config)``, and a module laid out
+      as the reference's own ``flow.flow.Flow`` (its ``get_flow`` is ``Flow(config)``): the parameter and state-dict names, order and
+      shapes recorded from it in tests/golden/param_order.json -- and the next Adam step is the same arithmetic on both sides.
 """
 import contextlib
 import io
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -23,7 +24,6 @@ from tests.agent_replay import ReplayedAgent
 from tests.golden.trained_cases import TRAJ
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
 REF_CKPT = os.path.join(GOLDEN, "traj_c1_step10.pth")
 
 
@@ -41,24 +41,27 @@ def classic_get_flow(cfg):
 
 
 def reference_get_flow():
-    """The reference's own ``get_flow`` (build container only; two third-party stand-ins from oracle/stubs), or None."""
-    if not os.path.isdir(REF):
-        return None
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    saved_path, saved_mods = list(sys.path), {k: v for k, v in sys.modules.items() if k == "flow" or k.startswith("flow.") or k == "utils" or k.startswith("utils.")}
-    for k in saved_mods:
-        del sys.modules[k]
-    sys.path[:0] = [os.path.join(root, "oracle", "stubs"), REF]
-    try:
-        import flow.flow as ref_flow_mod
-        assert ref_flow_mod.__file__.startswith(REF)
-        fn = ref_flow_mod.get_flow
-    finally:
-        sys.path[:] = saved_path
-        for k in [k for k in sys.modules if k == "flow" or k.startswith("flow.") or k == "utils" or k.startswith("utils.")]:
-            del sys.modules[k]
-        sys.modules.update(saved_mods)
-    return lambda cfg: quiet(fn, cfg)
+    """A ``get_flow`` whose module has the reference Flow's per-tensor layout for the trajectory structure: every parameter under its
+    dotted name, in the order the reference registers them (tests/golden/param_order.json, written by make_param_order.py from the
+    reference's own ``Flow``).  The checkpoint path never runs the flow, so names, order and shapes are all of the reference it touches."""
+    with open(os.path.join(GOLDEN, "param_order.json")) as fh:
+        layout = json.load(fh)["traj_c1"]
+    assert layout["cfg"] == TRAJ["traj_c1"]["cfg"]
+
+    def build(cfg):
+        root = torch.nn.Module()
+        for name, shape in layout["parameters"]:
+            *path, leaf = name.split(".")
+            mod = root
+            for part in path:
+                if part not in mod._modules:
+                    mod.add_module(part, torch.nn.Module())
+                mod = mod._modules[part]
+            mod.register_parameter(leaf, torch.nn.Parameter(torch.zeros(shape)))
+        assert [[k, list(p.shape)] for k, p in root.named_parameters()] == layout["parameters"]
+        assert [[k, list(v.shape)] for k, v in root.state_dict().items()] == layout["state_dict"]
+        return root
+    return build
 
 
 def cfg_traj():
@@ -121,8 +124,6 @@ def test_reference_written_checkpoint_loads_through_the_default_dropin(tmp_path)
 @pytest.mark.parametrize("target", ["classic", "reference"])
 def test_dropin_written_checkpoint_resumes_in_a_per_tensor_implementation(tmp_path, target):
     other = classic_get_flow if target == "classic" else reference_get_flow()
-    if other is None:
-        pytest.skip("reference tree not present on this box")
     cfg = cfg_traj()
     src = ReplayedAgent(cfg, quiet_get_flow, "cpu")
     src.load_ckpt(REF_CKPT)

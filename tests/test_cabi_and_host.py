@@ -345,3 +345,30 @@ def test_bench_compact_line_stays_parseable_and_small():
     line = bench.compact_record(fat, "bench_full.json")
     rec = json.loads(line)
     assert len(line) < bench.COMPACT_LIMIT and rec["value"] == json.loads(bench.compact_record(full))["value"] and "roofline" in rec
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_under_its_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files, at most DUMP_LIMIT bytes in all; beyond it the batch-sized arrays keep the
+    same seeded rows (sorted, one choice for all of them) in every run, the smaller arrays stay whole."""
+    import numpy as np
+    import torch
+    import bench
+    n = 4096
+    outputs = {"rotation": torch.arange(n * 9, dtype=torch.float32).reshape(n, 3, 3), "logp": torch.arange(n, dtype=torch.float32),
+               "estimate": torch.ones(8, 3, 3, dtype=torch.float32)}
+    tot = np.array([-123.5, float(n)])
+    bench.dump_outputs(outputs, tot, str(tmp_path / "whole"))
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in ("rotation", "logp", "estimate", "sum_count")}
+    assert np.array_equal(got["logp"], outputs["logp"].numpy()) and got["rotation"].shape == (n, 3, 3) and got["logp"].dtype == np.float32
+    assert got["sum_count"].dtype == np.float64 and np.array_equal(got["sum_count"], tot)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 60_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(outputs, tot, str(tmp_path / d))
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= 60_000
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in got}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in got}
+    rows = a["logp"].astype(np.int64)
+    assert 0 < rows.size < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["rotation"], outputs["rotation"].numpy()[rows]) and a["estimate"].shape == (8, 3, 3)
+    for k in got:
+        assert np.array_equal(a[k], b[k]), k

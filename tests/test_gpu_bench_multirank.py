@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +58,7 @@ def test_two_ranks_one_json_line():
         port = s.getsockname()[1]
     env = dict(os.environ, RNF_BENCH_SHARED_GPU="1", RNF_BENCH_HANG_DUMP="150")     # a hung rank dumps its stacks and exits
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-log2", "15"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-log2", "15", "--full"]
     out = _run(cmd, env)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = _compact(out)
@@ -99,7 +100,7 @@ def test_more_gpus_than_the_box_has_fails_loudly():
 
 
 def test_single_gpu_line_carries_both_arithmetics_and_every_config_runs():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "16", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "16", "--full", "--no-cpu-baseline",
                           "--no-configs", "--no-pmc"], cwd=ROOT, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
     short, rec = _compact(out), _full(out)
@@ -122,6 +123,32 @@ def test_single_gpu_line_carries_both_arithmetics_and_every_config_runs():
         rec = _compact(out)
         assert rec["value"] > 0 and rec["config"]["workload"].startswith(cfg)
 
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the run times the headline alone: no counter passes, no second arithmetic, no oracle or CPU legs, no other config.
+    --dump-outputs writes what the last timed step handed its caller; the same arguments give the same inputs, so two runs of an inverse
+    workload (base samples drawn on the device) dump the same rows."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"]
+    out = subprocess.run(base + ["--batch-log2", "15", "--dump-outputs", str(tmp_path / "c2")], cwd=ROOT, capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    short, rec = _compact(out), _full(out)
+    assert short["steps"] == 3 and short["ms_per_step"] > 0 and rec["config"]["workload"].startswith("C2")
+    for k in ("pmc", "configs", "secondary", "strict", "value_strict", "value_fp32_exact", "parity", "cpu_baseline", "device_state"):
+        assert k not in rec, k
+    logp, sc = np.load(tmp_path / "c2" / "logp.npy"), np.load(tmp_path / "c2" / "sum_count.npy")
+    assert logp.dtype == np.float32 and logp.shape == (1 << 15,) and np.isfinite(logp).all()
+    assert sc.dtype == np.float64 and sc[1] == 1 << 15 and -sc[0] / sc[1] == rec["mean_nll"]
+    assert abs(-logp.astype(np.float64).mean() - rec["mean_nll"]) < 1e-6 * abs(rec["mean_nll"])
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run(base + ["--batch-log2", "14", "--config", "C5u", "--dump-outputs", str(tmp_path / run)], cwd=ROOT,
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("rotation", "logp", "sum_count")})
+    assert dumps[0]["rotation"].shape == (1 << 14, 3, 3) and dumps[0]["rotation"].dtype == np.float32
+    for k in dumps[0]:
+        assert np.allclose(dumps[0][k], dumps[1][k], rtol=1e-5, atol=1e-5), k
 
 def test_rccl_leg_executes_under_a_launcher_on_one_gpu():
     """torchrun --nproc-per-node 1: the rank initialises the nccl (= RCCL) process group on its GPU and the barrier and the all-reduce of
@@ -163,7 +190,8 @@ def test_c3_strong_scaling_splits_one_global_batch():
 
 
 def test_default_line_has_the_reference_noise_beside_its_parity():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "16", "--no-configs", "--no-pmc"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "16", "--full", "--no-configs",
+                          "--no-pmc"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     short, rec = _compact(out), _full(out)
@@ -178,7 +206,7 @@ def test_full_line_carries_every_config_with_live_counters():
     """The default invocation (here at 2^15 rotations so that it takes seconds): ONE JSON line with the C2 headline, the exact-fp32 co-headline
     and a `configs` object for C1, C3, C4, C5, C5u -- each with both arithmetics, a parity block, a CPU baseline and a roofline whose HBM
     traffic and VALU / matrix-pipe fractions come from rocprofv3 --pmc passes run by this very process (children, before it touches the GPU)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "15"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch-log2", "15", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     short, rec = _compact(out), _full(out)
@@ -228,7 +256,7 @@ def test_eight_ranks_weak_and_strong_equal_the_single_rank_statistic():
     port, one JSON line from rank 0).  C2, weak: 8 x 2^14 rotations.  C3, strong: ONE global batch split 8 ways (`rotations_per_gpu` =
     global / 8) whose reduced mean NLL equals the one-rank evaluation of the same batch to fp64 addition order -- every shard reproduces its
     rows bit for bit whatever launch shape its size selects (tests/test_gpu_scale_properties.py)."""
-    weak = _self_launch(["--gpus", "8", "--steps", "2", "--warmup", "1", "--batch-log2", "14", "--no-secondary"])
+    weak = _self_launch(["--gpus", "8", "--steps", "2", "--warmup", "1", "--batch-log2", "14", "--full", "--no-secondary"])
     assert weak.returncode == 0, weak.stderr[-2000:]
     r = _compact(weak)
     assert r["n_gpus"] == 8 and r["rccl_ranks"] == 8 and r["scaling"] == "weak" and r["config"]["global_batch"] == 8 << 14
@@ -246,7 +274,7 @@ def test_eight_ranks_weak_and_strong_equal_the_single_rank_statistic():
     assert abs(r1["mean_nll"] - r8["mean_nll"]) <= 1e-12 * abs(r1["mean_nll"])
     # the STRONG-scaling line as the driver would launch it (CPU baseline and counters on): every contract key, `roofline`,
     # `cpu_baseline` (its sample as numbers, "cores of threads_available") and the rank count read back from the communicator, under 3 KB
-    strong = _self_launch(["--config", "C3", "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch-log2", "17", "--no-secondary"])
+    strong = _self_launch(["--config", "C3", "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch-log2", "17", "--full", "--no-secondary"])
     assert strong.returncode == 0, strong.stderr[-2000:]
     c = _compact(strong)
     assert c["scaling"] == "strong" and c["n_gpus"] == 8 and c["rccl_ranks"] == 8 and c["config"]["workload"].startswith("C3")

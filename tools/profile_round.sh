@@ -8,10 +8,10 @@ set -u
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/${1:-round}
 mkdir -p $OUT
-# 1. the default invocation, exactly as the driver runs it (+ the live PMC summary kept as pmc_live.json: bench.py replays it only if rocprofv3
+# 1. the --full invocation (+ the live PMC summary kept as pmc_live.json: bench.py replays it only if rocprofv3
 #    is missing on a box AND the kernel sources are unchanged)
-#    bench_default.json = the FULL record (the BENCH_FULL line / bench_full.json); bench_compact.json = the last stdout line the driver parses
-python3 bench.py --save-pmc $OUT --full-out $OUT/bench_default.json > $OUT/bench_stdout.txt 2> $OUT/bench.err
+#    bench_default.json = the FULL record (the BENCH_FULL line / bench_full.json); bench_compact.json = its last stdout line
+python3 bench.py --full --save-pmc $OUT --full-out $OUT/bench_default.json > $OUT/bench_stdout.txt 2> $OUT/bench.err
 tail -n 1 $OUT/bench_stdout.txt > $OUT/bench_compact.json
 rm -f $OUT/bench_stdout.txt
 # 2. kernel-trace statistics of the per-config commands (no PMC in these runs: timing and counters are never mixed)
