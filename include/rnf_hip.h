@@ -379,6 +379,13 @@ int rnf_fisher_log_prob(const float *rotation_dev, int64_t n, const float *fishe
  * between estimate i and the closest of its k ground-truth rotations.  est_dev float[n][9], gt_dev float[n][k][9], out_dev float[n]. */
 int rnf_min_geodesic(const float *est_dev, const float *gt_dev, int64_t n, int32_t k, float *out_dev, void *stream);
 
+/* Equivolumetric HEALPix grid over SO(3) for grid-search pose estimation, generated on the device already offset (replaces the host build of
+ * utils/sd.py:47-82 generate_healpix_grid -- healpy's pix2vec in the RING ordering, scipy's from_euler, numpy's einsum -- and eval.py:440-442's
+ * per-batch `samples = grid @ random_rot`).  out_dev float[72 * 8^level][3][3], row t * npix + p = Rx(phi_p) Rz(theta_p) Rx(tau_t) O with
+ * nside = 2^level, npix = 12 nside^2, (theta_p, phi_p) the centre of pixel p, tau_t = 2 pi t / (6 nside), O = offset9_dev (row-major device
+ * float[9]) or the identity when NULL.  fp64 inside, one rounding to fp32 per entry.  level 0..8 (level 8: 1.2e9 rows, 43 GB). */
+int rnf_so3_healpix_grid(int32_t level, const float *offset9_dev, float *out_dev, void *stream);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

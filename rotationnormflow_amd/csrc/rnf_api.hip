@@ -1899,6 +1899,72 @@ extern "C" int rnf_min_geodesic(const float *est, const float *gt, int64_t n, in
     return 0;
 }
 
+// Equivolumetric SO(3) grid of the grid-search pose estimate (utils/sd.py:47-82 generate_healpix_grid, offset on the right as eval.py:440-442
+// `grid @ random_rot`): row r = t * npix + p is Rx(phi_p) Rz(theta_p) Rx(tau_t) O, with (cos theta_p, phi_p) the centre of HEALPix pixel p
+// in the RING ordering for nside = 2^level (Gorski et al. 2005, pix2ang_ring), tau_t = 2 pi t / (6 * 2^level) (np.linspace(..., endpoint=
+// False)), Rx / Rz active rotations (scipy's from_euler("X" / "Z")).  fp64 throughout, one rounding per entry at the store.
+__device__ inline long long isqrt_ll(long long v) {
+    long long s = (long long)sqrt((double)v);
+    while (s * s > v) --s;
+    while ((s + 1) * (s + 1) <= v) ++s;
+    return s;
+}
+
+__global__ void so3_healpix_grid_kernel(int level, long long rows, const float *offset, float *out) {
+    const long long nside = 1LL << level, npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1);
+    const double pi = M_PI, tilt_step = 2.0 * M_PI / (double)(6LL << level);
+    double o[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (offset)
+        for (int c = 0; c < 9; ++c) o[c] = (double)offset[c];
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
+        const long long t = r / npix, p = r - t * npix;
+        double z, sth, phi;                                      // cos / sin of the polar angle, azimuth
+        if (p < ncap) {                                          // north polar cap: ring i holds 4 i pixels
+            const long long i = (1 + isqrt_ll(1 + 2 * p)) >> 1, j = p + 1 - 2 * i * (i - 1);
+            const double tmp = (double)(i * i) / (double)(3 * nside * nside);
+            z = 1.0 - tmp;
+            sth = sqrt(tmp * (2.0 - tmp));
+            phi = ((double)j - 0.5) * pi / (double)(2 * i);
+        } else if (p < npix - ncap) {                            // belt: 2 nside + 1 rings of 4 nside pixels
+            const long long q = p - ncap, i = q / (4 * nside) + nside, j = q % (4 * nside) + 1;
+            const double f = ((i + nside) & 1) ? 1.0 : 0.5;
+            z = (double)(2 * nside - i) * 2.0 / (double)(3 * nside);
+            sth = sqrt((1.0 - z) * (1.0 + z));
+            phi = ((double)j - f) * pi / (double)(2 * nside);
+        } else {                                                 // south polar cap, mirrored
+            const long long q = npix - p, i = (1 + isqrt_ll(2 * q - 1)) >> 1, j = 4 * i + 1 - (q - 2 * i * (i - 1));
+            const double tmp = (double)(i * i) / (double)(3 * nside * nside);
+            z = tmp - 1.0;
+            sth = sqrt(tmp * (2.0 - tmp));
+            phi = ((double)j - 0.5) * pi / (double)(2 * i);
+        }
+        double sphi, cphi, stau, ctau;
+        sincos(phi, &sphi, &cphi);
+        sincos((double)t * tilt_step, &stau, &ctau);
+        // Rx(phi) Rz(theta): columns (cos t, cphi sin t, sphi sin t), (-sin t, cphi cos t, sphi cos t), (0, -sphi, cphi); then Rx(tau)
+        // mixes the last two columns
+        const double a[9] = {z, -sth * ctau, sth * stau,
+                             cphi * sth, cphi * z * ctau - sphi * stau, -cphi * z * stau - sphi * ctau,
+                             sphi * sth, sphi * z * ctau + cphi * stau, -sphi * z * stau + cphi * ctau};
+        float *dst = out + r * 9;
+        for (int row = 0; row < 3; ++row)
+            for (int col = 0; col < 3; ++col)
+                dst[row * 3 + col] = (float)(a[row * 3] * o[col] + a[row * 3 + 1] * o[3 + col] + a[row * 3 + 2] * o[6 + col]);
+    }
+}
+
+extern "C" int rnf_so3_healpix_grid(int32_t level, const float *offset, float *out, void *stream) {
+    if (level < 0 || level > 8) return fail("rnf_so3_healpix_grid: level=%d outside 0..8 (72 * 8^level rotations)", level);
+    if (!out) return fail("rnf_so3_healpix_grid: null output pointer");
+    const long long rows = 72LL << (3 * level);
+    long long blocks = (rows + 255) / 256;
+    if (blocks > (1LL << 20)) blocks = 1LL << 20;
+    hipLaunchKernelGGL(so3_healpix_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (int)level, rows,
+                       offset, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // log-constants of MatrixFisherN(A, norm_type) (utils/fisher.py:67-76,79-97): c = s0 + s1 + s2 + log norm with the PROPER singular values
 // of A (fisher_math.h).  One thread per matrix, fp64, so that a per-sample A coming out of a network never goes through a host SVD and a
 // device->host sync.  scratch (doubles): [0] = Q = sum_b |A_b|_F^2 (norm_type 0 is batch-coupled through it), [1] = W, [2 + 10 b ..] =

@@ -346,6 +346,92 @@ def estimate_rotations(flow: Flow, feature: torch.Tensor, queries: torch.Tensor 
     return est, log_prob
 
 
+# Rotations per launch of the grid search: images are grouped up to about 2^21 rotations (the regime the shared-row kernels are measured
+# in); a single image's grid larger than GRID_MAX_LAUNCH_ROWS is evaluated in chunks of that size.  Flows with side layers take one feature
+# row per rotation (runtime.expand_shared_rows), so their launches are kept to GRID_SIDE_LAUNCH_ROWS to bound the expanded features.
+GRID_LAUNCH_ROWS = 1 << 21
+GRID_MAX_LAUNCH_ROWS = 1 << 24
+GRID_SIDE_LAUNCH_ROWS = 1 << 18
+
+
+def grid_estimate_rotations(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None,
+                            base=None, images_per_launch: int = None):
+    """Grid-search pose estimate of ``eval.py``'s ``log_pdf`` mode (eval.py:437-462): evaluate each image's log-density on the HEALPix grid
+    over SO(3) (``utils.sd``; level ``recursion_level``, or the one closest to ``number_queries``, default 500, in log space) multiplied on
+    the right by ``offset`` [3,3] (None: one Haar-uniform rotation drawn from torch's generator, as ``trans.random_rotation()``), and keep
+    the grid point of largest log p (``torch.argmax``: the first on a tie).
+
+    feature [B,F] (None for an unconditional flow: B = the base's rows, or 1).  ``base``: None (uniform) or a ``MatrixFisherN`` with one row
+    (shared by every image) or B rows (row b scores image b's grid; its log-constants are sliced, never recomputed on a slice).
+    ``images_per_launch``: images evaluated per launch (default: as many as fit in about 2^21 rotations; 1 for flows with batch-coupled
+    layers, whose matrices come from the first rows of a launch, as in the reference's per-image chunks).
+    Returns (est [B,3,3], max_log_prob [B], index [B] into the grid, offset [3,3])."""
+    from .utils import sd
+    if not flow.condition:
+        feature = None
+    if feature is not None:
+        dev, B = feature.device, feature.shape[0]
+    else:
+        dev = base.A.device if base is not None else torch.device("cuda", torch.cuda.current_device())
+        B = base.A.reshape(-1, 3, 3).shape[0] if base is not None else 1
+    if dev.type != "cuda":
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    level = int(recursion_level) if recursion_level is not None else sd.closest_grid_level(500 if number_queries is None else number_queries)
+    if offset is None:
+        offset = sd.random_rotations(1)[0]
+    offset = offset.reshape(3, 3).to(device=dev, dtype=torch.float32)
+    A = c = None
+    if base is not None:
+        A = base.A.detach().reshape(-1, 3, 3).to(device=dev, dtype=torch.float32)
+        c = base.log_const().reshape(-1).to(device=dev, dtype=torch.float32)
+        if A.shape[0] not in (1, B):
+            raise ValueError(f"grid_estimate_rotations: the base has {A.shape[0]} rows for {B} images (1 or {B})")
+    coupled = any(getattr(m, "_rnf_batch_coupled", False) for m in flow.modules())
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        Q = grid.shape[0]
+        packed = flow._packed(dev, feature)
+        budget = GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_LAUNCH_ROWS
+        if images_per_launch is None:
+            images_per_launch = 1 if coupled else max(1, budget // Q)
+        g = min(int(images_per_launch), B)
+        if g < 1 or (coupled and g > 1):
+            raise ValueError(f"grid_estimate_rotations: images_per_launch={images_per_launch}" + (" (batch-coupled layers: 1)" if coupled else ""))
+        if g > 1 and g * Q > GRID_MAX_LAUNCH_ROWS:
+            raise ValueError(f"grid_estimate_rotations: {g} images of {Q} rotations exceed {GRID_MAX_LAUNCH_ROWS} rotations per launch")
+        chunk = Q if g > 1 else min(Q, GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_MAX_LAUNCH_ROWS)
+
+        def log_prob(rot, b0, b1):
+            feat = feature[b0:b1] if feature is not None else None
+            rows = (A, c) if A is None or A.shape[0] == 1 else (A[b0:b1], c[b0:b1])
+            return runtime.run_log_prob(flow, packed, rot, feat, *rows, feature_repeat=rot.shape[0] // (b1 - b0))["logp"]
+
+        bests, indices = [], []
+        rep = grid.repeat(g, 1, 1) if g > 1 else grid          # one image per launch: the grid itself, no copy
+        for b0 in range(0, B, g):
+            b1 = min(B, b0 + g)
+            if g > 1:
+                lp = log_prob(rep[:(b1 - b0) * Q], b0, b1).reshape(b1 - b0, Q)
+                idx = torch.argmax(lp, dim=-1)
+                bests.append(lp.gather(1, idx[:, None])[:, 0])
+                indices.append(idx)
+                continue
+            for lo in range(0, Q, chunk):                       # the first chunk's maximum wins a tie, a NaN wins as in torch.argmax
+                lp = log_prob(grid[lo:lo + chunk], b0, b1)
+                idx = torch.argmax(lp)
+                val = lp[idx]
+                if lo == 0:
+                    v, i = val, idx
+                else:
+                    take = (val > v) | (val.isnan() & ~v.isnan())
+                    v, i = torch.where(take, val, v), torch.where(take, idx + lo, i)
+            bests.append(v.reshape(1))
+            indices.append(i.reshape(1))
+        best, index = (bests[0], indices[0]) if len(bests) == 1 else (torch.cat(bests), torch.cat(indices))
+        est = grid[index]
+    return est, best, index, offset
+
+
 def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
     """[B,3,3] rotations -> unit quaternions [B,4] (real part first), largest-component branch per row."""
     m = R.reshape(-1, 3, 3)
@@ -403,10 +489,23 @@ def min_geodesic_distance(est_rotation: torch.Tensor, gt_rotation: torch.Tensor)
     return out
 
 
-def pose_accuracy(flow: Flow, feature, gt_rotation, queries=None, base=None, number_queries: int = 500, thresholds_deg=(15.0, 30.0)):
+def pose_accuracy(flow: Flow, feature, gt_rotation, queries=None, base=None, number_queries: int = 500, thresholds_deg=(15.0, 30.0),
+                  method: str = "log_inv", recursion_level: int = None, offset=None, refine_steps: int = 100):
     """What ``Agent.eval_acc`` + ``eval.py`` report per batch (agent.py:238-283, utils/utils.py:208-209): arg-max pose estimate, geodesic
-    error in degrees against the (possibly several) ground truths, accuracy at the thresholds.  -> dict(err_deg, est_rotation, acc)"""
-    est, _ = estimate_rotations(flow, feature, queries=queries, base=base, number_queries=number_queries)
+    error in degrees against the (possibly several) ground truths, accuracy at the thresholds.  -> dict(err_deg, est_rotation, acc)
+
+    ``method`` (eval.py:36-44): "log_inv" (default) pushes base samples through the inverse (``estimate_rotations``); "log_pdf" is the
+    grid search (``grid_estimate_rotations`` with ``number_queries`` / ``recursion_level`` / ``offset`` / ``base``); "nll_grad" refines the
+    grid estimate with ``refine_steps`` gradient steps at lr 1e-4 without a base term (eval.py:464-480)."""
+    if method == "log_inv":
+        est, _ = estimate_rotations(flow, feature, queries=queries, base=base, number_queries=number_queries)
+    elif method in ("log_pdf", "nll_grad"):
+        est = grid_estimate_rotations(flow, feature, number_queries=number_queries, recursion_level=recursion_level, offset=offset,
+                                      base=base)[0]
+        if method == "nll_grad":
+            est = refine_rotations(flow, feature, est, steps=refine_steps, lr=1e-4, base=None)
+    else:
+        raise ValueError(f"pose_accuracy: method must be 'log_inv', 'log_pdf' or 'nll_grad', got {method!r}")
     err_deg = torch.rad2deg(min_geodesic_distance(est, gt_rotation))
     return dict(err_deg=err_deg, est_rotation=est, acc={t: float((err_deg <= t).float().mean()) for t in thresholds_deg})
 
