@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define RNF_ABI_VERSION 7
+#define RNF_ABI_VERSION 8
 
 /* width of the conditioner MLP's hidden layers: flow/condition.py:9 (Nh=64, never overridden by any caller) */
 #define RNF_HIDDEN 64
@@ -41,8 +41,8 @@ extern "C" {
  *                            (the largest code of its layers), the returned grid cell is the same for either
  *   desc[i][6] fallback param_offset   } RNF_PREC_F16X2 flows only: offsets in the SAME blob of the layer's records packed with a strict
  *   desc[i][7] fallback feat_offset    } arithmetic (or -1; the feature-projection record is the RNF_PREC_FP32 image for either).  When
- *                            every MLP layer has them, each rnf_flow_forward / _inverse /
- *                            _log_prob call is GUARDED: a sample that ends non-finite (an fp16 operand left the fp16 range, |x| >= 65504;
+ *                            every MLP layer has them, each rnf_flow_pass call without states is GUARDED: a sample that ends
+ *                            non-finite (an fp16 operand left the fp16 range, |x| >= 65504;
  *                            flow/condition.py:24-30 has no such limit) sets a device flag and the strict kernels, launched right
  *                            behind on the same stream, redo the chunk -- they return at once when the flag is clear.  No host
  *                            synchronisation; int32 word 1 of the last 8 bytes of the first 32 KiB of the workspace is 1 after a call in
@@ -60,7 +60,7 @@ extern "C" {
 #define RNF_LAYER_COND9_POLAR_L 8 /* flow/rottrans.py:108-121     Condition9RotL                               */
 #define RNF_LAYER_COND9_POLAR_R 9 /* flow/rottrans.py:138-151     Condition9RotR                               */
 #define RNF_LAYER_COND36 10       /* flow/squeezetrans.py:334-347 Condition36Trans (record from rnf_pack_cond36) */
-/* layers whose per-sample matrix the CALLER builds and hands in (rnf_flow_*_side; desc param_offset = slot in the side buffer, no blob
+/* layers whose per-sample matrix the CALLER builds and hands in (RnfFlowPass.side; desc param_offset = slot in the side buffer, no blob
  * record): the reference forms these matrices with batched torch ops that are not a per-sample function -- ConditionRot's U^T V of a
  * batched SVD (flow/rottrans.py:37-66; depends on the SVD routine's sign conventions) and ConditionLU's torch.diag over the BATCH
  * dimension (flow/squeezetrans.py:121-131) -- so the host side reproduces them with the same torch calls on outputs of
@@ -112,8 +112,8 @@ int rnf_set_train_block(int rotations);
 
 /* ---- parameter packing (host side, pure CPU; called once per parameter version) ------------------------------
  * Sizes are in floats.  `segments` (K) is any positive count (flow/mobiusflow.py:7-14 takes any): records hold ceil(K / 8) fc_last tiles,
- * the last one zero padded, and the kernels give the pad segments weight 0.  rnf_flow_inverse keeps a layer's segment parameters in
- * registers (64 per lane; beyond K = 128 the rest streams through a per-wave stash, see rnf_workspace_bytes_segments); the training entry
+ * the last one zero padded, and the kernels give the pad segments weight 0.  An inverse pass keeps a layer's segment parameters in
+ * registers (64 per lane; beyond K = 128 the rest streams through a per-wave stash in RnfFlowPass.workspace); the training entry
  * points take K <= 512 (the conditioner outputs of a 16-rotation block live in LDS).  `feature_dim` (F) is the number of
  * feature inputs of the layer's MLP (0 for an unconditional Moebius layer).
  */
@@ -169,43 +169,59 @@ int rnf_pack_cond36(const float *fc_first_w, const float *fc_first_b, const floa
                     float *out_layer, float *out_feat);
 
 /* ---- the flow -------------------------------------------------------------------------------------------------
- * rotation_dev   [n,3,3] float32 row-major contiguous
- * feature_dev    [n,F] float32 row-major contiguous (F % 8 == 0), or NULL for an unconditional flow
- * rotation_out   [n,3,3] or NULL;  ldj_out [n] or NULL
- * workspace_dev  scratch of at least rnf_workspace_bytes(n, n_cond_layers) bytes (may be NULL when that is 0)
- * Aliasing: rotation_out == rotation_dev (in place) is allowed -- every lane reads its rotation before it writes it -- but such a call
- * runs WITHOUT the range guard (the exact-fp32 re-run would start from the already overwritten input): an fp16 overflow then shows as
- * NaN outputs instead of being repaired.  No other overlap between inputs and outputs is supported.
+ * One pass through a packed flow: Flow.forward (flow/flow.py:53-72; ldj = sum of forward log-det-Jacobians) or Flow.inverse
+ * (flow/flow.py:74-92: walks the table backwards; ldj = sum of inverse-map log-dets, MobiusFlow.inverse returns -ldj:
+ * flow/mobiusflow.py:183), optionally fused with the base density and the NLL sum, or saving the layer inputs for training.  Which of
+ * these a call is follows from the fields that are set; combinations no caller uses (log p with dir 1, states with feature_div or log p,
+ * side with feature_div) are refused.  Fields left zero / NULL are off.
  */
+typedef struct RnfFlowPass {
+    size_t struct_bytes;        /* sizeof(RnfFlowPass); any other value is refused (header and library differ) */
+    int32_t dir;                /* 0 Flow.forward, 1 Flow.inverse */
+    int32_t feature_dim;        /* F, a multiple of 8 (pad on the host) */
+    const float *rotation;      /* dev [n,3,3] float32 row-major contiguous */
+    const float *feature;       /* dev [n,F] row-major contiguous, or NULL for an unconditional flow */
+    int64_t n;
+    /* > 0: shared feature rows.  `feature` holds n / feature_div rows and row r conditions rotations [r * feature_div, (r + 1) *
+     * feature_div) -- the pose-estimation pattern of Agent.eval_acc (agent.py:238-263) and the density of one image on a grid of
+     * rotations (eval.py:444-462), where the reference materialises feature.repeat(number_queries).  The feature projection runs once per
+     * row.  n must be a multiple of feature_div; an inverse pass takes at most 128 segments here. */
+    int64_t feature_div;
+    /* dev float[n_side_layers][n][16]: the per-sample matrices of the RNF_LAYER_SIDE* layers (row-major; 3x3 ones in the first 9 floats),
+     * in side-slot order.  Required when the flow has such layers. */
+    const float *side;
+    const float *blob;          /* dev: the packed parameter blob */
+    const int32_t *desc;        /* host: int32 [n_layers][RNF_DESC_STRIDE] */
+    int32_t n_layers, segments;
+    /* Fused density evaluation (dir 0): Flow.forward + MatrixFisherN(A)._log_prob(R') + the NLL accumulation (agent.py:54-65,217-229;
+     * utils/fisher.py:217-232).  fisher_A dev [B,3,3], fisher_c dev [B] with c_b = sum(S_b) + log(norm_b) (the host precomputes the proper
+     * singular values, utils/fisher.py:67-76,93-97); sample i uses row i / (n / B) (fisher.py:226).  Both NULL (and B = 0): a uniform
+     * base; one without the other is refused. */
+    const float *fisher_A, *fisher_c;
+    int64_t fisher_B;
+    float *rotation_out;        /* dev [n,3,3] or NULL.  == rotation (in place) is allowed -- every lane reads its rotation before it writes
+                                 * it -- but such a call runs WITHOUT the range guard (the exact-fp32 re-run would start from the already
+                                 * overwritten input): an fp16 overflow then shows as NaN outputs instead of being repaired.  No other
+                                 * overlap between inputs and outputs is supported. */
+    float *ldj_out;             /* dev [n] or NULL */
+    float *logp_out;            /* dev [n] or NULL (dir 0): per-sample log p = ldj + base */
+    double *sum_out;            /* dev double[2] or NULL (dir 0): {sum_i log p_i, n}, accumulated in fp64 in a fixed order
+                                 * (deterministic); written also when n == 0 */
+    /* dev float[n_layers][n][9] or NULL: a training pass, which also saves the rotation entering every ITERATION position (dir 0: every
+     * layer; dir 1: position 0 = the last flow layer) for rnf_flow_backward_pass.  Needs rotation_out; runs unguarded. */
+    float *states;
+    /* dev scratch of at least rnf_flow_pass_workspace_bytes(this struct) bytes: the block partials, the guard word (int32 word 1 of the
+     * last 8 bytes of the first 32 KiB is 1 after a call in which the exact-fp32 re-run happened, see desc columns 6, 7), the feature
+     * projection of the conditional layers and the per-wave stash of an inverse pass with more than 128 segments. */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfFlowPass;
+int rnf_flow_pass(const RnfFlowPass *pass);
+/* The workspace rnf_flow_pass requires for the same struct (the workspace fields are not read); 0 when struct_bytes is wrong. */
+size_t rnf_flow_pass_workspace_bytes(const RnfFlowPass *pass);
+/* Partials block + the feature-projection scratch of n_cond_layers conditional layers (the workspace of rnf_cond_mlp_forward). */
 size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers);
-/* the same plus the per-wave stash an INVERSE pass with more than 128 segments needs (equal to rnf_workspace_bytes up to 128) */
-size_t rnf_workspace_bytes_segments(int64_t n, int32_t n_cond_layers, int32_t segments);
-
-/* Flow.forward (flow/flow.py:53-72): ldj = sum of forward log-det-Jacobians. */
-int rnf_flow_forward(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                     const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                     float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes,
-                     void *stream);
-
-/* Flow.inverse (flow/flow.py:74-92): walks the table backwards; ldj = sum of inverse-map log-dets
- * (MobiusFlow.inverse returns -ldj: flow/mobiusflow.py:183). */
-int rnf_flow_inverse(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                     const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                     float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes,
-                     void *stream);
-
-/* The same three calls for flows that contain RNF_LAYER_SIDE* layers: side_dev float[n_side_layers][n][16] (row-major matrices; 3x3 ones
- * in the first 9 floats). */
-int rnf_flow_forward_side(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, const float *side_dev,
-                          const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                          float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
-int rnf_flow_inverse_side(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, const float *side_dev,
-                          const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                          float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
-int rnf_flow_log_prob_side(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, const float *side_dev,
-                           const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments, const float *fisher_A_dev,
-                           const float *fisher_c_dev, int64_t fisher_B, float *rotation_out_dev, float *ldj_out_dev, float *logp_out_dev,
-                           double *sum_out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ConditionRot (flow/rottrans.py:37-66): the per-sample orthogonal 4x4 matrices U^T V of svd(I + reshape(mlp_out, 4, 4)), with the sign
  * conventions of the reference's torch.svd (LAPACK's dense-SVD path restated for 4x4, csrc/svd4_lapack.h; identical for >= 99.8 % of
@@ -266,110 +282,71 @@ size_t rnf_plain_layer_floats(int32_t kind, int32_t segments, int32_t feature_di
 int rnf_pack_flow_device(const float *plain_dev, const int32_t *pack_desc, int32_t n_layers, int32_t segments,
                          int32_t feature_dim, int32_t precision, float *blob_dev, int32_t *flags_dev, void *stream);
 
-/* Flow.forward that also saves the rotation entering every layer: states_dev float[n_layers][n][9]. */
-int rnf_flow_forward_train(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                           const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                           float *rotation_out_dev, float *ldj_out_dev, float *states_dev, void *workspace_dev,
-                           size_t workspace_bytes, void *stream);
-
-/* rnf_flow_forward_train for small batches, from the PLAIN parameter blob (the layout rnf_flow_backward reads: no packing step) on
+/* Training forward for small batches, from the PLAIN parameter blob (the layout rnf_flow_backward_pass reads: no packing step) on
  * 16-rotation workgroups in exact fp32 (csrc/train_block16.h) -- the arithmetic of the backward sweep's own forward recompute.  Replaces
  * Flow.forward inside the training step (agent.py:75-92) for flows made of Moebius, Uncondition16Trans / UnconditionRot and
- * Condition16Trans layers, n_layers <= 200, segments <= 512; other flows are refused (use rnf_flow_forward_train).  train_desc: the
- * table of rnf_flow_backward; feature_dev [n][feature_dim], unpadded. */
+ * Condition16Trans layers, n_layers <= 200, segments <= 512; other flows are refused (use rnf_flow_pass with states).  train_desc: the
+ * table of rnf_flow_backward_pass; feature_dev [n][feature_dim], unpadded; states_dev float[n_layers][n][9]. */
 int rnf_flow_forward_train_plain(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
                                  const float *plain_dev, const int32_t *train_desc, int32_t n_layers, int32_t segments,
                                  float *rotation_out_dev, float *ldj_out_dev, float *states_dev, float *acts_dev, void *stream);
 /* acts_dev (may be NULL): rnf_train_acts_floats(n, conditioner layers, segments) floats in which the forward leaves every conditioner's
- * activations (2 KB per rotation and layer at 64 segments); rnf_flow_backward_saved -- rnf_flow_backward with that buffer -- then reads them
- * back instead of recomputing each conditioner (16-rotation sweep; the 64-rotation sweep of large batches ignores the buffer). */
+ * activations (2 KB per rotation and layer at 64 segments), for RnfFlowBackward.acts. */
 size_t rnf_train_acts_floats(int64_t n, int32_t n_conditioner_layers, int32_t segments);
-int rnf_flow_backward_saved(const float *states_dev, const float *acts_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                            const float *plain_dev, const int32_t *train_desc, int32_t n_layers, int32_t segments,
-                            const float *g_rotation_out_dev, const float *g_ldj_dev, float *grads_dev, float *g_rotation_in_dev,
-                            float *g_feature_dev, float *layer_scratch_dev, void *stream);
 
-/* Reverse sweep of Flow.forward (what autograd does for the reference, agent.py:79-80).
- * In : g_rotation_out_dev [n][9] (NULL = zeros), g_ldj_dev [n].
- * Out: grads_dev (plain layout, ACCUMULATED into: zero it first; NULL = skip every parameter gradient, for callers that only
- *      differentiate w.r.t. the inputs: pose refinement, eval.py:464-478), g_rotation_in_dev [n][9],
- *      g_feature_dev [n][F] (accumulated into; may be NULL).
- * Scratch: layer_scratch_dev float[n_layers], zeroed by the caller (batch sums of dL/dldj for the d log|det M| / dM term).
- * Any segment count 1..512 (the conditioner outputs of a 16-rotation block live in LDS), n_layers <= 400 like the forward passes (beyond 200
- * the sweep runs in chunks of 200 layers; g_rotation_in_dev then also carries the gradient between the chunks and may alias
- * g_rotation_out_dev). */
-int rnf_flow_backward(const float *states_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                      const float *plain_dev, const int32_t *train_desc, int32_t n_layers, int32_t segments,
-                      const float *g_rotation_out_dev, const float *g_ldj_dev, float *grads_dev, float *g_rotation_in_dev,
-                      float *g_feature_dev, float *layer_scratch_dev, void *stream);
+/* Reverse sweep of a training pass (RnfFlowPass with states): what autograd does for the reference, agent.py:79-80.  dir 1 gives the
+ * gradients THROUGH Flow.inverse (flow/flow.py:74-92; MobiusFlow.inverse with BinFind.backward's implicit-function gradient of the root,
+ * flow/mobiusflow.py:247-273; the affine layers apply M^-1, flow/squeezetrans.py:51-55,171-174).  Any segment count 1..512 (the
+ * conditioner outputs of a 16-rotation block live in LDS), n_layers <= 400 like the forward passes (beyond 200 the sweep runs in chunks of
+ * 200 layers).  Fields left zero / NULL are off. */
+typedef struct RnfFlowBackward {
+    size_t struct_bytes;        /* sizeof(RnfFlowBackward); any other value is refused (header and library differ) */
+    int32_t dir;                /* direction of the training pass: 0 Flow.forward, 1 Flow.inverse */
+    int32_t feature_dim;        /* F (unpadded) */
+    const float *states;        /* dev float[n_layers][n][9]: what the training pass saved */
+    /* dir 1: dev [n][9], the output of the inverse pass (each Moebius layer reads its root back from its own output, no second root
+     * search); required there, unused for dir 0 */
+    const float *rotation_out;
+    const float *feature;       /* dev [n][F] or NULL */
+    int64_t n;
+    /* dev: the plain blob (see "training" above); may be NULL when `side` is set and no layer has plain parameters */
+    const float *plain;
+    /* host int32 [n_layers][3] in the order the pass visited the layers (dir 1: reversed).  A side layer's slot goes into bits 16..23 of
+     * its kind word, its plain offset is unused (rnf_plain_layer_floats = 0). */
+    const int32_t *train_desc;
+    int32_t n_layers, segments;
+    /* dev or NULL (dir 0): the activations rnf_flow_forward_train_plain left for the same n, table and K -- every layer must be a kind it
+     * runs.  The 16-rotation sweep reads them back instead of recomputing each conditioner; the 64-rotation sweep of large batches
+     * ignores them. */
+    const float *acts;
+    /* Side layers (RNF_LAYER_SIDE16 / SIDE16_ROT / SIDE9: Condition16TransLU, ConditionRot, Condition9TransLU; flow/squeezetrans.py:
+     * 134-144,264-277, flow/rottrans.py:37-66): the caller builds their per-sample matrices with the reference's own tensor ops (the LU
+     * layers' torch.diag couples the batch; ConditionRot's U^T V follows torch.svd's conventions), so the gradient chain is split.  side:
+     * the RnfFlowPass.side buffer of the pass; side_grad: dev float[n_side][n][16] out, dL/d(matrix) (same layout) for the caller's
+     * autograd to carry through those ops into the conditioner networks (rnf_cond_mlp_backward).  Both required when the flow has such
+     * layers. */
+    const float *side;
+    float *side_grad;
+    const float *g_rotation_out;    /* dev [n][9] or NULL (= zeros) */
+    const float *g_ldj;             /* dev [n] */
+    /* dev, plain layout, ACCUMULATED into: zero it first; NULL = skip every parameter gradient, for callers that only differentiate
+     * w.r.t. the inputs: pose refinement, eval.py:464-478 */
+    float *grads;
+    /* dev [n][9] out: the gradient w.r.t. the rotations GIVEN to the pass.  Beyond 200 layers it also carries the gradient between the
+     * chunks and may alias g_rotation_out. */
+    float *g_rotation_in;
+    float *g_feature;               /* dev [n][F], ACCUMULATED into, or NULL */
+    float *layer_scratch;           /* dev float[n_layers], zeroed by the caller (batch sums of dL/dldj for the d log|det M| / dM term) */
+    void *stream;
+} RnfFlowBackward;
+int rnf_flow_backward_pass(const RnfFlowBackward *pass);
 
-/* Gradients THROUGH Flow.inverse (flow/flow.py:74-92; MobiusFlow.inverse with BinFind.backward's implicit-function gradient of the
- * root, flow/mobiusflow.py:247-273; the affine layers apply M^-1, flow/squeezetrans.py:51-55,171-174).
- * rnf_flow_inverse_train is rnf_flow_inverse that also saves the rotation entering every ITERATION position of the inverse pass
- * (position 0 = the last flow layer): states_dev float[n_layers][n][9].  rnf_flow_inverse_backward is the reverse sweep:
- * train_desc lists the layers in that iteration order, rotation_out_dev is the output of the inverse pass (each Moebius layer reads its
- * root back from its own output, no second root search); everything else as in rnf_flow_backward.  g_rotation_in_dev is the gradient
- * w.r.t. the rotations GIVEN to Flow.inverse. */
-int rnf_flow_inverse_train(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                           const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                           float *rotation_out_dev, float *ldj_out_dev, float *states_dev, void *workspace_dev,
-                           size_t workspace_bytes, void *stream);
-int rnf_flow_inverse_backward(const float *states_dev, const float *rotation_out_dev, const float *feature_dev, int64_t n,
-                              int32_t feature_dim, const float *plain_dev, const int32_t *train_desc, int32_t n_layers, int32_t segments,
-                              const float *g_rotation_out_dev, const float *g_ldj_dev, float *grads_dev, float *g_rotation_in_dev,
-                              float *g_feature_dev, float *layer_scratch_dev, void *stream);
-
-/* Training flows that contain side layers (RNF_LAYER_SIDE16 / SIDE16_ROT / SIDE9: Condition16TransLU, ConditionRot, Condition9TransLU;
- * flow/squeezetrans.py:134-144,264-277, flow/rottrans.py:37-66).  Their per-sample matrices are built by the caller with the reference's
- * own tensor ops (the LU layers' torch.diag couples the batch; ConditionRot's U^T V follows torch.svd's conventions), so the gradient
- * chain is split: rnf_flow_train_side (dir 0 = Flow.forward, 1 = Flow.inverse) is the pass that saves the layer inputs;
- * rnf_flow_backward_side is the reverse sweep, which also writes dL/d(matrix) into side_grad_dev float[n_side][n][16] (same layout as
- * side_dev) for the caller's autograd to carry through those ops; rnf_cond_mlp_backward is the backward of ONE conditioner network
- * evaluated by rnf_cond_mlp_forward.  train_desc: the side layer's slot goes into bits 16..23 of the kind word, its plain offset is
- * unused (rnf_plain_layer_floats = 0); pack_desc / desc as for any layer (an empty 4-float record). */
-int rnf_flow_train_side(int32_t dir, const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                        const float *side_dev, const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                        float *rotation_out_dev, float *ldj_out_dev, float *states_dev, void *workspace_dev, size_t workspace_bytes,
-                        void *stream);
-int rnf_flow_backward_side(int32_t dir, const float *states_dev, const float *rotation_out_dev, const float *feature_dev, int64_t n,
-                           int32_t feature_dim, const float *plain_dev, const int32_t *train_desc, int32_t n_layers, int32_t segments,
-                           const float *side_dev, float *side_grad_dev, const float *g_rotation_out_dev, const float *g_ldj_dev,
-                           float *grads_dev, float *g_rotation_in_dev, float *g_feature_dev, float *layer_scratch_dev, void *stream);
-/* plain_dev: the network's parameters in reference order (fc_first.weight [64][F], .bias, layers.{1,3,5}.weight / .bias, fc_last.weight
- * [n_out][64], .bias; flow/condition.py:14-22); g_out_dev float[n][n_out]; grads_dev (same layout as plain_dev) and g_feature_dev [n][F]
- * are ACCUMULATED into and may be NULL; scratch1_dev: one zeroed float.  n_out <= 64. */
+/* Backward of ONE conditioner network evaluated by rnf_cond_mlp_forward.  plain_dev: the network's parameters in reference order
+ * (fc_first.weight [64][F], .bias, layers.{1,3,5}.weight / .bias, fc_last.weight [n_out][64], .bias; flow/condition.py:14-22); g_out_dev
+ * float[n][n_out]; grads_dev (same layout as plain_dev) and g_feature_dev [n][F] are ACCUMULATED into and may be NULL; scratch1_dev: one
+ * zeroed float.  n_out <= 64. */
 int rnf_cond_mlp_backward(const float *feature_dev, int64_t n, int32_t feature_dim, const float *plain_dev, int32_t n_out,
                           const float *g_out_dev, float *grads_dev, float *g_feature_dev, float *scratch1_dev, void *stream);
-
-/* Shared feature rows: feature_dev holds n / feature_div rows and row r conditions rotations [r * feature_div, (r + 1) * feature_div)
- * -- the pose-estimation pattern of Agent.eval_acc (agent.py:238-263), where the reference materialises feature.repeat(number_queries).
- * The feature projection runs once per row; workspace from rnf_workspace_bytes_shared.  n must be a multiple of feature_div. */
-size_t rnf_workspace_bytes_shared(int64_t n, int32_t n_cond_layers, int64_t feature_div);
-int rnf_flow_forward_shared(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, int64_t feature_div,
-                            const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                            float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
-int rnf_flow_inverse_shared(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, int64_t feature_div,
-                            const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                            float *rotation_out_dev, float *ldj_out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
-
-/* rnf_flow_log_prob with shared feature rows (density of one image on a grid of rotations, eval.py:444-462). */
-int rnf_flow_log_prob_shared(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim, int64_t feature_div,
-                             const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments, const float *fisher_A,
-                             const float *fisher_c, int64_t fisher_B, float *rotation_out_dev, float *ldj_out_dev, float *logp_out_dev,
-                             double *sum_out, void *workspace_dev, size_t workspace_bytes, void *stream);
-
-/* Fused density evaluation: Flow.forward + MatrixFisherN(A)._log_prob(R') + the NLL accumulation
- * (agent.py:54-65,217-229; utils/fisher.py:217-232).
- *   fisher_A_dev [B,3,3], fisher_c_dev [B] with c_b = sum(S_b) + log(norm_b) (host precomputes the proper singular
- *   values, utils/fisher.py:67-76,93-97); sample i uses row i / (n / B) (fisher.py:226).  Pass NULL/0 for a uniform base.
- *   logp_out_dev [n] or NULL: per-sample log p = ldj + base.
- *   sum_out_dev  double[2] or NULL: {sum_i log p_i, n}, accumulated in fp64 in a fixed order (deterministic).
- *   rotation_out_dev / ldj_out_dev optional as above. */
-int rnf_flow_log_prob(const float *rotation_dev, const float *feature_dev, int64_t n, int32_t feature_dim,
-                      const float *blob_dev, const int32_t *desc, int32_t n_layers, int32_t segments,
-                      const float *fisher_A_dev, const float *fisher_c_dev, int64_t fisher_B,
-                      float *rotation_out_dev, float *ldj_out_dev, float *logp_out_dev, double *sum_out_dev,
-                      void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* MatrixFisherN._log_prob alone (utils/fisher.py:217-232), same A/c convention; out [n]. */
 int rnf_fisher_log_prob(const float *rotation_dev, int64_t n, const float *fisher_A_dev, const float *fisher_c_dev,

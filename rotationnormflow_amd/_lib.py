@@ -10,11 +10,38 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librnf_hip.so")
 
 _lib = None
-ABI_VERSION = 7
+ABI_VERSION = 8
 PREC_FP32, PREC_F16X2, PREC_BF16X3 = 0, 1, 2
 
 c_f32p = C.c_void_p      # device or host float*, passed as integer addresses
 c_i32p = C.c_void_p
+
+
+class _Pass(C.Structure):
+    """A struct whose first field is its own size (struct_bytes), filled in on construction; unnamed fields are zero / NULL."""
+
+    def __init__(self, **fields):
+        super().__init__(struct_bytes=C.sizeof(self), **fields)
+
+
+class FlowPass(_Pass):
+    """RnfFlowPass (include/rnf_hip.h): one pass through a packed flow."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("dir", C.c_int32), ("feature_dim", C.c_int32), ("rotation", C.c_void_p),
+                ("feature", C.c_void_p), ("n", C.c_int64), ("feature_div", C.c_int64), ("side", C.c_void_p), ("blob", C.c_void_p),
+                ("desc", C.c_void_p), ("n_layers", C.c_int32), ("segments", C.c_int32), ("fisher_A", C.c_void_p), ("fisher_c", C.c_void_p),
+                ("fisher_B", C.c_int64), ("rotation_out", C.c_void_p), ("ldj_out", C.c_void_p), ("logp_out", C.c_void_p),
+                ("sum_out", C.c_void_p), ("states", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class FlowBackward(_Pass):
+    """RnfFlowBackward (include/rnf_hip.h): the reverse sweep of a training pass."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("dir", C.c_int32), ("feature_dim", C.c_int32), ("states", C.c_void_p),
+                ("rotation_out", C.c_void_p), ("feature", C.c_void_p), ("n", C.c_int64), ("plain", C.c_void_p), ("train_desc", C.c_void_p),
+                ("n_layers", C.c_int32), ("segments", C.c_int32), ("acts", C.c_void_p), ("side", C.c_void_p), ("side_grad", C.c_void_p),
+                ("g_rotation_out", C.c_void_p), ("g_ldj", C.c_void_p), ("grads", C.c_void_p), ("g_rotation_in", C.c_void_p),
+                ("g_feature", C.c_void_p), ("layer_scratch", C.c_void_p), ("stream", C.c_void_p)]
+
 
 _SIGNATURES = {
     "rnf_abi_version": (C.c_int, []),
@@ -41,18 +68,9 @@ _SIGNATURES = {
     "rnf_cond36_packed_floats": (C.c_int64, []),
     "rnf_pack_cond36": (C.c_int, [c_f32p] * 10 + [C.c_int32, C.c_int32, c_f32p, c_f32p]),
     "rnf_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
-    "rnf_workspace_bytes_segments": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "rnf_flow_forward": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                   c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_inverse": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                   c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_forward_side": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                        c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_inverse_side": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                        c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_log_prob_side": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                         c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p,
-                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rnf_flow_pass": (C.c_int, [C.POINTER(FlowPass)]),
+    "rnf_flow_pass_workspace_bytes": (C.c_size_t, [C.POINTER(FlowPass)]),
+    "rnf_flow_backward_pass": (C.c_int, [C.POINTER(FlowBackward)]),
     "rnf_cond_mlp_forward": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnf_condrot_matrices": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_void_p]),
@@ -63,40 +81,15 @@ _SIGNATURES = {
                                       c_f32p, c_f32p, C.c_void_p]),
     "rnf_pack_flow_device": (C.c_int, [c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_i32p, C.c_void_p]),
     "rnf_plain_layer_floats": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    "rnf_flow_forward_train": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                         c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnf_flow_forward_train_plain": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
                                                c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_train_acts_floats": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
-    "rnf_flow_backward_saved": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                          c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "rnf_flow_backward": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                    c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "rnf_flow_inverse_train": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                         c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_inverse_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                            c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "rnf_workspace_bytes_shared": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
-    "rnf_flow_forward_shared": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_int64, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                          c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_inverse_shared": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_int64, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                          c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_log_prob_shared": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_int64, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                           c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p,
-                                           C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_log_prob": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32,
-                                    c_f32p, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "rnf_fisher_log_prob": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_min_geodesic": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_void_p]),
     "rnf_so3_healpix_grid": (C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_fisher_proper_svd": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_log_prob_backward": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
-    "rnf_flow_train_side": (C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p,
-                                      c_f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rnf_flow_backward_side": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p,
-                                         c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_cond_mlp_backward": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_matrix_to_quaternion": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_fisher_scratch_bytes": (C.c_size_t, [C.c_int64]),

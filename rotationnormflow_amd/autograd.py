@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, runtime
 
+ptr = runtime._ptr              # device address of a tensor, or None
 ORTHOGONAL_FLAG = 1 << 8        # layer-table kind flag: the 4x4 matrix is orthogonal, its layer reports ldj = 0 (flow/rottrans.py:21)
 
 
@@ -43,7 +44,7 @@ class TrainPlan:
         self.n_layers = n
         self.desc = np.zeros((n, runtime.DESC_STRIDE), dtype=np.int32)       # kernel blob table (runtime.pack_layers)
         self.pack_desc = np.zeros((n, 4), dtype=np.int32)                    # rnf_pack_flow_device
-        self.train_desc = np.zeros((n, 3), dtype=np.int32)                   # rnf_flow_backward
+        self.train_desc = np.zeros((n, 3), dtype=np.int32)                   # rnf_flow_backward_pass
         plain_off = rec_off = 0
         slot = 0
         side_slot = 0
@@ -89,7 +90,7 @@ class TrainPlan:
         self.plain_floats = plain_off
         self.blob_floats = max(rec_off, 4)
         self.desc = np.ascontiguousarray(self.desc)
-        self.train_desc_inverse = np.ascontiguousarray(self.train_desc[::-1])    # rnf_flow_inverse_backward: iteration order of the inverse pass
+        self.train_desc_inverse = np.ascontiguousarray(self.train_desc[::-1])    # rnf_flow_backward_pass, dir 1: iteration order of the inverse pass
         # packer status word: checked one call later through pinned memory, so that no step waits for the device
         self.flags = torch.zeros(1, dtype=torch.int32, device=device)
         self.flags_host = torch.zeros(1, dtype=torch.int32).pin_memory() if torch.cuda.is_available() else torch.zeros(1, dtype=torch.int32)
@@ -258,21 +259,17 @@ class _FlowFn(torch.autograd.Function):
                                                           plan.n_layers, plan.segments, out_rot.data_ptr(), out_ldj.data_ptr(),
                                                           states.data_ptr(), acts.data_ptr() if acts is not None else None, stream))
         elif n:
-            ws = runtime.workspace(dev, L.rnf_workspace_bytes_segments(n, plan.n_cond, plan.segments))     # (+ the K > 128 stash of an inverse pass)
-            fptr = feat.data_ptr() if feat is not None else None
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
+                p = _lib.FlowPass(dir=direction, rotation=rot.data_ptr(), feature=ptr(feat), n=n, feature_dim=plan.feat_padded, side=ptr(side_c),
+                                  desc=plan.desc.ctypes.data, n_layers=plan.n_layers, segments=plan.segments, rotation_out=out_rot.data_ptr(),
+                                  ldj_out=out_ldj.data_ptr(), states=states.data_ptr(), stream=stream)
+                ws = runtime.workspace(dev, L.rnf_flow_pass_workspace_bytes(p))
                 if plan.feat_dim:
                     plan.calibrate(feat)
                 blob = plan.pack(plain, stream)
-                if plan.n_side:
-                    _lib.check(L.rnf_flow_train_side(direction, rot.data_ptr(), fptr, n, plan.feat_padded, side_c.data_ptr(), blob.data_ptr(),
-                                                     plan.desc.ctypes.data, plan.n_layers, plan.segments, out_rot.data_ptr(),
-                                                     out_ldj.data_ptr(), states.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-                else:
-                    fn = L.rnf_flow_inverse_train if direction else L.rnf_flow_forward_train
-                    _lib.check(fn(rot.data_ptr(), fptr, n, plan.feat_padded, blob.data_ptr(), plan.desc.ctypes.data, plan.n_layers,
-                                  plan.segments, out_rot.data_ptr(), out_ldj.data_ptr(), states.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+                p.blob, p.workspace, p.workspace_bytes = blob.data_ptr(), ws.data_ptr(), ws.numel()
+                _lib.check(L.rnf_flow_pass(p))
         ctx.plan = plan
         ctx.grad_sync = grad_sync
         ctx.direction = direction
@@ -303,31 +300,16 @@ class _FlowFn(torch.autograd.Function):
             g_rot_c = g_rot.reshape(n, 9).to(torch.float32).contiguous() if g_rot is not None else None
             g_ldj_c = (g_ldj.to(torch.float32).contiguous() if g_ldj is not None
                        else torch.zeros(n, dtype=torch.float32, device=dev))
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             tdesc = plan.train_desc_inverse if ctx.direction else plan.train_desc
+            cond = plan.n_cond > 0                        # (a flow whose only feature consumers are side layers passes no feature here)
             with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                if plan.n_side:
-                    _lib.check(L.rnf_flow_backward_side(ctx.direction, states.data_ptr(), ptr(out_rot), ptr(feat_plain) if plan.n_cond else None, n,
-                                                        plan.feat_dim if plan.n_cond else 0, ptr(plain) if plain.numel() else None,
-                                                        tdesc.ctypes.data, plan.n_layers, plan.segments, side_c.data_ptr(), g_side.data_ptr(),
-                                                        ptr(g_rot_c), g_ldj_c.data_ptr(), ptr(grads), g_rot_in.data_ptr(), ptr(g_feat),
-                                                        scratch.data_ptr(), stream))
-                elif ctx.direction:
-                    _lib.check(L.rnf_flow_inverse_backward(states.data_ptr(), out_rot.data_ptr(), ptr(feat_plain), n, plan.feat_dim,
-                                                           plain.data_ptr(), tdesc.ctypes.data, plan.n_layers, plan.segments,
-                                                           ptr(g_rot_c), g_ldj_c.data_ptr(), ptr(grads), g_rot_in.data_ptr(), ptr(g_feat),
-                                                           scratch.data_ptr(), stream))
-                elif acts is not None:
-                    _lib.check(L.rnf_flow_backward_saved(states.data_ptr(), acts.data_ptr(), ptr(feat_plain) if plan.n_cond else None, n,
-                                                         plan.feat_dim if plan.n_cond else 0, plain.data_ptr(), tdesc.ctypes.data,
-                                                         plan.n_layers, plan.segments, ptr(g_rot_c), g_ldj_c.data_ptr(), ptr(grads),
-                                                         g_rot_in.data_ptr(), ptr(g_feat), scratch.data_ptr(), stream))
-                else:
-                    _lib.check(L.rnf_flow_backward(states.data_ptr(), ptr(feat_plain), n, plan.feat_dim, plain.data_ptr(),
-                                                   tdesc.ctypes.data, plan.n_layers, plan.segments, ptr(g_rot_c),
-                                                   g_ldj_c.data_ptr(), ptr(grads), g_rot_in.data_ptr(), ptr(g_feat),
-                                                   scratch.data_ptr(), stream))
+                b = _lib.FlowBackward(dir=ctx.direction, states=states.data_ptr(), rotation_out=ptr(out_rot), feature=ptr(feat_plain) if cond else None,
+                                      n=n, feature_dim=plan.feat_dim if cond else 0, plain=ptr(plain) if plain.numel() else None,
+                                      train_desc=tdesc.ctypes.data, n_layers=plan.n_layers, segments=plan.segments, acts=ptr(acts),
+                                      side=ptr(side_c), side_grad=ptr(g_side), g_rotation_out=ptr(g_rot_c), g_ldj=g_ldj_c.data_ptr(),
+                                      grads=ptr(grads), g_rotation_in=g_rot_in.data_ptr(), g_feature=ptr(g_feat), layer_scratch=scratch.data_ptr(),
+                                      stream=torch.cuda.current_stream(dev).cuda_stream)
+                _lib.check(L.rnf_flow_backward_pass(b))
         needs = ctx.needs_input_grad
         if want_w:
             runtime.note_training_step()                  # an optimizer step follows: host-packed blobs are stale from now on
@@ -423,7 +405,6 @@ class _CondMLPFn(torch.autograd.Function):
         g = g_out.to(torch.float32).contiguous()
         scratch = torch.zeros(1, dtype=torch.float32, device=dev)
         if n:
-            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
             with torch.cuda.device(dev):
                 _lib.check(L.rnf_cond_mlp_backward(feat.data_ptr(), n, F, plain.data_ptr(), ctx.n_out, g.data_ptr(), ptr(grads), ptr(g_feat),
                                                    scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))

@@ -614,21 +614,6 @@ static int device_cus() {
     return c;
 }
 
-extern "C" size_t rnf_workspace_bytes_shared(int64_t n, int32_t n_cond_layers, int64_t feature_div) {
-    if (feature_div <= 0) return rnf_workspace_bytes(n, n_cond_layers);
-    const size_t rows = (size_t)((n + feature_div - 1) / feature_div);
-    return PARTIALS_BYTES + (size_t)n_cond_layers * rows * 64 * sizeof(float);
-}
-
-// K > 128: the inverse pass keeps the parameters of 64 segments per lane in registers and the rest in a per-wave stash behind the scratch
-static size_t inv_stash_bytes(int32_t K) {
-    const int KT = (K + 7) / 8;
-    return KT > 16 ? (size_t)device_cus() * NW_INV_BIG * (size_t)(4 * (KT - 16)) * 64 * sizeof(float4) : 0;
-}
-extern "C" size_t rnf_workspace_bytes_segments(int64_t n, int32_t n_cond_layers, int32_t segments) {
-    return rnf_workspace_bytes(n, n_cond_layers) + inv_stash_bytes(segments);
-}
-
 extern "C" size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers) {
     size_t bytes = PARTIALS_BYTES;
     if (n_cond_layers > 0) {
@@ -638,6 +623,20 @@ extern "C" size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers) {
         if (g16 > groups) groups = g16;
         bytes += (size_t)n_cond_layers * groups * G_FLOATS_PER_GROUP * sizeof(float);
     }
+    return bytes;
+}
+
+// The workspace rnf_flow_pass requires (rnf_flow_pass_workspace_bytes returns it, run_flow checks against it): the partials block, the
+// feature-projection scratch of n_slots conditional slots -- one 64-float record per (slot, feature row) with shared feature rows -- and
+// behind them, from *stash_at on, the per-wave stash of an inverse pass with K > 128 (the parameters of 64 segments per lane stay in
+// registers, flow_kernels.h mobius_inv_tiles).
+static size_t flow_workspace(const RnfFlowPass &p, int n_slots, bool any_mlp, size_t *stash_at) {
+    const bool shared = p.feature_div > 0 && n_slots > 0;
+    size_t bytes = shared ? PARTIALS_BYTES + (size_t)n_slots * (size_t)((p.n + p.feature_div - 1) / p.feature_div) * 64 * sizeof(float)
+                          : rnf_workspace_bytes(p.n, n_slots);
+    *stash_at = bytes;
+    const int KT = (p.segments + 7) / 8;
+    if (p.dir == 1 && any_mlp && KT > 16) bytes += (size_t)device_cus() * NW_INV_BIG * (size_t)(4 * (KT - 16)) * 64 * sizeof(float4);
     return bytes;
 }
 
@@ -805,21 +804,15 @@ static int launch_big_inverse(const FlowArgs &a, int grid, size_t lds_bytes, hip
     return 0;
 }
 
-struct RunOpts {
-    int dir;                  // 0 forward, 1 inverse
-    const float *fisher_A, *fisher_c;
-    int64_t fisher_B;
-    float *logp_out;
-    double *sum_out;
-    float *states = nullptr;  // training forward: per-layer input rotations [n_layers][n][9]
-    int64_t feature_div = 0;  // > 0: feature row r serves rotations [r * feature_div, (r + 1) * feature_div)
-    const float *side = nullptr;   // per-sample matrices of RNF_LAYER_SIDE* layers: [side slot][n][16]
-};
-
-static int run_flow(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob, const int32_t *desc,
-                    int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws, size_t ws_bytes, void *stream_v,
-                    const RunOpts &o) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+static int run_flow(const RnfFlowPass &o) {
+    const float *rot = o.rotation, *feat = o.feature, *blob = o.blob;
+    const int32_t *desc = o.desc;
+    const int64_t n = o.n;
+    const int32_t F = o.feature_dim, n_layers = o.n_layers, K = o.segments;
+    float *rot_out = o.rotation_out, *ldj_out = o.ldj_out;
+    void *ws = o.workspace;
+    const size_t ws_bytes = o.workspace_bytes;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(o.stream);
     if (n < 0) return fail("n=%lld is negative", (long long)n);
     if (n_layers <= 0 || n_layers > MAX_LAYERS) return fail("n_layers=%d outside [1,%d]", n_layers, MAX_LAYERS);
     if (K <= 0) return fail("segments=%d must be positive", K);
@@ -850,7 +843,7 @@ static int run_flow(const float *rot, const float *feat, int64_t n, int32_t F, c
         if ((kind == RNF_KIND_COND16 || kind_is_cond9(kind) || kind == RNF_KIND_COND36) && slot < 0)
             return fail("layer %d: a conditional affine layer needs a cond_slot", l);
         if (kind_is_cond9(kind) || kind == RNF_KIND_COND36 || kind_is_side(kind)) ext = true;
-        if (kind_is_side(kind) && !o.side) return fail("layer %d takes per-sample matrices: call the rnf_flow_*_side entry points with a side buffer", l);
+        if (kind_is_side(kind) && !o.side) return fail("layer %d takes per-sample matrices: RnfFlowPass.side is null", l);
         if ((kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16) || slot >= 0) lean = false;
         if (kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16) lean2 = false;
         if (kind == RNF_KIND_COND36) min_tiles = 2;
@@ -905,9 +898,15 @@ static int run_flow(const float *rot, const float *feat, int64_t n, int32_t F, c
     const bool ext_layers = ext;                         // the flow holds a layer kind only the extended instantiation carries
     if (shared) ext = true;                              // shared feature rows: the extended instantiation, unless a ROWS one fits (below)
     if (shared && n % o.feature_div) return fail("n=%lld not divisible by feature_div=%lld", (long long)n, (long long)o.feature_div);
-    const size_t ws_need = shared ? rnf_workspace_bytes_shared(n, n_slots, o.feature_div) : rnf_workspace_bytes(n, n_slots);
-    if (ws_bytes < ws_need && (n_slots > 0 || o.sum_out)) return fail("workspace of %zu bytes is smaller than the %zu needed", ws_bytes, ws_need);
-    if ((n_slots > 0 || o.sum_out) && !ws) return fail("workspace pointer is null");
+    size_t stash_at;
+    const size_t ws_need = flow_workspace(o, n_slots, any_mlp, &stash_at);
+    const bool stash = ws_need > stash_at;               // overflow stash of the K > 128 inverse, behind everything else
+    if (stash && shared) return fail("inverse pass with segments > 128 is not built for shared feature rows; got %d", K);
+    if (n_slots > 0 || o.sum_out || stash) {
+        if (!ws) return fail("workspace pointer is null");
+        if (ws_bytes < ws_need) return fail("workspace of %zu bytes is smaller than the %zu needed (rnf_flow_pass_workspace_bytes)", ws_bytes, ws_need);
+    }
+    if (stash) a.inv_stash = reinterpret_cast<float4 *>(reinterpret_cast<char *>(ws) + stash_at);
 
     const int KT = (K + 7) / 8;
     // inverse: the segment parameters of a layer stay in registers through the root finder; instantiations hold 1, 2, 4, 8 tiles
@@ -915,14 +914,6 @@ static int run_flow(const float *rot, const float *feat, int64_t n, int32_t F, c
     const int kt_inv = KT <= 1 ? 1 : (KT <= 2 ? 2 : (KT <= 4 ? 4 : (KT <= 8 ? 8 : 16)));
     // (round 4: inverse passes with more than 64 segments also run for conditional 3x3 / 6x6 layers, side layers and shared feature rows --
     // flow/mobiusflow.py:7-14 takes any `segments` with any `rot` -- on the extended build of the 4-wave instantiation)
-
-    if (o.dir == 1 && any_mlp && KT > 16) {            // overflow stash of the K > 128 inverse (flow_kernels.h mobius_inv_tiles), behind everything else
-        if (shared) return fail("inverse pass with segments > 128 is not built for shared feature rows; got %d", K);
-        if (!ws || ws_bytes < ws_need + inv_stash_bytes(K))
-            return fail("workspace of %zu bytes is smaller than the %zu an inverse pass with %d segments needs (rnf_workspace_bytes_segments)",
-                        ws_bytes, ws_need + inv_stash_bytes(K), K);
-        a.inv_stash = reinterpret_cast<float4 *>(reinterpret_cast<char *>(ws) + ws_need);
-    }
     double *partials = reinterpret_cast<double *>(ws);
     float *G = n_slots ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + PARTIALS_BYTES) : nullptr;
     const int max_tiles = prec == 2 ? Lay<2>::MAX_TILES_IN_LDS : MOB_MAX_TILES_IN_LDS;
@@ -1182,60 +1173,40 @@ static int run_flow(const float *rot, const float *feat, int64_t n, int32_t F, c
     return 0;
 }
 
-extern "C" int rnf_flow_forward(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob,
-                                const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                size_t ws_bytes, void *stream) {
-    RunOpts o{0, nullptr, nullptr, 0, nullptr, nullptr};
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
+extern "C" int rnf_flow_pass(const RnfFlowPass *p) {
+    if (!p) return fail("RnfFlowPass pointer is null");
+    if (p->struct_bytes != sizeof(RnfFlowPass))
+        return fail("RnfFlowPass.struct_bytes=%zu, the library's is %zu: header and library differ", p->struct_bytes, sizeof(RnfFlowPass));
+    if (p->dir != 0 && p->dir != 1) return fail("RnfFlowPass.dir=%d must be 0 (Flow.forward) or 1 (Flow.inverse)", (int)p->dir);
+    if ((p->fisher_A == nullptr) != (p->fisher_c == nullptr)) return fail("RnfFlowPass.fisher_A and fisher_c must both be given or both be null");
+    if (p->feature_div < 0) return fail("RnfFlowPass.feature_div=%lld is negative", (long long)p->feature_div);
+    const bool logp = p->fisher_A || p->logp_out || p->sum_out;
+    if (logp && p->dir) return fail("RnfFlowPass: fisher_A / logp_out / sum_out (log p) need dir 0");
+    if (p->states && (p->feature_div > 0 || logp)) return fail("RnfFlowPass.states (training pass) takes neither feature_div nor fisher_A / logp_out / sum_out");
+    if (p->side && p->feature_div > 0) return fail("RnfFlowPass.side with feature_div > 0 is not built: expand the shared feature rows");
+    if (p->states && p->n > 0 && !p->rotation_out) return fail("RnfFlowPass.states needs rotation_out (the backward sweep reads the pass's output)");
+    return run_flow(*p);
 }
 
-// Shared feature rows (pose estimation, agent.py:238-263: every image feature is evaluated against number_queries rotations; the
-// reference materialises feature.repeat): feature_dev has n / feature_div rows, row r serves rotations [r * feature_div, (r+1) * feature_div).
-// The feature projection then runs once per ROW and its scratch is one 64-float record per (layer, row).
-extern "C" int rnf_flow_forward_shared(const float *rot, const float *feat, int64_t n, int32_t F, int64_t feature_div, const float *blob,
-                                       const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                       size_t ws_bytes, void *stream) {
-    RunOpts o{0, nullptr, nullptr, 0, nullptr, nullptr};
-    o.feature_div = feature_div;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
-extern "C" int rnf_flow_inverse_shared(const float *rot, const float *feat, int64_t n, int32_t F, int64_t feature_div, const float *blob,
-                                       const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                       size_t ws_bytes, void *stream) {
-    RunOpts o{1, nullptr, nullptr, 0, nullptr, nullptr};
-    o.feature_div = feature_div;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
+extern "C" size_t rnf_flow_pass_workspace_bytes(const RnfFlowPass *p) {
+    if (!p || p->struct_bytes != sizeof(RnfFlowPass)) {
+        fail("RnfFlowPass.struct_bytes does not match the library's %zu", sizeof(RnfFlowPass));
+        return 0;
+    }
+    int n_slots = 0;                                     // counted as run_flow counts them
+    bool any_mlp = false;
+    for (int l = 0; p->desc && l < p->n_layers && l < MAX_LAYERS; ++l) {
+        const int32_t *d = p->desc + (size_t)l * D_STRIDE;
+        if (d[D_SLOT] + 1 > n_slots) n_slots = d[D_SLOT] + 1;
+        any_mlp = any_mlp || kind_has_mlp(d[D_KIND]);
+    }
+    size_t stash_at;
+    return flow_workspace(*p, n_slots, any_mlp, &stash_at);
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // training: forward that saves per-layer states, and the reverse sweep (train_kernels.h)
 // ------------------------------------------------------------------------------------------------------------
-// per-sample matrix layers (RNF_LAYER_SIDE16 / SIDE16_ROT / SIDE9): side_dev float[n_side_layers][n][16], desc param_offset = slot
-extern "C" int rnf_flow_forward_side(const float *rot, const float *feat, int64_t n, int32_t F, const float *side, const float *blob,
-                                     const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                     size_t ws_bytes, void *stream) {
-    RunOpts o{0, nullptr, nullptr, 0, nullptr, nullptr};
-    o.side = side;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-extern "C" int rnf_flow_inverse_side(const float *rot, const float *feat, int64_t n, int32_t F, const float *side, const float *blob,
-                                     const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                     size_t ws_bytes, void *stream) {
-    RunOpts o{1, nullptr, nullptr, 0, nullptr, nullptr};
-    o.side = side;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-extern "C" int rnf_flow_log_prob_side(const float *rot, const float *feat, int64_t n, int32_t F, const float *side, const float *blob,
-                                      const int32_t *desc, int32_t n_layers, int32_t K, const float *fisher_A, const float *fisher_c,
-                                      int64_t fisher_B, float *rot_out, float *ldj_out, float *logp_out, double *sum_out, void *ws,
-                                      size_t ws_bytes, void *stream) {
-    if ((fisher_A == nullptr) != (fisher_c == nullptr)) return fail("fisher_A and fisher_c must both be given or both be null");
-    RunOpts o{0, fisher_A, fisher_c, fisher_B, logp_out, sum_out};
-    o.side = side;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
 // ConditionalTransform(F, <= 16 outputs)(feature) alone (flow/condition.py:24-30): the nets of ConditionRot (flow/rottrans.py:40) and
 // ConditionLU (flow/squeezetrans.py:117-119), whose outputs the reference post-processes with batched torch ops.  Records from
 // rnf_pack_cond16 (rows beyond the net's outputs zero); out [n][16], output o of the net in column o.
@@ -1511,18 +1482,9 @@ extern "C" int rnf_condlu_backward(const float *wl, const float *wu, const float
     return 0;
 }
 
-extern "C" int rnf_flow_forward_train(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob, const int32_t *desc,
-                                      int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, float *states, void *ws,
-                                      size_t ws_bytes, void *stream) {
-    if (n > 0 && !states) return fail("states buffer is null");
-    RunOpts o{0, nullptr, nullptr, 0, nullptr, nullptr};
-    o.states = states;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
 // Training forward from the plain blob on 16-rotation workgroups (train_block16.h: flow_train_forward16_kernel): no packed blob, exact fp32.
 // Built for the layer kinds of the reference's training recipes (Moebius, Uncondition16Trans / UnconditionRot, Condition16Trans) in the
-// forward direction, at most TR_MAX_LAYERS layers; the caller keeps every other flow on rnf_flow_forward_train.
+// forward direction, at most TR_MAX_LAYERS layers; the caller keeps every other flow on rnf_flow_pass with states.
 // Floats of the activation buffer the training forward can leave for the backward sweep: one slot of (256 + 4K rounded up to 16) x 16 floats
 // per conditioner layer and 16-rotation block (train_block16.h).
 static int act_rows_for(int32_t K) { return b16::ACT_HEAD_ROWS + (4 * K + 15) / 16 * 16; }
@@ -1548,7 +1510,7 @@ extern "C" int rnf_flow_forward_train_plain(const float *rot, const float *feat,
         const int32_t *d = tdesc + (size_t)l * 3;
         const int kind = d[0] & 15, orth = (d[0] >> 8) & 1;
         if ((d[0] & ~(15 | 256)) || (kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16))
-            return fail("rnf_flow_forward_train_plain: layer %d (kind %d) is not built here; use rnf_flow_forward_train", l, d[0]);
+            return fail("rnf_flow_forward_train_plain: layer %d (kind %d) is not built here; use rnf_flow_pass with states", l, d[0]);
         if (d[1] < 0 || d[1] > 5) return fail("layer %d: perm_row %d outside [0,5]", l, d[1]);
         if (d[2] < 0) return fail("layer %d: negative plain offset", l);
         if (kind == RNF_KIND_COND16 && F == 0) return fail("layer %d: a conditional affine layer needs a feature", l);
@@ -1626,48 +1588,17 @@ extern "C" size_t rnf_plain_layer_floats(int32_t kind, int32_t segments, int32_t
     return 64 * ni + 64 + 3 * (4096 + 64) + no * 64 + no;
 }
 
-struct BackwardExtra {
-    const float *side = nullptr;       // [n_side][n][16] per-sample matrices of the side layers
-    float *side_grad = nullptr;        // [n_side][n][16] out: dL/d(matrix)
-    const float *g_out_ext = nullptr;  // RNF_KIND_MLP_ONLY: dL/d(outputs) [n][NO]
-    const float *acts = nullptr;       // activations saved by rnf_flow_forward_train_plain (16-rotation sweep only; else recomputed)
-};
-static int run_backward(const float *states, const float *rot_final, int dir, const float *feat, int64_t n, int32_t F, const float *plain,
-                        const int32_t *tdesc, int32_t n_layers, int32_t K, const float *g_rot_out, const float *g_ldj, float *grads,
-                        float *g_rot_in, float *g_feature, float *g_ldj_sum, void *stream_v, const BackwardExtra &x = BackwardExtra());
-
-extern "C" int rnf_flow_backward(const float *states, const float *feat, int64_t n, int32_t F, const float *plain, const int32_t *tdesc,
-                                 int32_t n_layers, int32_t K, const float *g_rot_out, const float *g_ldj, float *grads,
-                                 float *g_rot_in, float *g_feature, float *g_ldj_sum, void *stream_v) {
-    return run_backward(states, nullptr, 0, feat, n, F, plain, tdesc, n_layers, K, g_rot_out, g_ldj, grads, g_rot_in, g_feature, g_ldj_sum, stream_v);
-}
-
-// rnf_flow_backward with the conditioner activations that rnf_flow_forward_train_plain saved (same n, table and K): the 16-rotation sweep
-// reads them back instead of recomputing every conditioner; the 64-rotation sweep of large batches ignores them.
-extern "C" int rnf_flow_backward_saved(const float *states, const float *acts, const float *feat, int64_t n, int32_t F, const float *plain,
-                                       const int32_t *tdesc, int32_t n_layers, int32_t K, const float *g_rot_out, const float *g_ldj, float *grads,
-                                       float *g_rot_in, float *g_feature, float *g_ldj_sum, void *stream_v) {
-    BackwardExtra x;
-    x.acts = acts;
-    for (int l = 0; acts && l < n_layers; ++l) {
-        const int kind = tdesc[(size_t)l * 3] & 15;
-        if (kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16)
-            return fail("rnf_flow_backward_saved: layer %d (kind %d) has no saved activations (rnf_flow_forward_train_plain does not run it)", l, kind);
-    }
-    return run_backward(states, nullptr, 0, feat, n, F, plain, tdesc, n_layers, K, g_rot_out, g_ldj, grads, g_rot_in, g_feature, g_ldj_sum, stream_v, x);
-}
-
-extern "C" int rnf_flow_inverse_backward(const float *states, const float *rot_out, const float *feat, int64_t n, int32_t F, const float *plain,
-                                         const int32_t *tdesc, int32_t n_layers, int32_t K, const float *g_rot_out, const float *g_ldj,
-                                         float *grads, float *g_rot_in, float *g_feature, float *g_ldj_sum, void *stream_v) {
-    if (n > 0 && !rot_out) return fail("rnf_flow_inverse_backward: the output rotations of the inverse pass are needed (they carry the roots)");
-    return run_backward(states, rot_out, 1, feat, n, F, plain, tdesc, n_layers, K, g_rot_out, g_ldj, grads, g_rot_in, g_feature, g_ldj_sum, stream_v);
-}
-
-static int run_backward(const float *states, const float *rot_final, int dir, const float *feat, int64_t n, int32_t F, const float *plain,
-                        const int32_t *tdesc, int32_t n_layers, int32_t K, const float *g_rot_out, const float *g_ldj, float *grads,
-                        float *g_rot_in, float *g_feature, float *g_ldj_sum, void *stream_v, const BackwardExtra &x) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
+// g_out_ext: dL/d(outputs) [n][NO] of an RNF_KIND_MLP_ONLY table (rnf_cond_mlp_backward)
+static int run_backward(const RnfFlowBackward &x, const float *g_out_ext = nullptr) {
+    const float *states = x.states, *feat = x.feature, *g_rot_out = x.g_rotation_out, *g_ldj = x.g_ldj;
+    const float *rot_final = x.dir ? x.rotation_out : nullptr;
+    static const float dummy = 0.f;                      // side-layer flows may have no plain parameters at all
+    const float *plain = x.plain ? x.plain : (x.side ? &dummy : nullptr);
+    const int32_t *tdesc = x.train_desc;
+    const int64_t n = x.n;
+    const int32_t F = x.feature_dim, n_layers = x.n_layers, K = x.segments;
+    float *grads = x.grads, *g_rot_in = x.g_rotation_in, *g_feature = x.g_feature, *g_ldj_sum = x.layer_scratch;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(x.stream);
     if (n < 0) return fail("n=%lld is negative", (long long)n);
     if (n_layers < 0 || n_layers > MAX_LAYERS) return fail("n_layers=%d outside [0,%d] (training path)", n_layers, MAX_LAYERS);
     if (K < 1 || K > 512) return fail("training path supports 1..512 segments, got %d", K);
@@ -1688,19 +1619,21 @@ static int run_backward(const float *states, const float *rot_final, int dir, co
             (kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16 && kind != RNF_KIND_GS9 && kind != RNF_KIND_GS36 &&
              kind != RNF_KIND_COND36 && !kind_is_cond9(kind) && !kind_is_side(kind) && !(kind == RNF_KIND_MLP_ONLY && mlp_only)))
             return fail("layer %d: kind %d has no backward kernel", l, d[0]);
-        if (kind_is_side(kind) && (!x.side || !x.side_grad)) return fail("layer %d is a side layer: side / side_grad buffers are needed (rnf_flow_backward_side)", l);
-        if (kind == RNF_KIND_MLP_ONLY && (aux < 1 || aux > 64 || !x.g_out_ext || F <= 0)) return fail("rnf_cond_mlp_backward: 1..64 outputs, a feature and dL/d(outputs) are needed");
+        if (kind_is_side(kind) && (!x.side || !x.side_grad)) return fail("layer %d is a side layer: RnfFlowBackward.side / side_grad are needed", l);
+        if (kind == RNF_KIND_MLP_ONLY && (aux < 1 || aux > 64 || !g_out_ext || F <= 0)) return fail("rnf_cond_mlp_backward: 1..64 outputs, a feature and dL/d(outputs) are needed");
+        if (x.acts && kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16)
+            return fail("RnfFlowBackward.acts: layer %d (kind %d) has no saved activations (rnf_flow_forward_train_plain does not run it)", l, kind);
         if (d[1] < 0 || d[1] > 5) return fail("layer %d: perm_row %d outside [0,5]", l, d[1]);
         if (kind_has_mlp(kind) && F > 0 && !feat) return fail("conditional layer %d but feature pointer is null", l);
         if ((kind == RNF_KIND_COND16 || kind == RNF_KIND_COND36 || kind_is_cond9(kind)) && F == 0) return fail("layer %d: a conditional affine layer needs a feature", l);
         if (d[2] < 0) return fail("layer %d: negative plain offset", l);
         table[l] = make_int2(kind | (d[1] << 4) | (orth << 8) | (aux << 16), d[2]);
     }
-    a.side = x.side; a.side_grad = x.side_grad; a.g_out_ext = x.g_out_ext;
+    a.side = x.side; a.side_grad = x.side_grad; a.g_out_ext = g_out_ext;
     a.feature = F ? feat : nullptr; a.plain = plain; a.grads = grads; a.g_ldj = g_ldj;
     a.g_rot_in = g_rot_in; a.g_feature = F ? g_feature : nullptr;
     a.n = n; a.K = K; a.F = F;
-    a.dir = dir;
+    a.dir = x.dir;
 #ifdef RNF_STAMPS
     {   // diagnostic build: RNF_TRAIN_STAMPS_PTR=<device address of 10 zeroed uint64> (tools/phase_stamps_train.py)
         const char *sp = std::getenv("RNF_TRAIN_STAMPS_PTR");
@@ -1769,31 +1702,15 @@ static int run_backward(const float *states, const float *rot_final, int dir, co
     return 0;
 }
 
-// Training with side layers (Condition16TransLU / Condition9TransLU / ConditionRot): the pass that saves the layer inputs, and the
-// backward sweep that also returns dL/d(per-sample matrix) -- the caller's autograd carries it through the reference's own tensor ops
-// (einsum / torch.diag / torch.svd) into the conditioner networks, whose backward is rnf_cond_mlp_backward.
-extern "C" int rnf_flow_train_side(int32_t dir, const float *rot, const float *feat, int64_t n, int32_t F, const float *side, const float *blob,
-                                   const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, float *states, void *ws,
-                                   size_t ws_bytes, void *stream) {
-    if (dir != 0 && dir != 1) return fail("rnf_flow_train_side: dir=%d", (int)dir);
-    if (n > 0 && (!states || !rot_out)) return fail("rnf_flow_train_side: states / rotation_out buffer is null");
-    RunOpts o{dir, nullptr, nullptr, 0, nullptr, nullptr};
-    o.states = states;
-    o.side = side;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
-extern "C" int rnf_flow_backward_side(int32_t dir, const float *states, const float *rot_out, const float *feat, int64_t n, int32_t F,
-                                      const float *plain, const int32_t *tdesc, int32_t n_layers, int32_t K, const float *side, float *side_grad,
-                                      const float *g_rot_out, const float *g_ldj, float *grads, float *g_rot_in, float *g_feature,
-                                      float *g_ldj_sum, void *stream_v) {
-    if (dir != 0 && dir != 1) return fail("rnf_flow_backward_side: dir=%d", (int)dir);
-    if (dir == 1 && n > 0 && !rot_out) return fail("rnf_flow_backward_side: the output rotations of the inverse pass are needed (they carry the roots)");
-    BackwardExtra x;
-    x.side = side; x.side_grad = side_grad;
-    static const float dummy = 0.f;
-    return run_backward(states, dir ? rot_out : nullptr, dir, feat, n, F, plain ? plain : &dummy, tdesc, n_layers, K, g_rot_out, g_ldj, grads, g_rot_in,
-                        g_feature, g_ldj_sum, stream_v, x);
+extern "C" int rnf_flow_backward_pass(const RnfFlowBackward *p) {
+    if (!p) return fail("RnfFlowBackward pointer is null");
+    if (p->struct_bytes != sizeof(RnfFlowBackward))
+        return fail("RnfFlowBackward.struct_bytes=%zu, the library's is %zu: header and library differ", p->struct_bytes, sizeof(RnfFlowBackward));
+    if (p->dir != 0 && p->dir != 1) return fail("RnfFlowBackward.dir=%d must be 0 (Flow.forward) or 1 (Flow.inverse)", (int)p->dir);
+    if (p->dir == 1 && p->n > 0 && !p->rotation_out)
+        return fail("RnfFlowBackward.rotation_out is needed for dir 1: the output rotations of the inverse pass carry the roots");
+    if (p->acts && p->dir) return fail("RnfFlowBackward.acts needs dir 0 (rnf_flow_forward_train_plain runs Flow.forward)");
+    return run_backward(*p);
 }
 
 // Backward of ONE ConditionalTransform(feature_dim -> n_out) evaluated on its own (rnf_cond_mlp_forward; flow/condition.py:24-30): plain =
@@ -1805,46 +1722,11 @@ extern "C" int rnf_cond_mlp_backward(const float *feat, int64_t n, int32_t F, co
     if (!feat || !plain || !g_out || !scratch1) return fail("rnf_cond_mlp_backward: null pointer");
     if (n_out < 1 || n_out > 64) return fail("rnf_cond_mlp_backward: n_out=%d outside [1,64]", (int)n_out);
     const int32_t tdesc[3] = {RNF_KIND_MLP_ONLY | (n_out << 16), 0, 0};
-    BackwardExtra x;
-    x.g_out_ext = g_out;
-    return run_backward(nullptr, nullptr, 0, feat, n, F, plain, tdesc, 1, 8, nullptr, nullptr, grads, nullptr, g_feature, scratch1, stream_v, x);
-}
-
-// Flow.inverse that also saves the rotation entering every iteration position of the inverse pass (position 0 = the last flow layer)
-extern "C" int rnf_flow_inverse_train(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob, const int32_t *desc,
-                                      int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, float *states, void *ws, size_t ws_bytes,
-                                      void *stream) {
-    if (!states && n > 0) return fail("rnf_flow_inverse_train: states pointer is null");
-    if (!rot_out && n > 0) return fail("rnf_flow_inverse_train: rotation_out is needed by rnf_flow_inverse_backward");
-    RunOpts o{1, nullptr, nullptr, 0, nullptr, nullptr};
-    o.states = states;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
-extern "C" int rnf_flow_inverse(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob,
-                                const int32_t *desc, int32_t n_layers, int32_t K, float *rot_out, float *ldj_out, void *ws,
-                                size_t ws_bytes, void *stream) {
-    RunOpts o{1, nullptr, nullptr, 0, nullptr, nullptr};
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
-extern "C" int rnf_flow_log_prob(const float *rot, const float *feat, int64_t n, int32_t F, const float *blob,
-                                 const int32_t *desc, int32_t n_layers, int32_t K, const float *fisher_A,
-                                 const float *fisher_c, int64_t fisher_B, float *rot_out, float *ldj_out, float *logp_out,
-                                 double *sum_out, void *ws, size_t ws_bytes, void *stream) {
-    if ((fisher_A == nullptr) != (fisher_c == nullptr)) return fail("fisher_A and fisher_c must both be given or both be null");
-    RunOpts o{0, fisher_A, fisher_c, fisher_B, logp_out, sum_out};
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
-}
-
-extern "C" int rnf_flow_log_prob_shared(const float *rot, const float *feat, int64_t n, int32_t F, int64_t feature_div, const float *blob,
-                                        const int32_t *desc, int32_t n_layers, int32_t K, const float *fisher_A, const float *fisher_c,
-                                        int64_t fisher_B, float *rot_out, float *ldj_out, float *logp_out, double *sum_out, void *ws,
-                                        size_t ws_bytes, void *stream) {
-    if ((fisher_A == nullptr) != (fisher_c == nullptr)) return fail("fisher_A and fisher_c must both be given or both be null");
-    RunOpts o{0, fisher_A, fisher_c, fisher_B, logp_out, sum_out};
-    o.feature_div = feature_div;
-    return run_flow(rot, feat, n, F, blob, desc, n_layers, K, rot_out, ldj_out, ws, ws_bytes, stream, o);
+    RnfFlowBackward x{};
+    x.struct_bytes = sizeof(x);
+    x.feature = feat; x.n = n; x.feature_dim = F; x.plain = plain; x.train_desc = tdesc; x.n_layers = 1; x.segments = 8;
+    x.grads = grads; x.g_feature = g_feature; x.layer_scratch = scratch1; x.stream = stream_v;
+    return run_backward(x, g_out);
 }
 
 // ------------------------------------------------------------------------------------------------------------

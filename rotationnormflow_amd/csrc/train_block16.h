@@ -854,7 +854,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void flow_train_backward16_kernel(co
 // For the reference's batches (128-1024 rotations) the fused stack kernel of flow_kernels.h is a latency chain of one wave per 32 rotations
 // (0.27 ms for 24 layer pairs at batch 1024); here 4 waves share the conditioner of 16 rotations and the K segments are split 16 ways.
 // Layer kinds: Moebius, Uncondition16Trans / UnconditionRot, Condition16Trans (forward direction); the launcher keeps every other flow on
-// the stack kernel.  Saves the rotation entering every layer (args.states), as rnf_flow_forward_train does.
+// the stack kernel.  Saves the rotation entering every layer (args.states), as rnf_flow_pass with states does.
 struct FwdArgs {
     const float *rot;         // [n][9]
     const float *feature;     // [n][F] (unpadded) or nullptr

@@ -2,7 +2,7 @@
 
 ``Flow(config)`` builds the same ModuleList (same order, same state-dict keys) as flow/flow.py:19-51; ``forward`` /
 ``inverse`` keep the reference signatures and return ``(rotation' [N,3,3], ldjs [N])`` but the whole layer stack runs
-as ONE fused HIP kernel launch (rnf_flow_forward / rnf_flow_inverse).  ``log_prob`` is the fused density evaluation
+as ONE fused HIP kernel launch (rnf_flow_pass).  ``log_prob`` is the fused density evaluation
 (flow + matrix-Fisher base + NLL sum) used by the benchmark and by rotationnormflow_amd.dist.
 """
 import torch

@@ -655,8 +655,30 @@ def _watch_guard(module, packed, ws):
         watch.watch(ws)
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _flow_pass(module, packed, rot, feat, feature, feature_div=0, inverse=False, **outputs):
+    """One rnf_flow_pass call of a packed flow on n > 0 rotations ``rot`` with the padded feature rows ``feat`` (n / feature_div of them
+    when ``feature_div`` > 0); ``feature`` is what the side layers build their matrices from.  ``outputs``: the output and base-density
+    fields of RnfFlowPass.  The library sizes the workspace."""
+    L = _lib.lib()
+    dev = rot.device
+    with torch.cuda.device(dev):
+        side = build_side_buffer(packed, feature, rot.shape[0], dev, inverse) if packed.side_layers else None
+        p = _lib.FlowPass(dir=int(inverse), rotation=rot.data_ptr(), feature=_ptr(feat), n=rot.shape[0], feature_dim=packed.feat_padded,
+                          feature_div=feature_div, side=_ptr(side), blob=packed.blob.data_ptr(), desc=packed.desc.ctypes.data,
+                          n_layers=packed.n_layers, segments=packed.segments, stream=torch.cuda.current_stream(dev).cuda_stream, **outputs)
+        ws = workspace(dev, L.rnf_flow_pass_workspace_bytes(p))
+        p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+        _lib.check(L.rnf_flow_pass(p))
+    if not feature_div and side is None:                  # plain calls only: neither shared feature rows nor side layers
+        _watch_guard(module, packed, ws)
+
+
 def run_flow(module, packed, rotation, feature, inverse=False, train_layers=None, train_rows=None, feature_repeat=None):
-    """-> (rotation' [N,3,3], ldj [N]) through rnf_flow_forward / rnf_flow_inverse.
+    """-> (rotation' [N,3,3], ldj [N]) through rnf_flow_pass (Flow.forward, or Flow.inverse when ``inverse``).
     When a gradient is required (training, agent.py:75-92) the forward direction goes through autograd.flow_forward, which
     needs the layer modules and their permutation rows (``train_layers``, ``train_rows``) and packs on the device itself.
     ``packed`` may be a callable that builds the host-packed flow on demand.
@@ -682,33 +704,12 @@ def run_flow(module, packed, rotation, feature, inverse=False, train_layers=None
         feature_repeat, shared = None, False
     rot, feat = _check_inputs(rotation, feature, packed, feature_repeat if shared else None)
     n = rot.shape[0]
-    L = _lib.lib()
     out_rot = torch.empty_like(rot)
     out_ldj = torch.empty(n, dtype=torch.float32, device=rot.device)
     if n == 0:                                             # empty batch: nothing to launch (data_ptr() would be null)
         return out_rot.reshape(rotation.shape), out_ldj
-    with torch.cuda.device(rot.device):
-        stream = torch.cuda.current_stream(rot.device).cuda_stream
-        if shared:
-            ws = workspace(rot.device, L.rnf_workspace_bytes_shared(n, packed.n_cond, feature_repeat))
-            fn = L.rnf_flow_inverse_shared if inverse else L.rnf_flow_forward_shared
-            _lib.check(fn(rot.data_ptr(), feat.data_ptr(), n, packed.feat_padded, feature_repeat, packed.blob.data_ptr(),
-                          packed.desc.ctypes.data, packed.n_layers, packed.segments, out_rot.data_ptr(), out_ldj.data_ptr(),
-                          ws.data_ptr(), ws.numel(), stream))
-        elif packed.side_layers:
-            side = build_side_buffer(packed, feature, n, rot.device, inverse)
-            ws = workspace(rot.device, L.rnf_workspace_bytes_segments(n, max(packed.n_cond, 1), packed.segments if inverse else 0))
-            fn = L.rnf_flow_inverse_side if inverse else L.rnf_flow_forward_side
-            _lib.check(fn(rot.data_ptr(), feat.data_ptr() if feat is not None else None, n, packed.feat_padded, side.data_ptr(),
-                          packed.blob.data_ptr(), packed.desc.ctypes.data, packed.n_layers, packed.segments,
-                          out_rot.data_ptr(), out_ldj.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-        else:
-            ws = workspace(rot.device, L.rnf_workspace_bytes_segments(n, packed.n_cond, packed.segments) if inverse else L.rnf_workspace_bytes(n, packed.n_cond))
-            fn = L.rnf_flow_inverse if inverse else L.rnf_flow_forward
-            _lib.check(fn(rot.data_ptr(), feat.data_ptr() if feat is not None else None, n, packed.feat_padded,
-                          packed.blob.data_ptr(), packed.desc.ctypes.data, packed.n_layers, packed.segments,
-                          out_rot.data_ptr(), out_ldj.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-            _watch_guard(module, packed, ws)
+    _flow_pass(module, packed, rot, feat, feature, feature_repeat if shared else 0, inverse,
+               rotation_out=out_rot.data_ptr(), ldj_out=out_ldj.data_ptr())
     return out_rot.reshape(rotation.shape), out_ldj
 
 
@@ -722,7 +723,6 @@ def run_log_prob(module, packed: PackedFlow, rotation, feature, fisher_A=None, f
     shared = bool(feature_repeat) and packed.n_cond > 0
     rot, feat = _check_inputs(rotation, feature, packed, feature_repeat if shared else None)
     n = rot.shape[0]
-    L = _lib.lib()
     dev = rot.device
     out_rot = torch.empty_like(rot) if want_rotation else None
     out_ldj = torch.empty(n, dtype=torch.float32, device=dev) if want_ldj else None
@@ -735,27 +735,6 @@ def run_log_prob(module, packed: PackedFlow, rotation, feature, fisher_A=None, f
         fisher_A = fisher_A.reshape(-1, 3, 3).to(device=dev, dtype=torch.float32).contiguous()
         fisher_c = fisher_c.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
         B = fisher_A.shape[0]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if shared:
-            ws = workspace(dev, L.rnf_workspace_bytes_shared(n, packed.n_cond, feature_repeat))
-            _lib.check(L.rnf_flow_log_prob_shared(rot.data_ptr(), ptr(feat), n, packed.feat_padded, feature_repeat, packed.blob.data_ptr(),
-                                                  packed.desc.ctypes.data, packed.n_layers, packed.segments,
-                                                  ptr(fisher_A), ptr(fisher_c), B, ptr(out_rot), ptr(out_ldj), ptr(out_lp),
-                                                  out_sum.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-        elif packed.side_layers:
-            side = build_side_buffer(packed, feature, n, dev, False)
-            ws = workspace(dev, L.rnf_workspace_bytes(n, max(packed.n_cond, 1)))
-            _lib.check(L.rnf_flow_log_prob_side(rot.data_ptr(), ptr(feat), n, packed.feat_padded, side.data_ptr(), packed.blob.data_ptr(),
-                                                packed.desc.ctypes.data, packed.n_layers, packed.segments,
-                                                ptr(fisher_A), ptr(fisher_c), B, ptr(out_rot), ptr(out_ldj), ptr(out_lp),
-                                                out_sum.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-        else:
-            ws = workspace(dev, L.rnf_workspace_bytes(n, packed.n_cond))
-            _lib.check(L.rnf_flow_log_prob(rot.data_ptr(), ptr(feat), n, packed.feat_padded, packed.blob.data_ptr(),
-                                           packed.desc.ctypes.data, packed.n_layers, packed.segments,
-                                           ptr(fisher_A), ptr(fisher_c), B, ptr(out_rot), ptr(out_ldj), ptr(out_lp),
-                                           out_sum.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-            _watch_guard(module, packed, ws)
+    _flow_pass(module, packed, rot, feat, feature, feature_repeat if shared else 0, fisher_A=_ptr(fisher_A), fisher_c=_ptr(fisher_c),
+               fisher_B=B, rotation_out=_ptr(out_rot), ldj_out=_ptr(out_ldj), logp_out=_ptr(out_lp), sum_out=out_sum.data_ptr())
     return dict(logp=out_lp, sum=out_sum, rotation=out_rot, ldj=out_ldj)

@@ -24,14 +24,14 @@ def quiet_flow(cfg):
         return Flow(cfg)
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_8():
     header = open(os.path.join(ROOT, "include", "rnf_hip.h")).read()
     declared = set(re.findall(r"\b(rnf_[a-z0-9_]+)\s*\(", header))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     handle = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(handle, name), name
-    assert _lib.lib().rnf_abi_version() == _lib.ABI_VERSION == 7
+    assert _lib.lib().rnf_abi_version() == _lib.ABI_VERSION == 8
 
 
 def test_packed_sizes_match_parameter_counts():
@@ -192,7 +192,7 @@ def test_fisher_constants_match_oracle():
         assert (got - want).abs().max() < 2e-6
 
 
-def test_argument_validation_happens_before_any_gpu_work():
+def test_pass_struct_validation_happens_before_any_gpu_work():
     """Every entry point checks its arguments on the host first: these calls return an error code (and a message) without a GPU."""
     import numpy as np
     L = _lib.lib()
@@ -205,31 +205,56 @@ def test_argument_validation_happens_before_any_gpu_work():
     assert L.rnf_cond36_packed_floats() == L.rnf_cond16_packed_floats() + 2080
     # training entry points
     tdesc = np.array([[1, 0, 0]], np.int32)
-    args = (None, None, 64, 0, None, tdesc.ctypes.data, 1, 513, None, None, None, None, None, None, None)      # K <= 512 (LDS of a 16-rotation block)
-    assert L.rnf_flow_backward(*args) != 0 and "segments" in err()
-    args = (None, None, 64, 0, None, tdesc.ctypes.data, 401, 64, None, None, None, None, None, None, None)        # <= 400 layers, like the forward passes
-    assert L.rnf_flow_backward(*args) != 0 and "n_layers" in err()
-    args = (None, None, 0, 0, None, tdesc.ctypes.data, 1, 64, None, None, None, None, None, None, None)
-    assert L.rnf_flow_backward(*args) == 0                                  # empty batch: nothing to do
+    bwd = lambda **kw: L.rnf_flow_backward_pass(_lib.FlowBackward(**kw))  # noqa: E731
+    assert bwd(n=64, train_desc=tdesc.ctypes.data, n_layers=1, segments=513) != 0 and "segments" in err()   # K <= 512 (LDS of a 16-rotation block)
+    assert bwd(n=64, train_desc=tdesc.ctypes.data, n_layers=401, segments=64) != 0 and "n_layers" in err()  # <= 400 layers, like the forward passes
+    assert bwd(n=0, train_desc=tdesc.ctypes.data, n_layers=1, segments=64) == 0                             # empty batch: nothing to do
     pdesc = np.array([[15, 0, 0, -1]], np.int32)
     assert L.rnf_pack_flow_device(buf.ctypes.data, pdesc.ctypes.data, 1, 64, 0, 1, buf.ctypes.data, buf.ctypes.data, None) != 0 and "kind" in err()
     assert L.rnf_pack_flow_device(buf.ctypes.data, pdesc.ctypes.data, 1, 0, 0, 1, buf.ctypes.data, buf.ctypes.data, None) != 0 and "must be positive" in err()
     assert L.rnf_plain_layer_floats(1, 64, 0) == 29376 and L.rnf_plain_layer_floats(2, 64, 0) == 16
     assert L.rnf_plain_layer_floats(3, 64, 40) == 64 * 40 + 64 + 3 * 4160 + 16 * 65
-    # shared feature rows
-    assert L.rnf_workspace_bytes_shared(1 << 20, 42, 512) == 4096 * 8 + 42 * 2048 * 64 * 4
-    assert L.rnf_workspace_bytes_shared(1 << 20, 42, 0) == L.rnf_workspace_bytes(1 << 20, 42)
+    # the flow pass sizes its own workspace: feature-projection slots counted from the desc, one record per (slot, row) with shared feature
+    # rows, the per-wave stash of an inverse pass with K > 128 (256 CUs: the MI355X's count, also what the library assumes without a device)
+    desc = np.full((42, 8), -1, np.int32)
+    desc[:, 0], desc[:, 1], desc[:, 3] = 1, 0, np.arange(42)
+    ws = lambda **kw: L.rnf_flow_pass_workspace_bytes(_lib.FlowPass(n=1 << 20, desc=desc.ctypes.data, n_layers=42, **kw))  # noqa: E731
+    assert ws(segments=64, feature_div=512) == 4096 * 8 + 42 * 2048 * 64 * 4
+    assert ws(segments=64) == ws(segments=64, feature_div=0) == L.rnf_workspace_bytes(1 << 20, 42)
+    assert ws(segments=256) == ws(segments=128, dir=1) == L.rnf_workspace_bytes(1 << 20, 42)                 # forward / K <= 128: no stash
+    assert ws(segments=256, dir=1) == L.rnf_workspace_bytes(1 << 20, 42) + 256 * 4 * (4 * 16) * 64 * 16
+    bad = _lib.FlowPass()
+    bad.struct_bytes -= 8
+    assert L.rnf_flow_pass(bad) != 0 and "struct_bytes" in err() and L.rnf_flow_pass_workspace_bytes(bad) == 0
+    bad = _lib.FlowBackward()
+    bad.struct_bytes += 8
+    assert L.rnf_flow_backward_pass(bad) != 0 and "struct_bytes" in err()
+    # field combinations no caller uses are refused (n_layers = 0 would be refused next: nothing reaches a launch)
+    p = buf.ctypes.data
+    for fields, word in ((dict(dir=1, logp_out=p), "dir 0"), (dict(dir=1, sum_out=p), "dir 0"), (dict(dir=1, fisher_A=p, fisher_c=p, fisher_B=1), "dir 0"),
+                         (dict(fisher_A=p), "fisher_c"), (dict(states=p, rotation_out=p, feature_div=8), "feature_div"),
+                         (dict(states=p, rotation_out=p, logp_out=p), "logp_out"), (dict(states=p), "rotation_out"),
+                         (dict(side=p, feature_div=8), "feature_div"), (dict(feature_div=-1), "negative")):
+        assert L.rnf_flow_pass(_lib.FlowPass(rotation=p, n=64, segments=8, **fields)) != 0 and word in err(), fields
+    assert L.rnf_flow_pass(_lib.FlowPass(rotation=p, n=64, segments=8)) != 0 and "n_layers" in err()
+    # saved activations: dir 0 and the layer kinds the plain-blob forward runs only (a second, unknown layer would be refused next)
+    gdesc = np.array([[4, 0, 0], [15, 0, 0]], np.int32)
+    bwd_args = dict(states=p, n=64, plain=p, train_desc=gdesc.ctypes.data, n_layers=2, segments=16, g_ldj=p, g_rotation_in=p, layer_scratch=p, acts=p)
+    assert bwd(**bwd_args) != 0 and "acts" in err() and "layer 0" in err()
+    assert bwd(dir=1, rotation_out=p, **bwd_args) != 0 and "acts" in err()
+    assert bwd(dir=1, **dict(bwd_args, acts=None)) != 0 and "rotation_out" in err()                     # the inverse sweep reads the roots
     # round-2 entry points: plain-blob sizes of the new trainable kinds, side-layer training, the conditioner backward, the Fisher gradient
     assert L.rnf_plain_layer_floats(5, 64, 0) == 36 and L.rnf_plain_layer_floats(11, 64, 24) == 0
     assert L.rnf_plain_layer_floats(6, 64, 24) == 64 * 24 + 64 + 3 * 4160 + 9 * 65
     assert L.rnf_plain_layer_floats(10, 64, 24) == 64 * 24 + 64 + 3 * 4160 + 36 * 65
-    sdesc = np.array([[11 | (0 << 16), 0, 0]], np.int32)
-    args = (0, buf.ctypes.data, None, None, 64, 0, buf.ctypes.data, sdesc.ctypes.data, 1, 16, None, None, None, buf.ctypes.data, None, buf.ctypes.data,
-            None, buf.ctypes.data, None)
-    assert L.rnf_flow_backward_side(*args) != 0 and "side" in err()             # a side layer without its side / side_grad buffers
-    args = (2,) + args[1:]
-    assert L.rnf_flow_backward_side(*args) != 0 and "dir" in err()
-    assert L.rnf_flow_train_side(3, None, None, 0, 0, None, None, None, 1, 8, None, None, None, None, 0, None) != 0 and "dir" in err()
+    sdesc = np.array([[11 | (0 << 16), 0, 0], [15, 0, 0]], np.int32)        # (the unknown second layer would be refused next)
+    side_args = dict(states=p, n=64, plain=p, train_desc=sdesc.ctypes.data, n_layers=2, segments=16, g_ldj=p, g_rotation_in=p, layer_scratch=p)
+    assert bwd(**side_args) != 0 and "side_grad" in err()                    # a side layer without its side / side_grad buffers
+    assert bwd(side=p, **side_args) != 0 and "side_grad" in err()
+    assert bwd(dir=2, **side_args) != 0 and "dir" in err()
+    assert L.rnf_flow_pass(_lib.FlowPass(dir=3, n_layers=1, segments=8)) != 0 and "dir" in err()
+    fdesc = np.array([[11, 0, 0, -1, -1, 0, -1, -1], [1, 0, 0, 0, 0, 0, -1, -1]], np.int32)   # a side layer: the side buffer is required
+    assert L.rnf_flow_pass(_lib.FlowPass(rotation=p, n=64, blob=p, desc=fdesc.ctypes.data, n_layers=2, segments=8)) != 0 and "side" in err()
     assert L.rnf_cond_mlp_backward(buf.ctypes.data, 64, 24, buf.ctypes.data, 65, buf.ctypes.data, None, None, buf.ctypes.data, None) != 0 and "n_out" in err()
     assert L.rnf_cond_mlp_backward(None, 64, 24, buf.ctypes.data, 16, buf.ctypes.data, None, None, buf.ctypes.data, None) != 0 and "null" in err()
     assert L.rnf_fisher_scratch_bytes(7) == (2 + 70) * 8

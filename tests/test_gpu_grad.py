@@ -1,4 +1,4 @@
-"""GPU: the training path (differentiable Flow.forward: rnf_flow_forward_train + rnf_flow_backward through the C ABI) against
+"""GPU: the training path (differentiable Flow.forward: rnf_flow_pass with states + rnf_flow_backward_pass through the C ABI) against
 torch autograd of the fp64 oracle -- what loss.backward() produces in the reference's training loop (agent.py:75-92).
 
 Parameter and feature gradients are compared in full.  The gradient w.r.t. the input rotation is compared on the tangent space of
@@ -162,7 +162,7 @@ def test_gradients_match_oracle_autograd(name):
 @pytest.mark.parametrize("kind", ["lu16", "rot16", "lu9"])
 def test_side_kernels_in_isolation(kind, inverse):
     """The kernel half of side-layer training on WELL-CONDITIONED per-sample matrices given as a leaf tensor: outputs, dL/d(matrix)
-    (rnf_flow_backward_side's side_grad) and dL/dR against fp64 autograd of the oracle's layer functions, forward and inverse pass."""
+    (RnfFlowBackward.side_grad) and dL/dR against fp64 autograd of the oracle's layer functions, forward and inverse pass."""
     from rotationnormflow_amd.flow.squeezetrans import Condition16TransLU, Condition9TransLU
     from rotationnormflow_amd.flow.rottrans import ConditionRot
     n = 70
@@ -211,7 +211,7 @@ INVERSE_CASES = ["uncond_k16", "uncond_k20", "cond_k11", "cond_k32", "uncond_k96
 
 @pytest.mark.parametrize("name", INVERSE_CASES)
 def test_inverse_gradients_match_oracle_autograd(name):
-    """Gradients THROUGH Flow.inverse (rnf_flow_inverse_train + rnf_flow_inverse_backward): BinFind.backward's implicit-function rule
+    """Gradients THROUGH Flow.inverse (rnf_flow_pass with states and dir 1 + rnf_flow_backward_pass): BinFind.backward's implicit-function rule
     for the Moebius layers (flow/mobiusflow.py:247-273), M^-1 for the affine layers, against fp64 autograd of the oracle (whose BinFind
     Function is pinned to the reference's own backward, tests/test_oracle_golden.py)."""
     cfg, w, R, feat, gR, gl = _make(name)
