@@ -85,7 +85,8 @@ extern "C" {
  *                  accumulator per product-sum.  Nothing data- or scale-dependent: no equalisation, no audit, no feature calibration, no range
  *                  guard.  Records are larger (rnf_mobius_packed_floats_prec / rnf_cond_packed_floats_prec: a weight tile is 3072 floats
  *                  instead of 2048), the feature-projection record holds the RNF_PREC_FP32 image, and the kernels stage synchronously.
- *                  Host-packed flows only (rnf_pack_flow_device does not build it).
+ *                  Built by the host packers and by rnf_pack_flow_device (same bits); rnf_cond_mlp_forward and rnf_conditioner_forward
+ *                  run it too.  The 16-rotation training forward and the backward sweeps run exact fp32 whatever the records hold.
  */
 #define RNF_PREC_FP32 0
 #define RNF_PREC_F16X2 1
@@ -255,7 +256,8 @@ int rnf_condlu_backward(const float *wl_dev, const float *wu_dev, const float *w
                         float *g_ws_dev, float *scratch_dev, void *stream);
 
 /* ConditionalTransform(feature_dim, <= 16 outputs)(feature) alone (flow/condition.py:24-30): records packed by rnf_pack_cond16 at
- * layer_offset / feat_offset (floats) of blob_dev; out_dev float[n][16], output o in column o.  Workspace: rnf_workspace_bytes(n, 1). */
+ * layer_offset / feat_offset (floats) of blob_dev; out_dev float[n][16], output o in column o.  Workspace: rnf_workspace_bytes(n, 1).
+ * RNF_PREC_BF16X3 projects the feature in exact fp32, as the flow pass does. */
 int rnf_cond_mlp_forward(const float *feature_dev, int64_t n, int32_t feature_dim, const float *blob_dev, int32_t layer_offset,
                          int32_t feat_offset, int32_t precision, float *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
@@ -278,7 +280,8 @@ size_t rnf_plain_layer_floats(int32_t kind, int32_t segments, int32_t feature_di
  * the layer record in the kernel blob, offset of its feature-projection record (or -1), all in floats; record offsets are
  * multiples of 4.  feature_dim is the real (unpadded) width; records are laid out for it padded to a multiple of 8.
  * flags_dev: device int32, zeroed by the caller; bit 0 = a weight outside the fp16 range under RNF_PREC_F16X2 (the blob
- * then holds inf/NaN), bit 1 = a singular 4x4 matrix. */
+ * then holds inf/NaN), bit 1 = a singular 4x4 matrix.  All three precisions; RNF_PREC_F16X2 alone is equalised (RNF_PREC_BF16X3
+ * records are sized by rnf_mobius_packed_floats_prec / rnf_cond_packed_floats_prec, their projection records hold the fp32 image). */
 int rnf_pack_flow_device(const float *plain_dev, const int32_t *pack_desc, int32_t n_layers, int32_t segments,
                          int32_t feature_dim, int32_t precision, float *blob_dev, int32_t *flags_dev, void *stream);
 

@@ -62,15 +62,15 @@ class TrainPlan:
                 rec_off += 4
                 continue
             if kind == runtime.KIND_MOBIUS:
-                size = L.rnf_mobius_packed_floats(self.segments)
+                size = L.rnf_mobius_packed_floats_prec(self.segments, self.prec)
             elif kind == runtime.KIND_COND16 or kind in runtime.COND9_KINDS:
-                size = L.rnf_cond16_packed_floats()                # Condition9*: the same record with a 9-row fc_last
+                size = L.rnf_cond_packed_floats_prec(16, self.prec)    # Condition9*: the same record with a 9-row fc_last
             elif kind == runtime.KIND_GS9:
                 size = L.rnf_gs_packed_floats(3)
             elif kind == runtime.KIND_GS36:
                 size = L.rnf_gs_packed_floats(6)
             elif kind == runtime.KIND_COND36:
-                size = L.rnf_cond36_packed_floats()
+                size = L.rnf_cond_packed_floats_prec(36, self.prec)
             else:
                 size = L.rnf_affine16_packed_floats()
             rec_sizes.append(size)
@@ -79,7 +79,7 @@ class TrainPlan:
             if f:
                 self.desc[i, 3] = slot
                 slot += 1
-        fsize = L.rnf_featproj_packed_floats(self.feat_padded) if self.feat_dim else 0
+        fsize = L.rnf_featproj_packed_floats(self.feat_padded) if self.feat_dim else 0     # (bf16x3: the exact-fp32 projection image)
         for i, (kind, k, f) in enumerate(shapes):
             if f and kind not in runtime.SIDE_KINDS:
                 self.desc[i, 4] = self.pack_desc[i, 3] = rec_off
@@ -363,7 +363,7 @@ class _CondMLPFn(torch.autograd.Function):
         plain16 = torch.cat([t.reshape(-1) for t in ts[:-2]] + [wl.reshape(-1), wl.new_zeros((16 - n_out) * 64), bl, bl.new_zeros(16 - n_out)])
         Fp = runtime.pad8(F)
         prec = runtime._PRECISIONS[runtime.device_precision()]
-        rec = (L.rnf_cond16_packed_floats() + 3) // 4 * 4
+        rec = (L.rnf_cond_packed_floats_prec(16, prec) + 3) // 4 * 4
         blob = torch.empty(rec + L.rnf_featproj_packed_floats(Fp), dtype=f32, device=dev)
         pack_desc = np.array([[runtime.KIND_COND16, 0, 0, rec]], dtype=np.int32)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -379,7 +379,7 @@ class _CondMLPFn(torch.autograd.Function):
                 _lib.check(L.rnf_pack_flow_device(plain16.data_ptr(), pack_desc.ctypes.data, 1, 8, F, prec, blob.data_ptr(), flags.data_ptr(), stream))
                 _lib.check(L.rnf_cond_mlp_forward(fpad.data_ptr(), n, Fp, blob.data_ptr(), 0, rec, prec, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                   stream))
-                if prec and not capturing and len(_pending_mlp_flags) < 64:
+                if prec == _lib.PREC_F16X2 and not capturing and len(_pending_mlp_flags) < 64:     # (only the fp16 split can overflow)
                     host = torch.zeros(1, dtype=torch.int32).pin_memory()
                     host.copy_(flags, non_blocking=True)
                     ev = torch.cuda.Event()

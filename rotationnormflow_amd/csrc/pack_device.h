@@ -43,10 +43,30 @@ __device__ __forceinline__ float pack2(float a, float b) {           // two fp16
     return __uint_as_float((unsigned)ua | ((unsigned)ub << 16));
 }
 
+// bf16x3 element of one weight (rnf_api.hip pack_w64_b3): term t of the truncated three-term split, as the low 16 bits
+__device__ __forceinline__ unsigned b3_term(float w, int t) {
+    const unsigned uh = __float_as_uint(w) & 0xffff0000u;
+    const float r1 = w - __uint_as_float(uh);                          // exact
+    const unsigned um = __float_as_uint(r1) & 0xffff0000u;
+    const float r2 = r1 - __uint_as_float(um);                         // exact
+    return (t == 0 ? uh : (t == 1 ? um : __float_as_uint(r2))) >> 16;
+}
+
 // float `r` of a [n_ot][...] weight image of 64-column rows; val(ot, i, col) -> the (already scaled) source value of row i of out tile
-// ot, column col (0 for a padding row)
-template <class ValFn>
+// ot, column col (0 for a padding row).  B3: the bf16x3 image (layout.h Lay<2>), whatever `prec` says.
+template <bool B3 = false, class ValFn>
 __device__ __forceinline__ float w64_image(int r, int prec, ValFn val, int *flags) {
+    if constexpr (B3) {                                                // [ot][s 4][hi, mid, lo][lane 64] 8 x bf16
+        unsigned v[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int e = 2 * r + q;
+            const int ot = e / 6144, rem = e % 6144;
+            const int s = rem / 1536, t = (rem >> 9) % 3, lane = (rem >> 3) & 63, j = e & 7;
+            v[q] = b3_term(val(ot, lane & 31, 16 * s + 8 * (j >> 2) + 4 * (lane >> 5) + (j & 3)), t);
+        }
+        return __uint_as_float(v[0] | (v[1] << 16));
+    }
     if (!prec) {                                                       // [ot][tg 8][lane 64] float4
         const int ot = r >> 11, tg = (r >> 8) & 7, lane = (r >> 2) & 63, c = r & 3;
         return val(ot, lane & 31, 8 * tg + 4 * (lane >> 5) + c);
@@ -112,7 +132,12 @@ __device__ inline bool inv4_double_dev(const double *m, double *inv, double *det
     return true;
 }
 
+// B3: the bf16x3 images (args.prec == 2): hidden and fc_last tiles at the Lay<2> offsets, the exact-fp32 feature-projection image
+// (bf16x3 flows project in exact fp32), no equalisation, nothing to flag.  A separate instantiation, so that the fp32 / f16x2 kernel is
+// the code it was (identical disassembly).
+template <bool B3>
 __global__ __launch_bounds__(256) void pack_flow_kernel(const PackArgs args) {
+    typedef Lay<B3 ? 2 : 0> LY;
     const PackLayer L = args.layers[blockIdx.y];
     const int kind = L.kind & 15;
     const float *P = args.plain + L.plain_off;
@@ -195,7 +220,7 @@ __global__ __launch_bounds__(256) void pack_flow_kernel(const PackArgs args) {
     hw[2] = hb[1] + 64; hb[2] = hw[2] + 4096;
     const float *WL = hb[2] + 64, *bL = WL + (size_t)NO * 64;
     const int n_tiles = mob ? (K + 7) / 8 : (kind == RNF_KIND_COND36 ? 2 : 1);
-    const int rec_floats = MOB_HEAD_FLOATS + n_tiles * MOB_LAST_TILE_FLOATS;
+    const int rec_floats = LY::HEAD_FLOATS + n_tiles * LY::LAST_TILE_FLOATS;
     // split precision: the layer's canonical scaling (equalize.h), the same per-unit functions the host packer evaluates, one unit per
     // thread; every workgroup of the layer computes the exponents for itself
     __shared__ double q_prev[64], q_cur[64], q_first[64];
@@ -238,27 +263,28 @@ __global__ __launch_bounds__(256) void pack_flow_kernel(const PackArgs args) {
             if (!mob) v = (e == 1 && h) ? ldexpf(b0[o], ex[0][o]) : 0.f;   // Condition16Trans: no rotation inputs, x0 = projection + b0
             else if (e == 0) v = ldexpf(W0[(size_t)o * ni + h], ex[0][o]);
             else v = h ? ldexpf(b0[o], ex[0][o]) : ldexpf(W0[(size_t)o * ni + 2], ex[0][o]);
-        } else if (idx < MOB_HB) {
-            const int q = idx - MOB_HID, Lh = q >> 12;
+        } else if (idx < LY::HB) {
+            const int q = idx - MOB_HID, Lh = B3 ? q / (2 * LY::W_TILE) : q >> 12;
             const float *W = hw[Lh];
             const int *eo = ex[(Lh + 1) % 3], *ei = ex[Lh];          // x1 <- x0, x2 <- x1, x3 (scaled like x0) <- x2
-            v = w64_image(q & 4095, prec, [&](int ot, int i, int col) { return ldexpf(W[(size_t)(32 * ot + i) * 64 + col], eo[32 * ot + i] - ei[col]); },
-                          args.flags);
-        } else if (idx < MOB_HEAD_FLOATS) {
-            const int q = idx - MOB_HB, Lh = q >> 6, row = bias_row(q & 63);
+            v = w64_image<B3>(B3 ? q % (2 * LY::W_TILE) : q & 4095, prec,
+                              [&](int ot, int i, int col) { return ldexpf(W[(size_t)(32 * ot + i) * 64 + col], eo[32 * ot + i] - ei[col]); },
+                              args.flags);
+        } else if (idx < LY::HEAD_FLOATS) {
+            const int q = idx - LY::HB, Lh = q >> 6, row = bias_row(q & 63);
             v = ldexpf(hb[Lh][row], ex[(Lh + 1) % 3][row]);
         } else {
-            const int q = idx - MOB_LAST, tau = q / MOB_LAST_TILE_FLOATS, r = q % MOB_LAST_TILE_FLOATS;
+            const int q = idx - LY::LAST, tau = q / LY::LAST_TILE_FLOATS, r = q % LY::LAST_TILE_FLOATS;
             // Moebius: the rows of the segment weights' pre-activations (source rows 0 .. K-1) are packed times log2 e (layout.h)
-            if (r < MOB_LAST_TILE_BIAS) {
-                v = w64_image(r, prec, [&](int, int i, int col) {
+            if (r < LY::LAST_TILE_BIAS) {
+                v = w64_image<B3>(r, prec, [&](int, int i, int col) {
                     const int s = src_row(tau, i);
                     if (s < 0) return 0.f;
                     const float w = ldexpf(WL[(size_t)s * 64 + col], -ex[0][col]);
                     return (mob && s < K) ? w * S_PRESCALE : w;
                 }, args.flags);
             } else {
-                const int s = src_row(tau, bias_row(r - MOB_LAST_TILE_BIAS));
+                const int s = src_row(tau, bias_row(r - LY::LAST_TILE_BIAS));
                 v = s < 0 ? 0.f : ((mob && s < K) ? bL[s] * S_PRESCALE : bL[s]);
             }
         }
@@ -266,11 +292,12 @@ __global__ __launch_bounds__(256) void pack_flow_kernel(const PackArgs args) {
     }
     if (L.feat_off >= 0) {                                             // feature projection record (pack_featproj / pack_featproj_h)
         float *fo = args.blob + L.feat_off;
-        const int w_floats = prec ? 2 * ((Fp + 15) / 16) * 512 : 2 * (Fp / 8) * 256;
+        const int fprec = B3 ? 0 : prec;                              // bf16x3 flows: the exact-fp32 projection image
+        const int w_floats = fprec ? 2 * ((Fp + 15) / 16) * 512 : 2 * (Fp / 8) * 256;
         const int total = (int)featproj_packed_floats(Fp);
         for (int idx = tid; idx < total; idx += nth) {
             float v = 0.f;
-            if (idx < w_floats) v = featproj_image(idx, prec, W0, ni, yo, F, Fp, args.flags, ex[0]);
+            if (idx < w_floats) v = featproj_image(idx, fprec, W0, ni, yo, F, Fp, args.flags, ex[0]);
             // (bias image: zero -- see the fc_first image above)
             fo[idx] = v;
         }

@@ -1210,22 +1210,55 @@ extern "C" size_t rnf_flow_pass_workspace_bytes(const RnfFlowPass *p) {
 // ConditionalTransform(F, <= 16 outputs)(feature) alone (flow/condition.py:24-30): the nets of ConditionRot (flow/rottrans.py:40) and
 // ConditionLU (flow/squeezetrans.py:117-119), whose outputs the reference post-processes with batched torch ops.  Records from
 // rnf_pack_cond16 (rows beyond the net's outputs zero); out [n][16], output o of the net in column o.
+// bf16x3 (PREC 2) images in the LDS of the standalone kernels: the two head units of Mlp<2>::head_ring back to back -- Ha = [fc_first | hidden
+// tiles 0..2 | hidden biases], Hb = [hidden tiles 3..5 | hidden biases] -- then the fc_last tile(s); 22,176 floats (87 KiB) with one tile
+struct B3Head {
+    static constexpr int HA = 0, HB = Mlp<2>::HA_FLOATS, LAST = HB + Mlp<2>::HB_FLOATS;
+    static constexpr int HEAD_TILE_FLOATS = LAST + Lay<2>::LAST_TILE_FLOATS;
+    // the head of a Lay<2> record (hidden biases once, behind tile 5) -> Ha, Hb; Hb is one contiguous piece of the record
+    static __device__ __forceinline__ void stage(float *lds, const float *rec, int tid, int nthreads) {
+        stage_floats(lds + HA, rec, Mlp<2>::HA_BIAS, tid, nthreads);
+        stage_floats(lds + HA + Mlp<2>::HA_BIAS, rec + Lay<2>::HB, MOB_HB_FLOATS, tid, nthreads);
+        stage_floats(lds + HB, rec + Mlp<2>::HA_BIAS, Mlp<2>::HB_FLOATS, tid, nthreads);
+    }
+    // head_ring's unit control: both units are already resident
+    struct Units {
+        const float *lds;
+        int next = 0;
+        __device__ __forceinline__ const float *begin_unit() { return lds + (next++ ? HB : HA); }
+    };
+};
+static_assert(Mlp<2>::HA_BIAS + MOB_HB_FLOATS == Mlp<2>::HA_FLOATS && Mlp<2>::HA_BIAS + Mlp<2>::HB_FLOATS == Lay<2>::HEAD_FLOATS,
+              "B3Head: Hb is the record's head from hidden tile 3 on");
+
 template <int NWc, int PREC>
 __global__ __launch_bounds__(NWc * 64) void cond_mlp_kernel(const float *G, long long g_groups, long long n, const float *layer, float *out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, h = lane >> 5;
     const long long ntiles = (n + NWc * 32 - 1) / (NWc * 32);
-    stage_floats(lds, layer, MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS, tid, NWc * 64);
+    if constexpr (PREC == 2) {
+        B3Head::stage(lds, layer, tid, NWc * 64);
+        stage_floats(lds + B3Head::LAST, layer + Lay<2>::LAST, Lay<2>::LAST_TILE_FLOATS, tid, NWc * 64);
+    } else {
+        stage_floats(lds, layer, MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS, tid, NWc * 64);
+    }
     __syncthreads();
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long group = tile * NWc + wave;
         const long long sample = group * 32 + j;
         typename Mlp<PREC>::Act tt;
-        Fair nofair{lds, wave, -1, 0};
         bool bad = false;
         GFrag<false> g{G + (size_t)group * G_FLOATS_PER_GROUP, false};
-        Mlp<PREC>::head(lds, lane, h, 0.f, 0.f, 0.f, g, tt, nofair, bad);
-        const f32x16 o = Mlp<PREC>::last(lds + MOB_LAST, lane, h, tt);
+        f32x16 o;
+        if constexpr (PREC == 2) {
+            B3Head::Units units{lds};
+            Mlp<2>::head_ring<GFrag<false>, false>(units, lane, h, 0.f, 0.f, 0.f, g, tt, bad);
+            o = Mlp<2>::last(lds + B3Head::LAST, lane, h, tt);
+        } else {
+            Fair nofair{lds, wave, -1, 0};
+            Mlp<PREC>::head(lds, lane, h, 0.f, 0.f, 0.f, g, tt, nofair, bad);
+            o = Mlp<PREC>::last(lds + MOB_LAST, lane, h, tt);
+        }
         if (sample < n) {
 #pragma unroll
             for (int gq = 0; gq < 2; ++gq) {              // packed row 8g + 4h + c  <->  output 4 (2g + h) + c (rnf_pack_cond16)
@@ -1242,14 +1275,14 @@ extern "C" int rnf_cond_mlp_forward(const float *feat, int64_t n, int32_t F, con
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_v);
     if (n < 0) return fail("n=%lld is negative", (long long)n);
     if (F <= 0 || F % 8) return fail("feature_dim=%d must be a positive multiple of 8 (pad on the host)", F);
-    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2) return fail("unknown precision %d", prec);
+    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2 && prec != RNF_PREC_BF16X3) return fail("unknown precision %d", prec);
     if (layer_off < 0 || layer_off % 4 || feat_off < 0 || feat_off % 4) return fail("record offsets must be non-negative multiples of 4");
     if (n == 0) return 0;
     if (!feat || !blob || !out || !ws) return fail("rnf_cond_mlp_forward: null pointer");
     if (ws_bytes < rnf_workspace_bytes(n, 1)) return fail("workspace of %zu bytes is smaller than the %zu needed", ws_bytes, rnf_workspace_bytes(n, 1));
     float *G = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + PARTIALS_BYTES);
     const int cus = device_cus();
-    const size_t lds_bytes = sizeof(float) * (MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS);
+    const size_t lds_bytes = sizeof(float) * (prec == RNF_PREC_BF16X3 ? B3Head::HEAD_TILE_FLOATS : MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS);
     for (long long base = 0; base < n; base += CHUNK_SAMPLES) {
         const long long cn = (n - base) < CHUNK_SAMPLES ? (n - base) : CHUNK_SAMPLES;
         const long long ntiles = (cn + NW * 32 - 1) / (NW * 32), ntiles_fp = (cn + NW_FP * 32 - 1) / (NW_FP * 32);
@@ -1261,9 +1294,9 @@ extern "C" int rnf_cond_mlp_forward(const float *feat, int64_t n, int32_t F, con
         const int cus_fp = cus * (8 / NW_FP);
         const int grid_fp = (int)(ntiles_fp < cus_fp ? ntiles_fp : cus_fp);
         const int kchunk = F < FP_KCHUNK ? F : FP_KCHUNK;
-        const size_t fl = sizeof(float) * (prec ? (size_t)2 * (FP_KCHUNK / 16) * 512 : (size_t)kchunk / 8 * 256);
+        const size_t fl = sizeof(float) * (prec == RNF_PREC_F16X2 ? (size_t)2 * (FP_KCHUNK / 16) * 512 : (size_t)kchunk / 8 * 256);
         const int grid = (int)(ntiles < cus ? ntiles : cus);
-        if (prec) {
+        if (prec == RNF_PREC_F16X2) {
             if (F > FP_KCHUNK && F <= 2 * FP_KCHUNK) {
                 const long long pt2 = (cn + 127) / 128;
                 auto kp = featproj_ksplit_kernel;
@@ -1281,11 +1314,11 @@ extern "C" int rnf_cond_mlp_forward(const float *feat, int64_t n, int32_t F, con
             auto kern = cond_mlp_kernel<NW, 1>;
             HIP_TRY(allow_lds(kern, lds_bytes));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, (const float *)G, groups, cn, blob + layer_off, out + base * 16);
-        } else {
+        } else {                                                // exact fp32 and bf16x3: the exact-fp32 projection (as the flow pass projects)
             auto kp = featproj_kernel<NW_FP, 0>;
             HIP_TRY(allow_lds(kp, fl));
             hipLaunchKernelGGL(kp, dim3(grid_fp), dim3(NW_FP * 64), fl, stream, fp);
-            auto kern = cond_mlp_kernel<NW, 0>;
+            auto kern = prec == RNF_PREC_BF16X3 ? cond_mlp_kernel<NW, 2> : cond_mlp_kernel<NW, 0>;
             HIP_TRY(allow_lds(kern, lds_bytes));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, (const float *)G, groups, cn, blob + layer_off, out + base * 16);
         }
@@ -1545,7 +1578,7 @@ extern "C" int rnf_pack_flow_device(const float *plain, const int32_t *pdesc, in
     if (n_layers < 0 || n_layers > MAX_LAYERS) return fail("n_layers=%d outside [0,%d] (device packer)", n_layers, MAX_LAYERS);
     if (K <= 0) return fail("segments=%d must be positive", K);
     if (F < 0) return fail("feature_dim %d is negative", F);
-    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2) return fail("unknown precision %d", prec);
+    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2 && prec != RNF_PREC_BF16X3) return fail("unknown precision %d", prec);
     if (n_layers == 0) return 0;
     if (!plain || !pdesc || !blob || !flags) return fail("null pointer argument");
     PackArgs a;
@@ -1572,7 +1605,8 @@ extern "C" int rnf_pack_flow_device(const float *plain, const int32_t *pdesc, in
             a.layers[l] = PackLayer{d[0], d[1], d[2], d[3]};
         }
         a.n_layers = cnt;
-        hipLaunchKernelGGL(pack_flow_kernel, dim3(8, cnt), dim3(256), 0, stream, a);
+        if (prec == RNF_PREC_BF16X3) hipLaunchKernelGGL(pack_flow_kernel<true>, dim3(8, cnt), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(pack_flow_kernel<false>, dim3(8, cnt), dim3(256), 0, stream, a);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -2138,17 +2172,25 @@ __global__ __launch_bounds__(NWc * 64) void conditioner_kernel(const float *y, l
         float y0 = 0.f, y1 = 0.f, y2 = 0.f;
         if (valid) { y0 = y[sample * 3]; y1 = y[sample * 3 + 1]; y2 = y[sample * 3 + 2]; }
         __syncthreads();
-        stage_floats(lds, layer, MOB_HEAD_FLOATS, tid, NWc * 64);
+        if constexpr (PREC == 2) B3Head::stage(lds, layer, tid, NWc * 64);
+        else stage_floats(lds, layer, MOB_HEAD_FLOATS, tid, NWc * 64);
         __syncthreads();
         typename Mlp<PREC>::Act tt;
-        Fair nofair{lds, wave, -1, 0};
         bool bad = false;
-        Mlp<PREC>::head(lds, lane, h, y0, y1, y2, GFrag<false>{nullptr, false}, tt, nofair, bad);
+        if constexpr (PREC == 2) {
+            B3Head::Units units{lds};
+            Mlp<2>::head_ring<GFrag<false>, false>(units, lane, h, y0, y1, y2, GFrag<false>{nullptr, false}, tt, bad);
+        } else {
+            Fair nofair{lds, wave, -1, 0};
+            Mlp<PREC>::head(lds, lane, h, y0, y1, y2, GFrag<false>{nullptr, false}, tt, nofair, bad);
+        }
+        // fc_last: one tile at a time (bf16x3: the head and one tile are 87 KiB)
+        constexpr int T_LDS = PREC == 2 ? B3Head::LAST : MOB_LAST;
         for (int tau = 0; tau < KT; ++tau) {
             __syncthreads();
-            stage_floats(lds + MOB_LAST, layer + MOB_LAST + (size_t)tau * MOB_LAST_TILE_FLOATS, MOB_LAST_TILE_FLOATS, tid, NWc * 64);
+            stage_floats(lds + T_LDS, layer + Lay<PREC>::LAST + (size_t)tau * Lay<PREC>::LAST_TILE_FLOATS, Lay<PREC>::LAST_TILE_FLOATS, tid, NWc * 64);
             __syncthreads();
-            f32x16 o = Mlp<PREC>::last(lds + MOB_LAST, lane, h, tt);
+            f32x16 o = Mlp<PREC>::last(lds + T_LDS, lane, h, tt);
             if (valid) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -2166,13 +2208,17 @@ __global__ __launch_bounds__(NWc * 64) void conditioner_kernel(const float *y, l
 extern "C" int rnf_conditioner_forward(const float *y, int64_t n, const float *layer, int32_t K, int32_t prec, float *out,
                                        void *stream) {
     if (K <= 0) return fail("segments=%d must be positive", K);
-    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2) return fail("unknown precision %d", prec);
+    if (prec != RNF_PREC_FP32 && prec != RNF_PREC_F16X2 && prec != RNF_PREC_BF16X3) return fail("unknown precision %d", prec);
     if (!y || !layer || !out) return fail("rnf_conditioner_forward: null pointer");
     if (n == 0) return 0;
-    const size_t lds_bytes = sizeof(float) * (MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS);
+    const size_t lds_bytes = sizeof(float) * (prec == RNF_PREC_BF16X3 ? B3Head::HEAD_TILE_FLOATS : MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS);
     long long ntiles = (n + NW * 32 - 1) / (NW * 32);
     int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
-    if (prec) {
+    if (prec == RNF_PREC_BF16X3) {
+        auto kern = conditioner_kernel<NW, 2>;
+        HIP_TRY(allow_lds(kern, lds_bytes));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);
+    } else if (prec) {
         auto kern = conditioner_kernel<NW, 1>;
         HIP_TRY(allow_lds(kern, lds_bytes));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);

@@ -34,8 +34,9 @@ _fallback_precision = os.environ.get("RNF_FALLBACK", "bf16x3")       # arithmeti
 
 def device_precision() -> str:
     """The arithmetic of the paths whose kernel images are built ON THE DEVICE (training passes, nn.DataParallel replicas, the side layers'
-    conditioners): "bf16x3" images exist for host-packed flows only, those paths then run the exact-fp32 kernels."""
-    return "fp32" if _precision == "bf16x3" else _precision
+    conditioners): the selected one, for all three arithmetics (rnf_pack_flow_device writes the same images as the host packers).  The
+    16-rotation training forward and every backward sweep run exact fp32 whatever is selected."""
+    return _precision
 
 
 def set_precision(name: str):
