@@ -366,6 +366,46 @@ int rnf_min_geodesic(const float *est_dev, const float *gt_dev, int64_t n, int32
  * float[9]) or the identity when NULL.  fp64 inside, one rounding to fp32 per entry.  level 0..8 (level 8: 1.2e9 rows, 43 GB). */
 int rnf_so3_healpix_grid(int32_t level, const float *offset9_dev, float *out_dev, void *stream);
 
+/* Top-k pose modes of g images evaluated on one grid of the search above, with the probability mass each carries: the commented-out
+ * `for top_k in [1, 2, 4]` of eval.py:243,297,406 and the spread of IPDF (Murphy et al. 2021, the expected angular error under the
+ * predicted distribution).  Every grid cell has the same Haar volume and the flow densities are relative to the normalised Haar measure,
+ * so exp(lp_i) / Q is cell i's mass.  Per image, with thr = 1 + 2 cos(separation_rad) (a row is "within sep" of mode m when
+ * tr(M_m^T R_i) > thr; at separation_rad = pi every row is within sep of mode 0):
+ *   mode 0      the first arg-max of the image's log p, a NaN winning (torch.argmax);
+ *   mode j > 0  the first arg-max over the rows within sep of no earlier mode; index -1, log p -inf, mass 0 when there is none (and for
+ *               every later mode);
+ *   log_norm    log(sum_i exp(lp_i) / Q): the maximum M first, exp(lp_i - M) in fp32, sums in fp64;
+ *   mass_j      sum exp(lp_i - M) / sum_i exp(lp_i - M) over mode j's region: the rows within sep of mode j and of no earlier mode
+ *               (the masses add up to at most 1);
+ *   spread      sum_i p_i min_g acos(clip((tr(G_g^T R_i) - 1) / 2, -1, 1)) in radians against the image's ground truths, p the masses.
+ * A NaN in the image's log p: mode 0 as torch.argmax, modes > 0 index -1, log_norm, every mass and spread NaN.  A row without a finite
+ * value has log_norm -inf and NaN masses of its modes.  Deterministic: bit-identical from run to run and whatever g (no atomics). */
+typedef struct RnfGridModes {
+    size_t struct_bytes;        /* sizeof(RnfGridModes); any other value is refused (header and library differ) */
+    const float *logp;          /* dev float[g][Q]: image b's log p on grid row i */
+    const float *grid;          /* dev float[Q][9], 16-byte aligned: the (offset) grid the log p were evaluated on */
+    int64_t Q;                  /* >= 1 */
+    int32_t g;                  /* images, 1..65535 */
+    int32_t top_k;              /* k, 1..16 */
+    double separation_rad;      /* 0 < sep <= pi */
+    const float *gt;            /* dev float[g][n_gt][9] ground truths, or NULL (no spread) */
+    int32_t n_gt;               /* 1..128 with gt */
+    int64_t *index_out;         /* dev int64[g][k] */
+    float *logp_out;            /* dev float[g][k] */
+    float *mass_out;            /* dev float[g][k] */
+    float *log_norm_out;        /* dev float[g] */
+    float *spread_out;          /* dev float[g]; required with gt, ignored without */
+    /* dev scratch of at least rnf_grid_modes_workspace_bytes(this struct) bytes = g * min(ceil(Q / 2048), 2048) * 8 * (top_k + 2): the
+     * per-block partials of one pass (their count depends on Q alone) */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfGridModes;
+int rnf_grid_modes(const RnfGridModes *modes);
+/* The workspace rnf_grid_modes requires for the same struct (the workspace fields are not read); 0 when struct_bytes, g, Q or top_k are
+ * out of range. */
+size_t rnf_grid_modes_workspace_bytes(const RnfGridModes *modes);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

@@ -43,6 +43,14 @@ class FlowBackward(_Pass):
                 ("g_feature", C.c_void_p), ("layer_scratch", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class GridModes(_Pass):
+    """RnfGridModes (include/rnf_hip.h): top-k pose modes and their mass on an SO(3) grid."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("logp", C.c_void_p), ("grid", C.c_void_p), ("Q", C.c_int64), ("g", C.c_int32),
+                ("top_k", C.c_int32), ("separation_rad", C.c_double), ("gt", C.c_void_p), ("n_gt", C.c_int32), ("index_out", C.c_void_p),
+                ("logp_out", C.c_void_p), ("mass_out", C.c_void_p), ("log_norm_out", C.c_void_p), ("spread_out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 _SIGNATURES = {
     "rnf_abi_version": (C.c_int, []),
     "rnf_last_error": (C.c_char_p, []),
@@ -87,6 +95,8 @@ _SIGNATURES = {
     "rnf_fisher_log_prob": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_min_geodesic": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_void_p]),
     "rnf_so3_healpix_grid": (C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_void_p]),
+    "rnf_grid_modes": (C.c_int, [C.POINTER(GridModes)]),
+    "rnf_grid_modes_workspace_bytes": (C.c_size_t, [C.POINTER(GridModes)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_fisher_proper_svd": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_log_prob_backward": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_void_p]),

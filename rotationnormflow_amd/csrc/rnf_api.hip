@@ -21,6 +21,7 @@
 #include "layout.h"
 #include "equalize.h"
 #include "svd4_lapack.h"
+#include "grid_modes.h"
 
 using namespace rnf;
 
@@ -1877,6 +1878,61 @@ extern "C" int rnf_so3_healpix_grid(int32_t level, const float *offset, float *o
     if (blocks > (1LL << 20)) blocks = 1LL << 20;
     hipLaunchKernelGGL(so3_healpix_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (int)level, rows,
                        offset, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Top-k pose modes on the grid (csrc/grid_modes.h): k arg-max passes and one mass pass, each followed by its per-image finalise.
+static const char *grid_modes_check(const RnfGridModes *p) {
+    static thread_local char msg[256];
+    if (!p || p->struct_bytes != sizeof(RnfGridModes)) {
+        snprintf(msg, sizeof(msg), "RnfGridModes.struct_bytes does not match the library's %zu", sizeof(RnfGridModes));
+        return msg;
+    }
+    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridModes.g=%d outside 1..65535", p->g);
+    else if (p->Q < 1) snprintf(msg, sizeof(msg), "RnfGridModes.Q=%lld must be >= 1", (long long)p->Q);
+    else if (p->top_k < 1 || p->top_k > gm::MAX_K) snprintf(msg, sizeof(msg), "RnfGridModes.top_k=%d outside 1..%d", p->top_k, gm::MAX_K);
+    else return nullptr;
+    return msg;
+}
+
+extern "C" size_t rnf_grid_modes_workspace_bytes(const RnfGridModes *p) {
+    if (const char *e = grid_modes_check(p)) {
+        fail("%s", e);
+        return 0;
+    }
+    return (size_t)p->g * (size_t)gm::blocks_for(p->Q) * sizeof(double) * (size_t)(p->top_k + 2);
+}
+
+extern "C" int rnf_grid_modes(const RnfGridModes *p) {
+    if (const char *e = grid_modes_check(p)) return fail("%s", e);
+    if (!(p->separation_rad > 0.0 && p->separation_rad <= M_PI))
+        return fail("RnfGridModes.separation_rad=%g outside (0, pi]", p->separation_rad);
+    if (!p->logp || !p->grid || !p->index_out || !p->logp_out || !p->mass_out || !p->log_norm_out)
+        return fail("RnfGridModes: null logp, grid or output pointer");
+    if (reinterpret_cast<uintptr_t>(p->grid) % 16) return fail("RnfGridModes.grid must be 16-byte aligned");
+    if (p->gt && (p->n_gt < 1 || p->n_gt > gm::MAX_GT)) return fail("RnfGridModes.n_gt=%d outside 1..%d", p->n_gt, gm::MAX_GT);
+    if (p->gt && !p->spread_out) return fail("RnfGridModes.gt needs spread_out");
+    const size_t need = rnf_grid_modes_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfGridModes.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_modes_workspace_bytes)", p->workspace_bytes, need);
+    const float thr = p->separation_rad >= M_PI ? -INFINITY : (float)(1.0 + 2.0 * cos(p->separation_rad));
+    const int nb = (int)gm::blocks_for(p->Q), k = p->top_k;
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    for (int j = 0; j < k; ++j) {
+        hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nb, p->g), dim3(gm::THREADS), 0, s, p->logp, p->grid, (long long)p->Q, k, j, thr,
+                           (const long long *)p->index_out, (const float *)p->logp_out, (gm::ArgPart *)p->workspace);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)p->workspace, nb, k, j,
+                           (long long *)p->index_out, p->logp_out);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(gm::grid_modes_mass_kernel, dim3(nb, p->g), dim3(gm::THREADS), 0, s, p->logp, p->grid, (long long)p->Q, k, thr,
+                       p->gt, p->gt ? p->n_gt : 0, (const long long *)p->index_out, (const float *)p->logp_out, (double *)p->workspace);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gm::grid_modes_mass_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const double *)p->workspace, nb, (long long)p->Q,
+                       k, p->gt ? 1 : 0, (const long long *)p->index_out, (const float *)p->logp_out, p->mass_out, p->log_norm_out,
+                       p->spread_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

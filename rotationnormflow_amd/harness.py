@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import argparse
 import contextlib
+import ctypes as C
 import io
 import os
 
@@ -354,18 +355,8 @@ GRID_MAX_LAUNCH_ROWS = 1 << 24
 GRID_SIDE_LAUNCH_ROWS = 1 << 18
 
 
-def grid_estimate_rotations(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None,
-                            base=None, images_per_launch: int = None):
-    """Grid-search pose estimate of ``eval.py``'s ``log_pdf`` mode (eval.py:437-462): evaluate each image's log-density on the HEALPix grid
-    over SO(3) (``utils.sd``; level ``recursion_level``, or the one closest to ``number_queries``, default 500, in log space) multiplied on
-    the right by ``offset`` [3,3] (None: one Haar-uniform rotation drawn from torch's generator, as ``trans.random_rotation()``), and keep
-    the grid point of largest log p (``torch.argmax``: the first on a tie).
-
-    feature [B,F] (None for an unconditional flow: B = the base's rows, or 1).  ``base``: None (uniform) or a ``MatrixFisherN`` with one row
-    (shared by every image) or B rows (row b scores image b's grid; its log-constants are sliced, never recomputed on a slice).
-    ``images_per_launch``: images evaluated per launch (default: as many as fit in about 2^21 rotations; 1 for flows with batch-coupled
-    layers, whose matrices come from the first rows of a launch, as in the reference's per-image chunks).
-    Returns (est [B,3,3], max_log_prob [B], index [B] into the grid, offset [3,3])."""
+def _grid_inputs(flow: Flow, feature, number_queries, recursion_level, offset, base, who: str):
+    """The common arguments of the grid searches -> (feature or None, device, B images, level, offset [3,3], base A [1|B,3,3], c)."""
     from .utils import sd
     if not flow.condition:
         feature = None
@@ -385,51 +376,157 @@ def grid_estimate_rotations(flow: Flow, feature: torch.Tensor = None, number_que
         A = base.A.detach().reshape(-1, 3, 3).to(device=dev, dtype=torch.float32)
         c = base.log_const().reshape(-1).to(device=dev, dtype=torch.float32)
         if A.shape[0] not in (1, B):
-            raise ValueError(f"grid_estimate_rotations: the base has {A.shape[0]} rows for {B} images (1 or {B})")
+            raise ValueError(f"{who}: the base has {A.shape[0]} rows for {B} images (1 or {B})")
+    return feature, dev, B, level, offset, A, c
+
+
+def _grid_launches(flow: Flow, feature, grid, B, A, c, images_per_launch, who: str):
+    """Evaluate B images' log-density on ``grid`` [Q,3,3] in launches of about GRID_LAUNCH_ROWS shared-row rotations (call under no_grad).
+    Yields (b0, b1, lo, logp [b1 - b0, rows]) per launch: images b0..b1-1 on grid rows lo..lo+rows-1 -- whole images (lo = 0, rows = Q)
+    when several share a launch, consecutive chunks of one image otherwise."""
+    Q = grid.shape[0]
     coupled = any(getattr(m, "_rnf_batch_coupled", False) for m in flow.modules())
+    packed = flow._packed(grid.device, feature)
+    budget = GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_LAUNCH_ROWS
+    if images_per_launch is None:
+        images_per_launch = 1 if coupled else max(1, budget // Q)
+    g = min(int(images_per_launch), B)
+    if g < 1 or (coupled and g > 1):
+        raise ValueError(f"{who}: images_per_launch={images_per_launch}" + (" (batch-coupled layers: 1)" if coupled else ""))
+    if g > 1 and g * Q > GRID_MAX_LAUNCH_ROWS:
+        raise ValueError(f"{who}: {g} images of {Q} rotations exceed {GRID_MAX_LAUNCH_ROWS} rotations per launch")
+    chunk = Q if g > 1 else min(Q, GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_MAX_LAUNCH_ROWS)
+
+    def log_prob(rot, b0, b1):
+        feat = feature[b0:b1] if feature is not None else None
+        rows = (A, c) if A is None or A.shape[0] == 1 else (A[b0:b1], c[b0:b1])
+        return runtime.run_log_prob(flow, packed, rot, feat, *rows, feature_repeat=rot.shape[0] // (b1 - b0))["logp"]
+
+    rep = grid.repeat(g, 1, 1) if g > 1 else grid          # one image per launch: the grid itself, no copy
+    for b0 in range(0, B, g):
+        b1 = min(B, b0 + g)
+        if g > 1:
+            yield b0, b1, 0, log_prob(rep[:(b1 - b0) * Q], b0, b1).reshape(b1 - b0, Q)
+            continue
+        for lo in range(0, Q, chunk):
+            yield b0, b1, lo, log_prob(grid[lo:lo + chunk], b0, b1).reshape(1, -1)
+
+
+def grid_estimate_rotations(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None,
+                            base=None, images_per_launch: int = None):
+    """Grid-search pose estimate of ``eval.py``'s ``log_pdf`` mode (eval.py:437-462): evaluate each image's log-density on the HEALPix grid
+    over SO(3) (``utils.sd``; level ``recursion_level``, or the one closest to ``number_queries``, default 500, in log space) multiplied on
+    the right by ``offset`` [3,3] (None: one Haar-uniform rotation drawn from torch's generator, as ``trans.random_rotation()``), and keep
+    the grid point of largest log p (``torch.argmax``: the first on a tie).
+
+    feature [B,F] (None for an unconditional flow: B = the base's rows, or 1).  ``base``: None (uniform) or a ``MatrixFisherN`` with one row
+    (shared by every image) or B rows (row b scores image b's grid; its log-constants are sliced, never recomputed on a slice).
+    ``images_per_launch``: images evaluated per launch (default: as many as fit in about 2^21 rotations; 1 for flows with batch-coupled
+    layers, whose matrices come from the first rows of a launch, as in the reference's per-image chunks).
+    Returns (est [B,3,3], max_log_prob [B], index [B] into the grid, offset [3,3])."""
+    from .utils import sd
+    feature, dev, B, level, offset, A, c = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base,
+                                                        "grid_estimate_rotations")
     with torch.no_grad():
         grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
-        Q = grid.shape[0]
-        packed = flow._packed(dev, feature)
-        budget = GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_LAUNCH_ROWS
-        if images_per_launch is None:
-            images_per_launch = 1 if coupled else max(1, budget // Q)
-        g = min(int(images_per_launch), B)
-        if g < 1 or (coupled and g > 1):
-            raise ValueError(f"grid_estimate_rotations: images_per_launch={images_per_launch}" + (" (batch-coupled layers: 1)" if coupled else ""))
-        if g > 1 and g * Q > GRID_MAX_LAUNCH_ROWS:
-            raise ValueError(f"grid_estimate_rotations: {g} images of {Q} rotations exceed {GRID_MAX_LAUNCH_ROWS} rotations per launch")
-        chunk = Q if g > 1 else min(Q, GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_MAX_LAUNCH_ROWS)
-
-        def log_prob(rot, b0, b1):
-            feat = feature[b0:b1] if feature is not None else None
-            rows = (A, c) if A is None or A.shape[0] == 1 else (A[b0:b1], c[b0:b1])
-            return runtime.run_log_prob(flow, packed, rot, feat, *rows, feature_repeat=rot.shape[0] // (b1 - b0))["logp"]
-
         bests, indices = [], []
-        rep = grid.repeat(g, 1, 1) if g > 1 else grid          # one image per launch: the grid itself, no copy
-        for b0 in range(0, B, g):
-            b1 = min(B, b0 + g)
-            if g > 1:
-                lp = log_prob(rep[:(b1 - b0) * Q], b0, b1).reshape(b1 - b0, Q)
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, "grid_estimate_rotations"):
+            if b1 - b0 > 1:
                 idx = torch.argmax(lp, dim=-1)
                 bests.append(lp.gather(1, idx[:, None])[:, 0])
                 indices.append(idx)
                 continue
-            for lo in range(0, Q, chunk):                       # the first chunk's maximum wins a tie, a NaN wins as in torch.argmax
-                lp = log_prob(grid[lo:lo + chunk], b0, b1)
-                idx = torch.argmax(lp)
-                val = lp[idx]
-                if lo == 0:
-                    v, i = val, idx
-                else:
-                    take = (val > v) | (val.isnan() & ~v.isnan())
-                    v, i = torch.where(take, val, v), torch.where(take, idx + lo, i)
-            bests.append(v.reshape(1))
-            indices.append(i.reshape(1))
+            lp = lp[0]                                          # the first chunk's maximum wins a tie, a NaN wins as in torch.argmax
+            idx = torch.argmax(lp)
+            val = lp[idx]
+            if lo == 0:
+                v, i = val, idx
+            else:
+                take = (val > v) | (val.isnan() & ~v.isnan())
+                v, i = torch.where(take, val, v), torch.where(take, idx + lo, i)
+            if lo + lp.shape[0] == grid.shape[0]:
+                bests.append(v.reshape(1))
+                indices.append(i.reshape(1))
         best, index = (bests[0], indices[0]) if len(bests) == 1 else (torch.cat(bests), torch.cat(indices))
         est = grid[index]
     return est, best, index, offset
+
+
+def grid_modes(logp: torch.Tensor, grid: torch.Tensor, top_k: int, separation_rad: float, gt: torch.Tensor = None):
+    """``rnf_grid_modes`` on g images' log-densities ``logp`` [g,Q] (float32, on the device) over ``grid`` [Q,3,3]: the top-k modes
+    separated by ``separation_rad`` and the mass each carries (include/rnf_hip.h).  ``gt``: None or [g,K,3,3] ground truths for the spread.
+    -> (index [g,k] int64, log_prob [g,k], mass [g,k], log_norm [g], spread [g] in radians or None)"""
+    from . import _lib
+    g, Q = logp.shape
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    grid = grid.reshape(Q, 9).to(torch.float32).contiguous()
+    gt = None if gt is None else gt.reshape(g, -1, 9).to(device=dev, dtype=torch.float32).contiguous()
+    index = torch.empty(g, top_k, dtype=torch.int64, device=dev)
+    log_prob = torch.empty(g, top_k, dtype=torch.float32, device=dev)
+    mass = torch.empty(g, top_k, dtype=torch.float32, device=dev)
+    log_norm = torch.empty(g, dtype=torch.float32, device=dev)
+    spread = torch.empty(g, dtype=torch.float32, device=dev) if gt is not None else None
+    args = _lib.GridModes(logp=lp.data_ptr(), grid=grid.data_ptr(), Q=Q, g=g, top_k=int(top_k), separation_rad=float(separation_rad),
+                          gt=gt.data_ptr() if gt is not None else None, n_gt=gt.shape[1] if gt is not None else 0,
+                          index_out=index.data_ptr(), logp_out=log_prob.data_ptr(), mass_out=mass.data_ptr(),
+                          log_norm_out=log_norm.data_ptr(), spread_out=spread.data_ptr() if spread is not None else None)
+    L = _lib.lib()
+    need = L.rnf_grid_modes_workspace_bytes(C.byref(args))
+    if need == 0:
+        _lib.check(1)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.rnf_grid_modes(C.byref(args)))
+    return index, log_prob, mass, log_norm, spread
+
+
+def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, separation_deg: float = 15.0, number_queries: int = None,
+                    recursion_level: int = None, offset=None, base=None, gt_rotation=None, images_per_launch: int = None) -> dict:
+    """The ``top_k`` pose modes of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches), at least
+    ``separation_deg`` apart, with the probability mass of each.  Grid cells have equal Haar volume and the flow's density is relative to the
+    normalised Haar measure, so exp(log p_i) / Q is cell i's mass; ``log_norm`` = log(sum_i exp(log p_i) / Q) tends to 0 as the grid level
+    grows.  Mode 0 is ``grid_estimate_rotations``'s estimate; mode j the first arg-max among the points at least ``separation_deg`` from
+    modes 0..j-1, its mass that of the points within ``separation_deg`` of it and of no earlier mode (``rnf_grid_modes``,
+    include/rnf_hip.h).  Modes that do not exist have index -1, log p -inf, mass 0 and NaN rotations.  ``gt_rotation`` [B,K,3,3] or
+    [B,3,3] adds IPDF's spread: the expected angle (degrees) to the closest ground truth under the grid-normalised mass.
+    An image whose grid is evaluated in chunks (more than 2^24 rows, level >= 6; 2^18 with side layers) has its chunks gathered into one
+    [Q] float32 buffer (4 bytes per grid row) before the reduction.
+    -> dict(est [B,k,3,3], log_prob [B,k], index [B,k] int64, mass [B,k], log_norm [B], spread_deg [B] (with gt_rotation), offset [3,3])"""
+    from .utils import sd
+    if not 1 <= int(top_k) <= 16:
+        raise ValueError(f"grid_pose_modes: top_k={top_k} outside 1..16")
+    if not 0.0 < float(separation_deg) <= 180.0:
+        raise ValueError(f"grid_pose_modes: separation_deg={separation_deg} outside (0, 180]")
+    k, sep = int(top_k), float(np.deg2rad(np.float64(separation_deg)))
+    feature, dev, B, level, offset, A, c = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_pose_modes")
+    gt = None
+    if gt_rotation is not None:
+        gt = gt_rotation.reshape(B, -1, 3, 3).to(device=dev, dtype=torch.float32)
+        if gt.shape[1] > 128:
+            raise ValueError(f"grid_pose_modes: {gt.shape[1]} ground truths per image (at most 128)")
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        Q = grid.shape[0]
+        outs, whole = [], None
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, "grid_pose_modes"):
+            if lp.shape[1] < Q:                                 # one image in chunks: gather them first
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            outs.append(grid_modes(lp, grid, k, sep, gt[b0:b1] if gt is not None else None))
+        index, log_prob, mass, log_norm, spread = (torch.cat(t) if t[0] is not None else None for t in zip(*outs))
+        est = grid[index.clamp(min=0)]
+        est[index < 0] = float("nan")
+    out = dict(est=est, log_prob=log_prob, index=index, mass=mass, log_norm=log_norm, offset=offset)
+    if gt is not None:
+        out["spread_deg"] = torch.rad2deg(spread)
+    return out
 
 
 def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
@@ -490,25 +587,52 @@ def min_geodesic_distance(est_rotation: torch.Tensor, gt_rotation: torch.Tensor)
 
 
 def pose_accuracy(flow: Flow, feature, gt_rotation, queries=None, base=None, number_queries: int = 500, thresholds_deg=(15.0, 30.0),
-                  method: str = "log_inv", recursion_level: int = None, offset=None, refine_steps: int = 100):
+                  method: str = "log_inv", recursion_level: int = None, offset=None, refine_steps: int = 100, top_k: int = 1,
+                  separation_deg: float = 15.0):
     """What ``Agent.eval_acc`` + ``eval.py`` report per batch (agent.py:238-283, utils/utils.py:208-209): arg-max pose estimate, geodesic
     error in degrees against the (possibly several) ground truths, accuracy at the thresholds.  -> dict(err_deg, est_rotation, acc)
 
     ``method`` (eval.py:36-44): "log_inv" (default) pushes base samples through the inverse (``estimate_rotations``); "log_pdf" is the
     grid search (``grid_estimate_rotations`` with ``number_queries`` / ``recursion_level`` / ``offset`` / ``base``); "nll_grad" refines the
-    grid estimate with ``refine_steps`` gradient steps at lr 1e-4 without a base term (eval.py:464-480)."""
+    grid estimate with ``refine_steps`` gradient steps at lr 1e-4 without a base term (eval.py:464-480).
+
+    ``top_k`` > 1 (grid methods only; the commented-out ``for top_k in [1, 2, 4]`` of eval.py:243,297,406): the estimates are the modes of
+    ``grid_pose_modes`` (``separation_deg`` apart; "nll_grad" refines every valid one, each with its image's feature row), ``est_rotation``
+    is [B,k,3,3] (NaN for a missing mode) and an image's error is the smallest over its valid modes (best of k)."""
+    if method not in ("log_inv", "log_pdf", "nll_grad"):
+        raise ValueError(f"pose_accuracy: method must be 'log_inv', 'log_pdf' or 'nll_grad', got {method!r}")
+    if int(top_k) < 1 or (int(top_k) > 1 and method == "log_inv"):
+        raise ValueError(f"pose_accuracy: top_k={top_k} needs a grid method (log_inv's samples are not equivolumetric and carry no mass)")
+    if top_k > 1:
+        return _pose_accuracy_top_k(flow, feature, gt_rotation, base, number_queries, thresholds_deg, method, recursion_level, offset,
+                                    refine_steps, int(top_k), separation_deg)
     if method == "log_inv":
         est, _ = estimate_rotations(flow, feature, queries=queries, base=base, number_queries=number_queries)
-    elif method in ("log_pdf", "nll_grad"):
+    else:
         est = grid_estimate_rotations(flow, feature, number_queries=number_queries, recursion_level=recursion_level, offset=offset,
                                       base=base)[0]
         if method == "nll_grad":
             est = refine_rotations(flow, feature, est, steps=refine_steps, lr=1e-4, base=None)
-    else:
-        raise ValueError(f"pose_accuracy: method must be 'log_inv', 'log_pdf' or 'nll_grad', got {method!r}")
     err_deg = torch.rad2deg(min_geodesic_distance(est, gt_rotation))
     return dict(err_deg=err_deg, est_rotation=est, acc={t: float((err_deg <= t).float().mean()) for t in thresholds_deg})
 
+
+def _pose_accuracy_top_k(flow, feature, gt_rotation, base, number_queries, thresholds_deg, method, recursion_level, offset, refine_steps,
+                         k, separation_deg):
+    modes = grid_pose_modes(flow, feature, top_k=k, separation_deg=separation_deg, number_queries=number_queries,
+                            recursion_level=recursion_level, offset=offset, base=base)
+    est, valid = modes["est"], modes["index"] >= 0
+    B = est.shape[0]
+    if method == "nll_grad":
+        flat, ok = est.reshape(B * k, 3, 3).clone(), valid.reshape(-1)
+        feat = feature if feature is not None and flow.condition else None
+        rows = feat.repeat_interleave(k, 0)[ok] if feat is not None else None
+        flat[ok] = refine_rotations(flow, rows, flat[ok], steps=refine_steps, lr=1e-4, base=None)
+        est = flat.reshape(B, k, 3, 3)
+    gt = gt_rotation.reshape(B, -1, 3, 3).to(device=est.device)
+    err = min_geodesic_distance(est.reshape(B * k, 3, 3), gt.repeat_interleave(k, 0)).reshape(B, k)
+    err_deg = torch.rad2deg(torch.where(valid, err, torch.full_like(err, float("inf"))).min(-1).values)
+    return dict(err_deg=err_deg, est_rotation=est, acc={t: float((err_deg <= t).float().mean()) for t in thresholds_deg})
 
 if __name__ == "__main__":
     main()
