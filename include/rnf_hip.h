@@ -366,6 +366,49 @@ int rnf_min_geodesic(const float *est_dev, const float *gt_dev, int64_t n, int32
  * float[9]) or the identity when NULL.  fp64 inside, one rounding to fp32 per entry.  level 0..8 (level 8: 1.2e9 rows, 43 GB). */
 int rnf_so3_healpix_grid(int32_t level, const float *offset9_dev, float *out_dev, void *stream);
 
+/* The grid's hierarchy, for the coarse-to-fine beam search.  The children of level-l row r = t * npix + p (nside = 2^l) are the 12
+ * level-(l + 1) rows with pixel ring(4 nest(p) + c), c = 0..3 (ring2nest / nest2ring of Gorski et al. 2005 at nside and 2 nside: the four
+ * NESTED sub-pixels) and tilt 2t - 1, 2t, 2t + 1 modulo 6 * 2^(l + 1); child j = 4 k + c has tilt 2t - 1 + k.  The children of all level-l
+ * rows cover every level-(l + 1) row (the odd tilts are shared by neighbouring parents, so some rows are children of several).
+ * rows_out[q][j] = child j of parents[q] as a level-(l + 1) row (-1 for a parent outside 0..72 * 8^l - 1, e.g. the -1 padding of
+ * rnf_grid_beam_select); rot_out[q][j] (optional) = its rotation, bit-identical to the row rnf_so3_healpix_grid(l + 1, offset) writes
+ * (one shared row function; the rotation of row 0 for a child -1). */
+typedef struct RnfGridChildren {
+    size_t struct_bytes;        /* sizeof(RnfGridChildren); any other value is refused */
+    int32_t level;              /* the parents' level l, 0..7 */
+    const int64_t *parents;     /* dev int64[n]: g images * m parent rows each */
+    int64_t n;                  /* 0..2^36 */
+    const float *offset;        /* dev float[9] row-major, or NULL (identity) */
+    int64_t *rows_out;          /* dev int64[n][12] */
+    float *rot_out;             /* dev float[n][12][9], or NULL */
+    void *stream;
+} RnfGridChildren;
+int rnf_so3_grid_children(const RnfGridChildren *children);
+
+/* Beam selection per image: of its M candidates (log p, row), the `beam` best DISTINCT rows, ordered by log p descending (a NaN first, as
+ * torch.argmax; -0 and +0 tie) and then row ascending; a row duplicated among the candidates counts once, with its best candidate.  Past
+ * the distinct rows: row -1, log p -inf.  logp_out holds the candidate's value (a NaN as the canonical quiet NaN, -0 as +0).  A candidate
+ * whose row is < 0 or > 2^31 - 2 is ignored.  Deterministic: no atomics, passes and block counts depend on (M, beam) alone, so results
+ * are bit-identical from run to run and whatever g. */
+typedef struct RnfGridBeamSelect {
+    size_t struct_bytes;        /* sizeof(RnfGridBeamSelect); any other value is refused */
+    const float *logp;          /* dev float[g][M] */
+    const int64_t *rows;        /* dev int64[g][M] the candidates' rows, or NULL: candidate i is row i (distinct, no deduplication) */
+    int64_t M;                  /* candidates per image, 1..2^31 - 1 */
+    int32_t g;                  /* images, 1..65535 */
+    int32_t beam;               /* 1..1024 */
+    int64_t *rows_out;          /* dev int64[g][beam] */
+    float *logp_out;            /* dev float[g][beam] */
+    /* dev scratch of at least rnf_grid_beam_select_workspace_bytes(this struct) bytes = 2 g ceil(M / 4096) beam 8 (8 when M <= 4096) */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfGridBeamSelect;
+int rnf_grid_beam_select(const RnfGridBeamSelect *select);
+/* The workspace rnf_grid_beam_select requires for the same struct (the workspace fields are not read); 0 when struct_bytes, g, M or beam
+ * are out of range. */
+size_t rnf_grid_beam_select_workspace_bytes(const RnfGridBeamSelect *select);
+
 /* Top-k pose modes of g images evaluated on one grid of the search above, with the probability mass each carries: the commented-out
  * `for top_k in [1, 2, 4]` of eval.py:243,297,406 and the spread of IPDF (Murphy et al. 2021, the expected angular error under the
  * predicted distribution).  Every grid cell has the same Haar volume and the flow densities are relative to the normalised Haar measure,

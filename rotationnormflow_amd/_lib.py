@@ -51,6 +51,19 @@ class GridModes(_Pass):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class GridChildren(_Pass):
+    """RnfGridChildren (include/rnf_hip.h): the 12 children of SO(3) grid rows one level down, and their rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("parents", C.c_void_p), ("n", C.c_int64), ("offset", C.c_void_p),
+                ("rows_out", C.c_void_p), ("rot_out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class GridBeamSelect(_Pass):
+    """RnfGridBeamSelect (include/rnf_hip.h): the best distinct rows per image of the beam search."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("logp", C.c_void_p), ("rows", C.c_void_p), ("M", C.c_int64), ("g", C.c_int32),
+                ("beam", C.c_int32), ("rows_out", C.c_void_p), ("logp_out", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 _SIGNATURES = {
     "rnf_abi_version": (C.c_int, []),
     "rnf_last_error": (C.c_char_p, []),
@@ -97,6 +110,9 @@ _SIGNATURES = {
     "rnf_so3_healpix_grid": (C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "rnf_grid_modes": (C.c_int, [C.POINTER(GridModes)]),
     "rnf_grid_modes_workspace_bytes": (C.c_size_t, [C.POINTER(GridModes)]),
+    "rnf_so3_grid_children": (C.c_int, [C.POINTER(GridChildren)]),
+    "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
+    "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_fisher_proper_svd": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_log_prob_backward": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -22,6 +22,8 @@
 #include "equalize.h"
 #include "svd4_lapack.h"
 #include "grid_modes.h"
+#include "so3_grid.h"
+#include "grid_beam.h"
 
 using namespace rnf;
 
@@ -1816,70 +1818,83 @@ extern "C" int rnf_min_geodesic(const float *est, const float *gt, int64_t n, in
     return 0;
 }
 
-// Equivolumetric SO(3) grid of the grid-search pose estimate (utils/sd.py:47-82 generate_healpix_grid, offset on the right as eval.py:440-442
-// `grid @ random_rot`): row r = t * npix + p is Rx(phi_p) Rz(theta_p) Rx(tau_t) O, with (cos theta_p, phi_p) the centre of HEALPix pixel p
-// in the RING ordering for nside = 2^level (Gorski et al. 2005, pix2ang_ring), tau_t = 2 pi t / (6 * 2^level) (np.linspace(..., endpoint=
-// False)), Rx / Rz active rotations (scipy's from_euler("X" / "Z")).  fp64 throughout, one rounding per entry at the store.
-__device__ inline long long isqrt_ll(long long v) {
-    long long s = (long long)sqrt((double)v);
-    while (s * s > v) --s;
-    while ((s + 1) * (s + 1) <= v) ++s;
-    return s;
-}
-
-__global__ void so3_healpix_grid_kernel(int level, long long rows, const float *offset, float *out) {
-    const long long nside = 1LL << level, npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1);
-    const double pi = M_PI, tilt_step = 2.0 * M_PI / (double)(6LL << level);
-    double o[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (offset)
-        for (int c = 0; c < 9; ++c) o[c] = (double)offset[c];
-    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
-        const long long t = r / npix, p = r - t * npix;
-        double z, sth, phi;                                      // cos / sin of the polar angle, azimuth
-        if (p < ncap) {                                          // north polar cap: ring i holds 4 i pixels
-            const long long i = (1 + isqrt_ll(1 + 2 * p)) >> 1, j = p + 1 - 2 * i * (i - 1);
-            const double tmp = (double)(i * i) / (double)(3 * nside * nside);
-            z = 1.0 - tmp;
-            sth = sqrt(tmp * (2.0 - tmp));
-            phi = ((double)j - 0.5) * pi / (double)(2 * i);
-        } else if (p < npix - ncap) {                            // belt: 2 nside + 1 rings of 4 nside pixels
-            const long long q = p - ncap, i = q / (4 * nside) + nside, j = q % (4 * nside) + 1;
-            const double f = ((i + nside) & 1) ? 1.0 : 0.5;
-            z = (double)(2 * nside - i) * 2.0 / (double)(3 * nside);
-            sth = sqrt((1.0 - z) * (1.0 + z));
-            phi = ((double)j - f) * pi / (double)(2 * nside);
-        } else {                                                 // south polar cap, mirrored
-            const long long q = npix - p, i = (1 + isqrt_ll(2 * q - 1)) >> 1, j = 4 * i + 1 - (q - 2 * i * (i - 1));
-            const double tmp = (double)(i * i) / (double)(3 * nside * nside);
-            z = tmp - 1.0;
-            sth = sqrt(tmp * (2.0 - tmp));
-            phi = ((double)j - 0.5) * pi / (double)(2 * i);
-        }
-        double sphi, cphi, stau, ctau;
-        sincos(phi, &sphi, &cphi);
-        sincos((double)t * tilt_step, &stau, &ctau);
-        // Rx(phi) Rz(theta): columns (cos t, cphi sin t, sphi sin t), (-sin t, cphi cos t, sphi cos t), (0, -sphi, cphi); then Rx(tau)
-        // mixes the last two columns
-        const double a[9] = {z, -sth * ctau, sth * stau,
-                             cphi * sth, cphi * z * ctau - sphi * stau, -cphi * z * stau - sphi * ctau,
-                             sphi * sth, sphi * z * ctau + cphi * stau, -sphi * z * stau + cphi * ctau};
-        float *dst = out + r * 9;
-        for (int row = 0; row < 3; ++row)
-            for (int col = 0; col < 3; ++col)
-                dst[row * 3 + col] = (float)(a[row * 3] * o[col] + a[row * 3 + 1] * o[3 + col] + a[row * 3 + 2] * o[6 + col]);
-    }
-}
-
+// Equivolumetric SO(3) grid of the grid-search pose estimate and its hierarchy: csrc/so3_grid.h.
 extern "C" int rnf_so3_healpix_grid(int32_t level, const float *offset, float *out, void *stream) {
     if (level < 0 || level > 8) return fail("rnf_so3_healpix_grid: level=%d outside 0..8 (72 * 8^level rotations)", level);
     if (!out) return fail("rnf_so3_healpix_grid: null output pointer");
     const long long rows = 72LL << (3 * level);
     long long blocks = (rows + 255) / 256;
     if (blocks > (1LL << 20)) blocks = 1LL << 20;
-    hipLaunchKernelGGL(so3_healpix_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (int)level, rows,
+    hipLaunchKernelGGL(so3g::so3_healpix_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (int)level, rows,
                        offset, out);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" int rnf_so3_grid_children(const RnfGridChildren *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridChildren))
+        return fail("RnfGridChildren.struct_bytes does not match the library's %zu", sizeof(RnfGridChildren));
+    if (p->level < 0 || p->level >= so3g::MAX_LEVEL)
+        return fail("RnfGridChildren.level=%d outside 0..%d (children at level + 1 <= %d)", p->level, so3g::MAX_LEVEL - 1, so3g::MAX_LEVEL);
+    if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridChildren.n=%lld outside 0..2^36", (long long)p->n);
+    if (p->n == 0) return 0;
+    if (!p->parents || !p->rows_out) return fail("RnfGridChildren: null parents or rows_out");
+    const long long total = p->n * 12;
+    long long blocks = (total + 255) / 256;
+    if (blocks > (1LL << 20)) blocks = 1LL << 20;
+    hipLaunchKernelGGL(so3g::so3_grid_children_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(p->stream),
+                       (int)p->level, (long long)p->n, (const long long *)p->parents, p->offset, (long long *)p->rows_out, p->rot_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Beam selection (csrc/grid_beam.h): passes of one-chunk-per-block sorts until one chunk per image remains.
+static const char *grid_beam_check(const RnfGridBeamSelect *p) {
+    static thread_local char msg[256];
+    if (!p || p->struct_bytes != sizeof(RnfGridBeamSelect)) {
+        snprintf(msg, sizeof(msg), "RnfGridBeamSelect.struct_bytes does not match the library's %zu", sizeof(RnfGridBeamSelect));
+        return msg;
+    }
+    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.g=%d outside 1..65535", p->g);
+    else if (p->M < 1 || p->M > gb::ROW_MAX + 1) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.M=%lld outside 1..2^31 - 1", (long long)p->M);
+    else if (p->beam < 1 || p->beam > gb::MAX_BEAM) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.beam=%d outside 1..%d", p->beam, gb::MAX_BEAM);
+    else return nullptr;
+    return msg;
+}
+
+extern "C" size_t rnf_grid_beam_select_workspace_bytes(const RnfGridBeamSelect *p) {
+    if (const char *e = grid_beam_check(p)) {
+        fail("%s", e);
+        return 0;
+    }
+    const long long nb = gb::blocks_for(p->M);
+    // two ping-pong buffers of the first pass's keys; 8 bytes when a single pass suffices (never 0, which means an error)
+    return nb > 1 ? 2 * (size_t)p->g * (size_t)nb * (size_t)p->beam * sizeof(unsigned long long) : 8;
+}
+
+extern "C" int rnf_grid_beam_select(const RnfGridBeamSelect *p) {
+    if (const char *e = grid_beam_check(p)) return fail("%s", e);
+    if (!p->logp || !p->rows_out || !p->logp_out) return fail("RnfGridBeamSelect: null logp or output pointer");
+    const size_t need = rnf_grid_beam_select_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfGridBeamSelect.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_beam_select_workspace_bytes)",
+                    p->workspace_bytes, need);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    const int dedup = p->rows != nullptr;
+    unsigned long long *ws = (unsigned long long *)p->workspace;
+    unsigned long long *half = ws + (size_t)p->g * (size_t)gb::blocks_for(p->M) * (size_t)p->beam;
+    const unsigned long long *in = nullptr;
+    long long n = p->M;
+    for (int pass = 0;; ++pass) {
+        const long long nb = gb::blocks_for(n);
+        unsigned long long *out = nb > 1 ? (pass & 1 ? half : ws) : nullptr;
+        hipLaunchKernelGGL(gb::beam_select_kernel, dim3((unsigned)nb, (unsigned)p->g), dim3(gb::THREADS), 0, s, p->logp,
+                           (const long long *)p->rows, in, n, dedup, (int)p->beam, out, (long long *)p->rows_out, p->logp_out);
+        HIP_TRY(hipGetLastError());
+        if (nb == 1) return 0;
+        in = out;
+        n = nb * p->beam;
+    }
 }
 
 // Top-k pose modes on the grid (csrc/grid_modes.h): k arg-max passes and one mass pass, each followed by its per-image finalise.

@@ -529,6 +529,133 @@ def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, se
     return out
 
 
+def grid_children(parents: torch.Tensor, level: int, offset=None, rotations: bool = True):
+    """``rnf_so3_grid_children``: the 12 level-(``level`` + 1) children of each level-``level`` grid row in ``parents`` [..., m] (int64, on
+    the device; a row outside the level, e.g. -1, has children -1) -> (rows [..., m * 12] int64, rotations [..., m * 12, 3, 3] or None).
+    The rotations are bit-identical to the rows of ``utils.sd.generate_healpix_grid(level + 1, offset=offset)`` (include/rnf_hip.h)."""
+    from . import _lib
+    dev = parents.device
+    par = parents.to(torch.int64).contiguous()
+    shape = par.shape[:-1] + (par.shape[-1] * 12,)
+    rows = torch.empty(shape, dtype=torch.int64, device=dev)
+    rot = torch.empty(shape + (3, 3), dtype=torch.float32, device=dev) if rotations else None
+    off = offset.reshape(9).to(device=dev, dtype=torch.float32).contiguous() if offset is not None else None
+    with torch.cuda.device(dev):
+        args = _lib.GridChildren(level=int(level), parents=par.data_ptr(), n=par.numel(), offset=off.data_ptr() if off is not None else None,
+                                 rows_out=rows.data_ptr(), rot_out=rot.data_ptr() if rot is not None else None,
+                                 stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().rnf_so3_grid_children(C.byref(args)))
+    return rows, rot
+
+
+def grid_beam_select(logp: torch.Tensor, beam: int, rows: torch.Tensor = None):
+    """``rnf_grid_beam_select``: per image (row of ``logp`` [g,M], float32 on the device), the ``beam`` best distinct candidate rows --
+    log p descending (a NaN first), then row ascending; ``rows`` [g,M] int64 the candidates' grid rows (None: candidate i is row i; a row
+    < 0 is no candidate).  Past the distinct rows: row -1, log p -inf.  -> (rows [g,beam] int64, log_prob [g,beam])"""
+    from . import _lib
+    g, M = logp.shape
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    rw = rows.reshape(g, M).to(torch.int64).contiguous() if rows is not None else None
+    rows_out = torch.empty(g, int(beam), dtype=torch.int64, device=dev)
+    logp_out = torch.empty(g, int(beam), dtype=torch.float32, device=dev)
+    args = _lib.GridBeamSelect(logp=lp.data_ptr(), rows=rw.data_ptr() if rw is not None else None, M=M, g=g, beam=int(beam),
+                               rows_out=rows_out.data_ptr(), logp_out=logp_out.data_ptr())
+    L = _lib.lib()
+    need = L.rnf_grid_beam_select_workspace_bytes(C.byref(args))
+    if need == 0:
+        _lib.check(1)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.rnf_grid_beam_select(C.byref(args)))
+    return rows_out, logp_out
+
+
+GRID_BEAM_MAX = 1024
+GRID_BEAM_MAX_START = 4
+
+
+def grid_beam_estimate_rotations(flow: Flow, feature: torch.Tensor = None, recursion_level: int = 5, start_level: int = 2, beam: int = 16,
+                                 offset=None, base=None, images_per_launch: int = None):
+    """Coarse-to-fine beam search for ``grid_estimate_rotations``'s estimate at level ``recursion_level``: evaluate the whole level
+    ``start_level`` grid, keep each image's ``beam`` best distinct rows (``rnf_grid_beam_select``), then at every level up to
+    ``recursion_level`` evaluate the 12 children of each kept row (``rnf_so3_grid_children``: the four NESTED sub-pixels times the tilts
+    2t - 1, 2t, 2t + 1) and select again; the last level keeps the best row.  Every evaluated row is a row of the full level-L grid (same
+    rotation bits, same log p), so ``index`` is in the full grid's row order and, when the beams cover every row, the result is
+    ``grid_estimate_rotations(recursion_level=L)``'s.  About beam * 12 * (L - start_level) rows per image instead of 72 * 8^L.
+    No host synchronisation between levels.
+
+    Inputs as ``grid_estimate_rotations`` (feature [B,F] or None, ``offset``, ``base`` with 1 or B rows); ``images_per_launch`` groups the
+    start level as there and the refinement launches up to about 2^21 rows (beam * 12 per image).  Limits (ValueError before any launch):
+    0 <= start_level <= min(recursion_level, 4), recursion_level <= 8, 1 <= beam <= 1024; flows with batch-coupled layers are refused
+    (their matrices come from a launch's first rows, so a candidate set would change the density).  start_level == recursion_level is
+    ``grid_estimate_rotations`` itself.  Returns (est [B,3,3], max_log_prob [B], index [B] into the level-L grid, offset [3,3])."""
+    from .utils import sd
+    who = "grid_beam_estimate_rotations"
+    L, S, beam = int(recursion_level), int(start_level), int(beam)
+    if not 0 <= L <= sd.MAX_LEVEL:
+        raise ValueError(f"{who}: recursion_level={recursion_level} outside 0..{sd.MAX_LEVEL}")
+    if not 0 <= S <= min(L, GRID_BEAM_MAX_START):
+        raise ValueError(f"{who}: start_level={start_level} outside 0..min(recursion_level, {GRID_BEAM_MAX_START})")
+    if not 1 <= beam <= GRID_BEAM_MAX:
+        raise ValueError(f"{who}: beam={beam} outside 1..{GRID_BEAM_MAX}")
+    if images_per_launch is not None and int(images_per_launch) < 1:
+        raise ValueError(f"{who}: images_per_launch={images_per_launch}")
+    coupled = sorted({type(m).__name__ for m in flow.modules() if getattr(m, "_rnf_batch_coupled", False)})
+    if coupled:
+        raise ValueError(f"{who}: batch-coupled layers ({', '.join(coupled)}) take their matrices from a launch's first rows; "
+                         "use grid_estimate_rotations")
+    if S == L:
+        return grid_estimate_rotations(flow, feature, recursion_level=L, offset=offset, base=base, images_per_launch=images_per_launch)
+    feature, dev, B, _, offset, A, c = _grid_inputs(flow, feature, None, L, offset, base, who)
+    with torch.no_grad():
+        # the start level: the whole grid, in grid_estimate_rotations' launches; an image evaluated in chunks is gathered first
+        grid = sd.generate_healpix_grid(S, device=dev, offset=offset)
+        Q = grid.shape[0]
+        kept = torch.empty(B, beam, dtype=torch.int64, device=dev)
+        whole = None
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, who):
+            if lp.shape[1] < Q:
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            kept[b0:b1] = grid_beam_select(lp, beam)[0]
+        del grid, whole
+        # the refinement levels: each image's beam * 12 children in one shared-row launch group of about 2^21 rows
+        packed = flow._packed(dev, feature)
+        M = beam * 12
+        budget = GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_LAUNCH_ROWS
+        g = int(images_per_launch) if images_per_launch is not None else max(1, budget // M)
+        g = max(1, min(g, B, 65535))
+        est = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+        best = torch.empty(B, dtype=torch.float32, device=dev)
+        index = torch.empty(B, dtype=torch.int64, device=dev)
+        for level in range(S, L):
+            last = level + 1 == L
+            nxt = torch.empty(B, beam, dtype=torch.int64, device=dev) if not last else None
+            for b0 in range(0, B, g):
+                b1 = min(B, b0 + g)
+                rows, rot = grid_children(kept[b0:b1], level, offset)
+                feat = feature[b0:b1] if feature is not None else None
+                fisher = (A, c) if A is None or A.shape[0] == 1 else (A[b0:b1], c[b0:b1])
+                lp = runtime.run_log_prob(flow, packed, rot.reshape(-1, 3, 3), feat, *fisher, feature_repeat=M)["logp"]
+                lp = lp.reshape(b1 - b0, M)
+                sel = grid_beam_select(lp, 1 if last else beam, rows)[0]
+                if not last:
+                    nxt[b0:b1] = sel
+                    continue
+                pos = torch.argmax((rows == sel).to(torch.int32), dim=-1)          # the first candidate of the chosen row
+                ar = torch.arange(b1 - b0, device=dev)
+                est[b0:b1], best[b0:b1], index[b0:b1] = rot[ar, pos], lp[ar, pos], sel[:, 0]     # log p with its own bits
+            kept = nxt
+    return est, best, index, offset
+
+
 def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
     """[B,3,3] rotations -> unit quaternions [B,4] (real part first), largest-component branch per row."""
     m = R.reshape(-1, 3, 3)
@@ -588,7 +715,7 @@ def min_geodesic_distance(est_rotation: torch.Tensor, gt_rotation: torch.Tensor)
 
 def pose_accuracy(flow: Flow, feature, gt_rotation, queries=None, base=None, number_queries: int = 500, thresholds_deg=(15.0, 30.0),
                   method: str = "log_inv", recursion_level: int = None, offset=None, refine_steps: int = 100, top_k: int = 1,
-                  separation_deg: float = 15.0):
+                  separation_deg: float = 15.0, beam: int = None, start_level: int = 2):
     """What ``Agent.eval_acc`` + ``eval.py`` report per batch (agent.py:238-283, utils/utils.py:208-209): arg-max pose estimate, geodesic
     error in degrees against the (possibly several) ground truths, accuracy at the thresholds.  -> dict(err_deg, est_rotation, acc)
 
@@ -598,21 +725,31 @@ def pose_accuracy(flow: Flow, feature, gt_rotation, queries=None, base=None, num
 
     ``top_k`` > 1 (grid methods only; the commented-out ``for top_k in [1, 2, 4]`` of eval.py:243,297,406): the estimates are the modes of
     ``grid_pose_modes`` (``separation_deg`` apart; "nll_grad" refines every valid one, each with its image's feature row), ``est_rotation``
-    is [B,k,3,3] (NaN for a missing mode) and an image's error is the smallest over its valid modes (best of k)."""
+    is [B,k,3,3] (NaN for a missing mode) and an image's error is the smallest over its valid modes (best of k).
+
+    ``beam`` (grid methods with top_k = 1 only): the grid estimate is ``grid_beam_estimate_rotations``'s coarse-to-fine search from
+    ``start_level`` to the level above, keeping ``beam`` rows per image ("nll_grad" refines it); None (default) searches the whole grid."""
     if method not in ("log_inv", "log_pdf", "nll_grad"):
         raise ValueError(f"pose_accuracy: method must be 'log_inv', 'log_pdf' or 'nll_grad', got {method!r}")
     if int(top_k) < 1 or (int(top_k) > 1 and method == "log_inv"):
         raise ValueError(f"pose_accuracy: top_k={top_k} needs a grid method (log_inv's samples are not equivolumetric and carry no mass)")
+    if beam is not None and (method == "log_inv" or int(top_k) > 1):
+        raise ValueError(f"pose_accuracy: beam={beam} needs a grid method and top_k = 1 (modes and masses need the whole grid)")
     if top_k > 1:
         return _pose_accuracy_top_k(flow, feature, gt_rotation, base, number_queries, thresholds_deg, method, recursion_level, offset,
                                     refine_steps, int(top_k), separation_deg)
     if method == "log_inv":
         est, _ = estimate_rotations(flow, feature, queries=queries, base=base, number_queries=number_queries)
+    elif beam is not None:
+        from .utils import sd
+        level = recursion_level if recursion_level is not None else sd.closest_grid_level(number_queries)
+        est = grid_beam_estimate_rotations(flow, feature, recursion_level=level, start_level=start_level, beam=beam, offset=offset,
+                                           base=base)[0]
     else:
         est = grid_estimate_rotations(flow, feature, number_queries=number_queries, recursion_level=recursion_level, offset=offset,
                                       base=base)[0]
-        if method == "nll_grad":
-            est = refine_rotations(flow, feature, est, steps=refine_steps, lr=1e-4, base=None)
+    if method == "nll_grad":
+        est = refine_rotations(flow, feature, est, steps=refine_steps, lr=1e-4, base=None)
     err_deg = torch.rad2deg(min_geodesic_distance(est, gt_rotation))
     return dict(err_deg=err_deg, est_rotation=est, acc={t: float((err_deg <= t).float().mean()) for t in thresholds_deg})
 
