@@ -82,6 +82,20 @@ RNF_FM_HD void proper_svd3(const double a[9], double U[9], double s[3], double V
     s[1] = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
     const double i1 = s[1] > 0.0 ? 1.0 / s[1] : 0.0;
     for (int i = 0; i < 3; ++i) u1[i] *= i1;
+    // rank <= 1: A v1 = 0 leaves u1 (and A = 0 leaves u0 too) undetermined.  Any completion to a rotation is a proper SVD, and
+    // MF(A) is invariant under rotations within an eigenspace of singular value 0: A = 0 takes U = V, rank 1 takes the unit
+    // vector u0 x e_k for the axis e_k least aligned with u0.  Full-rank matrices never enter these branches.
+    if (s[0] == 0.0) {
+        for (int i = 0; i < 3; ++i) { u0[i] = v0[i]; u1[i] = v1[i]; }
+    } else if (s[1] == 0.0) {
+        const int k = fabs(u0[0]) <= fabs(u0[1]) ? (fabs(u0[0]) <= fabs(u0[2]) ? 0 : 2) : (fabs(u0[1]) <= fabs(u0[2]) ? 1 : 2);
+        const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
+        u1[0] = u0[1] * e[2] - u0[2] * e[1];
+        u1[1] = u0[2] * e[0] - u0[0] * e[2];
+        u1[2] = u0[0] * e[1] - u0[1] * e[0];
+        const double in = 1.0 / sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
+        for (int i = 0; i < 3; ++i) u1[i] *= in;
+    }
     u2[0] = u0[1] * u1[2] - u0[2] * u1[1];
     u2[1] = u0[2] * u1[0] - u0[0] * u1[2];
     u2[2] = u0[0] * u1[1] - u0[1] * u1[0];
