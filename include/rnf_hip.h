@@ -228,8 +228,11 @@ size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers);
  * conventions of the reference's torch.svd (LAPACK's dense-SVD path restated for 4x4, csrc/svd4_lapack.h; identical for >= 99.8 % of
  * random matrices, the rest differ like two LAPACK builds do).  mlp_out_dev [n][16] from rnf_cond_mlp_forward, rot_out_dev [n][16] = one
  * slot of the side buffer of an RNF_LAYER_SIDE16_ROT layer.  Stream-ordered, no host synchronisation.
- * fail_flag_dev (int32, may be null): bit 0 is OR-ed in when the QR iteration of a sample did not converge within LAPACK's sweep limit (the
- * slot then holds the factors of the last sweep); the caller zeroes it and reads it back when convenient.
+ * fail_flag_dev (int32, may be null): bit 0 is OR-ed in when a sample has no usable result: a NaN / inf entry in its matrix or a singular
+ * value beyond FLT_MAX (rot and the factors of that sample are then NaN throughout), or a QR iteration that did not converge within
+ * LAPACK's sweep limit (the slot then holds the factors of the last sweep).  With the flag clear every rot is orthogonal to rounding,
+ * whatever the scale of the matrix (it is rescaled by a power of two when its largest entry leaves [2^-24, 2^24]).  The caller zeroes the
+ * flag and reads it back when convenient; other samples of the launch are not affected.
  * rnf_condrot_svd also returns the factors -- u_out_dev [n][16] (U row-major), s_out_dev [n][4] (decreasing), vt_out_dev [n][16] (V^T
  * row-major) -- which is what the backward of U^T V needs (d rot = -wU rot + rot wV with wU, wV from U^T dM V; flow/rottrans.py here), so
  * that evaluation AND training see the same routine's sign choices (ABI v6; v5 trained through the host's torch.svd). */
@@ -242,7 +245,9 @@ int rnf_condrot_svd(const float *mlp_out_dev, int64_t n, float *rot_out_dev, flo
  *     weight[n] = w_p (reshape(wl[n], C, C) * l_mask + l_eye) (reshape(wu[n], C, C) * u_mask + dvec),  dvec[d] = s_sign[d] exp(ws[d][d])
  * where `torch.diag` of the 2-D tensor s_sign * exp(ws) is its diagonal ACROSS THE BATCH (rows 0..C-1) and the C-vector is broadcast over
  * the last axis -- added to every row of the upper factor.  Reproduced as the reference defines it: the matrix of sample n depends on the
- * first C rows of the batch; n < C is an error (the reference fails to broadcast).
+ * first C rows of the batch.  n = 1 follows the reference as well (torch.diag of a [1, C] tensor is the one-entry vector
+ * s_sign[0] exp(ws[0][0]), broadcast to every column; its gradient lands in g_ws[0][0]); 1 < n < C is an error (the reference fails
+ * to broadcast).
  * wl_dev, wu_dev, ws_dev: the three conditioners' outputs (rnf_cond_mlp_forward), rows of stride_wl / stride_wu (>= C*C) and stride_ws
  * (>= C) floats; C = 3 or 4; consts_dev = w_p [C*C] | l_mask [C*C] | u_mask [C*C] | l_eye [C*C] | s_sign [C] (the module's buffers);
  * add_identity != 0: + I (Condition9TransLU, squeezetrans.py:269-271); side_out_dev [n][16]: one slot of the side buffer of an

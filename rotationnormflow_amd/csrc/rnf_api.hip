@@ -1373,7 +1373,9 @@ extern "C" int rnf_condrot_svd(const float *mlp_out, int64_t n, float *rot_out, 
 //     weight[n] = w_p . (reshape(wl[n], C, C) * l_mask + l_eye) . (reshape(wu[n], C, C) * u_mask + dvec),   dvec[d] = s_sign[d] exp(ws[d][d])
 // `torch.diag` of the 2-D [N, C] tensor s_sign * exp(ws) (squeezetrans.py:126-127) is its DIAGONAL ACROSS THE BATCH -- entry d of row d,
 // d < C -- and the resulting C-vector is broadcast over the last axis of every sample's upper factor: it is added to EVERY row c of
-// column d, and the weight of sample n depends on batch rows 0 .. C-1.  Reproduced as defined.  consts = w_p [C*C] | l_mask [C*C] |
+// column d, and the weight of sample n depends on batch rows 0 .. C-1.  Reproduced as defined, a batch of ONE row included: torch.diag of
+// a [1, C] tensor is the one-entry vector s_sign[0] exp(ws[0][0]), which broadcasts to every column (dvec[d] = that entry for all d, its
+// gradient the sum over the columns); 2 .. C-1 rows have a diagonal of the wrong length and fail in the reference, and here.  consts = w_p [C*C] | l_mask [C*C] |
 // u_mask [C*C] | l_eye [C*C] | s_sign [C] (the module's buffers, as loaded from the checkpoint).  One thread per sample; out [n][16]:
 // the C x C matrix row-major in the first C*C floats (+ identity when add_identity: Condition9TransLU, squeezetrans.py:269-271), rest 0.
 template <int C>
@@ -1385,7 +1387,7 @@ __global__ void condlu_assemble_kernel(const float *wl, const float *wu, const f
     const float *wp = consts, *lm = consts + CC, *um = consts + 2 * CC, *le = consts + 3 * CC, *sg = consts + 4 * CC;
     float dvec[C], Lm[CC], Um[CC], PL[CC];
 #pragma unroll
-    for (int d = 0; d < C; ++d) dvec[d] = sg[d] * expf(ws[(long long)d * ss + d]);       // rows 0 .. C-1 of the BATCH
+    for (int d = 0; d < C; ++d) dvec[d] = n == 1 ? sg[0] * expf(ws[0]) : sg[d] * expf(ws[(long long)d * ss + d]);       // rows 0 .. C-1 of the BATCH
 #pragma unroll
     for (int k = 0; k < CC; ++k) {
         Lm[k] = wl[i * sl + k] * lm[k] + le[k];
@@ -1433,7 +1435,7 @@ __global__ void condlu_backward_kernel(const float *wl, const float *wu, const f
     if (i < n) {
         float dvec[C], Lm[CC], Um[CC], PL[CC], PtG[CC], G[CC];
 #pragma unroll
-        for (int d = 0; d < C; ++d) dvec[d] = sg[d] * expf(ws[(long long)d * ss + d]);
+        for (int d = 0; d < C; ++d) dvec[d] = n == 1 ? sg[0] * expf(ws[0]) : sg[d] * expf(ws[(long long)d * ss + d]);
 #pragma unroll
         for (int k = 0; k < CC; ++k) {
             Lm[k] = wl[i * sl + k] * lm[k] + le[k];
@@ -1483,14 +1485,21 @@ __global__ void condlu_diag_kernel(const float *ws, int ss, long long n, const f
     const float *sg = consts + 4 * C * C;
 #pragma unroll
     for (int d = 0; d < C; ++d) g_ws[i * gss + d] = (i == d) ? dsum[d] * sg[d] * expf(ws[(long long)d * ss + d]) : 0.f;
+    if (n == 1) {                                   // the one-entry diagonal feeds every column: its gradient collects all of them
+        float t = 0.f;
+#pragma unroll
+        for (int d = 0; d < C; ++d) t += dsum[d];
+        g_ws[0] = t * sg[0] * expf(ws[0]);
+    }
 }
 extern "C" int rnf_condlu_matrices(const float *wl, const float *wu, const float *ws, int32_t stride_wl, int32_t stride_wu, int32_t stride_ws, int64_t n,
                                    int32_t C, const float *consts, int32_t add_identity, float *side_out, void *stream) {
     if (C != 3 && C != 4) return fail("rnf_condlu_matrices: in_channel %d (3 or 4)", C);
     if (n < 0 || stride_wl < C * C || stride_wu < C * C || stride_ws < C) return fail("rnf_condlu_matrices: n=%lld row strides %d %d %d", (long long)n, stride_wl, stride_wu, stride_ws);
     if (n == 0) return 0;
-    // the reference broadcasts the C-vector torch.diag(...) of an [n, C] tensor (length min(n, C)) against [n, C, C]: fewer than C rows fail there
-    if (n < C) return fail("rnf_condlu_matrices: a batch of %lld rows has no %d-entry batch diagonal (flow/squeezetrans.py:126-127 fails to broadcast)", (long long)n, C);
+    // the reference broadcasts the vector torch.diag(...) of an [n, C] tensor (length min(n, C)) against [n, C, C]: 2 .. C-1 rows fail there,
+    // one row broadcasts its single entry
+    if (n > 1 && n < C) return fail("rnf_condlu_matrices: a batch of %lld rows has no %d-entry batch diagonal (flow/squeezetrans.py:126-127 fails to broadcast)", (long long)n, C);
     if (!wl || !wu || !ws || !consts || !side_out) return fail("rnf_condlu_matrices: null pointer");
     const dim3 grid((unsigned)((n + 127) / 128)), block(128);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1502,7 +1511,7 @@ extern "C" int rnf_condlu_matrices(const float *wl, const float *wu, const float
 extern "C" int rnf_condlu_backward(const float *wl, const float *wu, const float *ws, int32_t stride_wl, int32_t stride_wu, int32_t stride_ws, int64_t n,
                                    int32_t C, const float *consts, const float *g_side, float *g_wl, float *g_wu, float *g_ws, float *scratch, void *stream) {
     if (C != 3 && C != 4) return fail("rnf_condlu_backward: in_channel %d (3 or 4)", C);
-    if (n < C || stride_wl < C * C || stride_wu < C * C || stride_ws < C) return fail("rnf_condlu_backward: n=%lld row strides %d %d %d", (long long)n, stride_wl, stride_wu, stride_ws);
+    if (n < 1 || (n > 1 && n < C) || stride_wl < C * C || stride_wu < C * C || stride_ws < C) return fail("rnf_condlu_backward: n=%lld row strides %d %d %d", (long long)n, stride_wl, stride_wu, stride_ws);
     if (!wl || !wu || !ws || !consts || !g_side || !g_wl || !g_wu || !g_ws || !scratch) return fail("rnf_condlu_backward: null pointer");
     const dim3 grid((unsigned)((n + 127) / 128)), block(128);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

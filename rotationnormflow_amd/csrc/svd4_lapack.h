@@ -13,7 +13,19 @@
 //              positive by negating ROWS OF V^T, then sorted by decreasing value with row / column swaps.
 // fp32 throughout, like the fp32 reference.  A restatement in numpy of exactly this code agreed with torch.svd on U^T V for 20 000 of
 // 20 000 random matrices (tests/test_svd4.py pins the compiled header the same way, on the CPU).
+//
+// RANGE (sgesdd's slascl step): the path above squares its entries in fp32 (slartg's f^2 + g^2, slas2, slasv2), which overflows from
+// max|a_ij| ~ 2e19 and loses everything to underflow below ~ 1e-16.  svd() therefore multiplies a matrix whose largest entry lies outside
+// [2^-24, 2^24] by the exact power of two that brings that entry into [1, 2), factorises, and multiplies the singular values back; U, V^T
+// and U^T V are invariant, and a matrix inside the band -- every matrix ConditionRot meets in a healthy flow -- takes the path untouched.
+// svd() RETURNS FALSE, the failure flag of its callers, in exactly two cases:
+//   * a NaN / inf entry in the matrix, or a non-finite factor or singular value after the factorisation (a singular value beyond
+//     FLT_MAX): U, s and V^T -- and with them U^T V -- are then NaN THROUGHOUT, so that no caller can take them for a rotation;
+//   * sbdsqr's sweep limit (6 n^2 rotations): the slots hold the last sweep's factors, orthogonal but not converged.
+// With `true`, U and V^T are orthogonal to rounding and s is finite, non-negative and non-increasing (tests/test_svd4.py and
+// tests/test_gpu_condrot_svd.py judge every sample against fp64, tests/svd4_exact.py).
 #pragma once
+#include <float.h>
 #include <math.h>
 #if defined(__HIPCC__)
 #define RNF_SV_HD __host__ __device__ inline
@@ -149,11 +161,13 @@ RNF_SV_HD void rot_cols(float *M, int i, int j, float c, float s) {
     }
 }
 
-// A (row-major 4x4) -> U (columns = left singular vectors), s (decreasing), VT (rows = right singular vectors), signs as LAPACK's sgesdd
-RNF_SV_HD bool svd(const float *A_in, float *U, float *sv, float *VT) {
+// A 2^-ex (A row-major 4x4 and finite; its largest entry times 2^-ex is 0 or inside the safe band) -> U (columns = left singular
+// vectors), s (decreasing, multiplied back by 2^ex), VT (rows = right singular vectors), signs as LAPACK's sgesdd; false = sweep limit.
+// ldexpf is exact, and the identity at ex = 0.
+RNF_SV_HD bool svd_scaled(const float *A_in, int ex, float *U, float *sv, float *VT) {
     constexpr int n = 4;
     float A[16], d[4], e[3], tauq[4], taup[3];
-    for (int k = 0; k < 16; ++k) A[k] = A_in[k];
+    for (int k = 0; k < 16; ++k) A[k] = ldexpf(A_in[k], -ex);
     // ---- sgebd2 ----
     for (int i = 0; i < n; ++i) {
         {   // H(i): annihilate A(i+1:n, i)
@@ -390,7 +404,35 @@ RNF_SV_HD bool svd(const float *A_in, float *U, float *sv, float *VT) {
             }
         }
     }
-    for (int i = 0; i < n; ++i) sv[i] = d[i];
+    for (int i = 0; i < n; ++i) sv[i] = ldexpf(d[i], ex);
+    return ok;
+}
+
+constexpr float kBandLo = 5.9604644775390625e-08f;     // 2^-24: 32 amax^2 stays below FLT_MAX up to 2^24, and the square of an entry 2^-24 amax
+constexpr float kBandHi = 16777216.f;                  // (all that fp32 resolves beside amax) stays a normal number down to 2^-24
+
+// svd_scaled behind the range handling described at the top of this file
+RNF_SV_HD bool svd(const float *A_in, float *U, float *sv, float *VT) {
+    float amax = 0.f;
+    bool finite = true;
+    for (int k = 0; k < 16; ++k) {
+        const float a = fabsf(A_in[k]);
+        finite = finite && a <= FLT_MAX;              // false for NaN and inf
+        amax = fmaxf(amax, a);
+    }
+    bool ok = false;
+    if (finite) {
+        // amax = 2^ilogbf(amax) * [1, 2), subnormals included; inside the band (and for the zero matrix) the matrix stays as it is
+        const int ex = (amax == 0.f || (amax >= kBandLo && amax <= kBandHi)) ? 0 : ilogbf(amax);
+        ok = svd_scaled(A_in, ex, U, sv, VT);
+        for (int k = 0; k < 16; ++k) finite = finite && fabsf(U[k]) <= FLT_MAX && fabsf(VT[k]) <= FLT_MAX;
+        for (int k = 0; k < 4; ++k) finite = finite && sv[k] <= FLT_MAX;
+    }
+    if (!finite) {
+        ok = false;
+        for (int k = 0; k < 16; ++k) { U[k] = NAN; VT[k] = NAN; }
+        for (int k = 0; k < 4; ++k) sv[k] = NAN;
+    }
     return ok;
 }
 

@@ -176,8 +176,9 @@ _pending_svd_flags = []          # (event, pinned host int32, device flag): conv
 
 
 def _check_svd_flags(wait: bool = False):
-    """Raise if the 4x4 QR iteration of an EARLIER ConditionRot call did not converge (csrc/svd4_lapack.h returns false after LAPACK's
-    sweep limit; the slot then holds the last sweep's factors).  Like the sampler's flag (utils/fisher.py) the failure surfaces one call
+    """Raise if the 4x4 SVD of an EARLIER ConditionRot call had a sample without a usable result (csrc/svd4_lapack.h returns false for a
+    matrix with NaN / inf entries or a singular value beyond FLT_MAX -- that sample's rot is NaN throughout -- and after LAPACK's sweep
+    limit, where the slot holds the last sweep's factors; finite matrices of any scale are rescaled, not flagged).  Like the sampler's flag (utils/fisher.py) the failure surfaces one call
     later, so that no call waits for the device."""
     if torch.cuda.is_current_stream_capturing():            # inside a HIP graph capture: no event queries
         return
@@ -191,12 +192,13 @@ def _check_svd_flags(wait: bool = False):
             keep.append((ev, host, flag))
     _pending_svd_flags[:] = keep
     if bad:
-        raise RuntimeError("ConditionRot: the SVD of a per-sample 4x4 matrix did not converge in an earlier call (LAPACK's sbdsqr sweep limit, "
-                           "csrc/svd4_lapack.h): the conditioner's output is not a usable matrix (NaN / inf entries?)")
+        raise RuntimeError("ConditionRot: the SVD of a per-sample 4x4 matrix failed in an earlier call (csrc/svd4_lapack.h): the conditioner's "
+                           "output holds NaN / inf entries or overflows fp32 (that sample's rotation is NaN), or the QR iteration hit "
+                           "LAPACK's sbdsqr sweep limit")
 
 
 def condrot_failures(wait: bool = True):
-    """Raise if any earlier ConditionRot evaluation reported a non-converged SVD (waits for outstanding calls by default)."""
+    """Raise if any earlier ConditionRot evaluation reported a failed SVD (waits for outstanding calls by default)."""
     _check_svd_flags(wait)
 
 
@@ -269,8 +271,8 @@ class ConditionRot(_SideLayer):
     the layer is defined by the routine: net(feature) and the per-sample U^T V both run on the GPU, the latter through
     csrc/svd4_lapack.h -- LAPACK's dense-SVD path (sgebd2, sorgbr, sbdsqr) restated for 4x4 so that its sign conventions are those of the
     reference's ``torch.svd`` (tests/test_svd4.py) -- in evaluation AND in training (round 4: ``_CondRotFn`` differentiates U^T V from the
-    device routine's own factors; round 3 trained through the host's torch.svd).  No device -> host copy in either mode; a non-converged QR
-    iteration raises one call later (``condrot_failures``)."""
+    device routine's own factors; round 3 trained through the host's torch.svd).  No device -> host copy in either mode; a sample whose
+    matrix is not finite (its rot is NaN) or whose QR iteration did not converge raises one call later (``condrot_failures``)."""
     _rnf_kind = runtime.KIND_SIDE16_ROT
     _rnf_no_graph = False          # nothing between the conditioner and the stack kernel leaves the device: capturable into a HIP graph
 

@@ -274,7 +274,7 @@ class ConditionLU(nn.Module):
     ConditionalTransforms.  Buffer / parameter names are the checkpoint contract.  The reference's expression is reproduced as defined,
     including ``torch.diag`` of the 2-D [N, C] tensor: that call takes the diagonal ACROSS THE BATCH (entry i of sample i, i < C) and the
     C-vector is then broadcast onto every row of every sample's upper factor -- the weight of one sample depends on the first C samples
-    of the batch it travels in (and a batch of fewer than C rows fails to broadcast, as in the reference).  The three MLPs run through the
+    of the batch it travels in (a batch of 2 .. C-1 rows fails to broadcast, as in the reference, and a batch of ONE row broadcasts its one-entry diagonal to every column, as there).  The three MLPs run through the
     HIP conditioner (runtime.SideNet), the assembly and its backward through ``rnf_condlu_matrices`` / ``rnf_condlu_backward`` (round 6)."""
 
     _rnf_batch_coupled = True
@@ -343,7 +343,7 @@ class _CondLUFn(torch.autograd.Function):
         from .. import _lib
         (wl, sl), (wu, su), (ws, ss) = _rows(wl.detach()), _rows(wu.detach()), _rows(ws.detach())
         n, dev = wl.shape[0], wl.device
-        if 0 < n < C:          # the reference's broadcast of the C-vector torch.diag(...) against [n, C, C] fails for fewer than C rows
+        if 1 < n < C:          # the reference's broadcast of torch.diag(...) (length min(n, C)) against [n, C, C] fails for 2 .. C-1 rows; ONE row broadcasts
             raise RuntimeError(f"The size of tensor a ({n}) must match the size of tensor b ({C}) at non-singleton dimension 2")
         out = torch.empty((n, 16), dtype=torch.float32, device=dev)
         if n:

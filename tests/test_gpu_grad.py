@@ -583,9 +583,29 @@ def test_condition_lu_assembly_kernel_and_its_backward_equal_the_reference_expre
                 scale = max(1.0, float(b.grad.abs().max()))
                 assert (a.grad.cpu().double() - b.grad).abs().max() < 5e-5 * scale
                 a.grad = None
-    # fewer rows than C fail like the reference's broadcast
-    with pytest.raises(RuntimeError, match="must match the size"):
-        _CondLUFn.apply(*(t[: C - 1] for t in ins), consts, C, False)
+    # 2 .. C-1 rows fail like the reference's broadcast
+    for k in range(2, C):
+        with pytest.raises(RuntimeError, match="must match the size"):
+            _CondLUFn.apply(*(t[:k] for t in ins), consts, C, False)
+        with pytest.raises(RuntimeError, match="must match the size"):
+            _condlu_reference(*(b[:k, : (C * C if i < 2 else C)] for i, b in enumerate(bufs)), w_p, l_mask, u_mask, l_eye, s_sign, C)
+    # ONE row: torch.diag of a [1, C] tensor is a one-entry vector, which broadcasts to every column; forward and backward as above
+    for add_eye in (False, True):
+        one = [b[5:6].cuda()[:, : (C * C if i < 2 else C)].requires_grad_(True) for i, b in enumerate(bufs)]
+        out = _CondLUFn.apply(*one, consts, C, add_eye)
+        ref_in = [b[5:6, : (C * C if i < 2 else C)].double().requires_grad_(True) for i, b in enumerate(bufs)]
+        want = _condlu_reference(*ref_in, w_p.double(), l_mask.double(), u_mask.double(), l_eye.double(), s_sign.double(), C)
+        if add_eye:
+            want = want + torch.eye(C, dtype=torch.float64)
+        got = out[:, : C * C].detach().cpu().double().reshape(1, C, C)
+        assert (got - want.detach()).abs().max() < 2e-5 * max(1.0, float(want.detach().abs().max()))
+        if C == 3:
+            assert float(out[:, 9:].abs().max()) == 0.0
+        (out * G[5:6].cuda()).sum().backward()
+        (want * G[5:6, : C * C].double().reshape(1, C, C)).sum().backward()
+        assert float(ref_in[2].grad[0, 0].abs()) > 1e-3 and float(ref_in[2].grad[0, 1:].abs().max()) == 0.0
+        for a, b in zip(one, ref_in):
+            assert (a.grad.cpu().double() - b.grad).abs().max() < 5e-5 * max(1.0, float(b.grad.abs().max()))
 
 
 def test_condition_lu_flow_trains_inside_a_hip_graph():
