@@ -8,11 +8,13 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/rnf_hip.h"
 #include "featproj_kernel.h"
 #include "flow_kernels.h"
+#include "flow_plan.h"
 #include "train_kernels.h"
 #include "train_block16.h"
 #include "pack_device.h"
@@ -49,6 +51,13 @@ static int fail(const char *fmt, ...) {
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// The 0/1 switches of the environment: on unless the value starts with '0' (default on), or off unless it starts with '1'.  Each is read
+// once per process (flow_switches, equalise_allowed); flow_plan.h struct Switches says what each one does.
+static bool env_flag(const char *name, bool dflt) {
+    const char *e = std::getenv(name);
+    return (e && e[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
+}
 
 extern "C" int rnf_abi_version(void) { return RNF_ABI_VERSION; }
 extern "C" const char *rnf_last_error(void) { return g_err; }
@@ -198,10 +207,7 @@ struct ScaledMlp {
 // catch without the equalisation)
 static int g_equalize = -1;
 static bool equalise_allowed() {
-    if (g_equalize < 0) {
-        const char *e = std::getenv("RNF_EQUALIZE");
-        g_equalize = (e && e[0] == '0') ? 0 : 1;
-    }
+    if (g_equalize < 0) g_equalize = env_flag("RNF_EQUALIZE", true) ? 1 : 0;
     return g_equalize == 1;
 }
 extern "C" int rnf_set_equalize(int on) {
@@ -582,25 +588,10 @@ extern "C" int rnf_pack_rot16(const float *mat16, float *out) {
 // ------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------
-constexpr int NW = 8;                                   // waves per workgroup (2 per SIMD): exact-fp32 and inverse kernels, featproj
-constexpr int NW_FWD_H = 8;                             // forward split-precision kernel small launches
-constexpr int NW_FWD_NARROW = 4;                        // same kernel, 1 wave per SIMD: launches that leave half of the CUs empty at 8 waves (small
-                                                        // batches, training: forward latency 0.41 -> 0.34 ms at 1024 rotations)
-constexpr int NW_FWD_WIDE = 16;                         // same kernel, 4 waves per SIMD (fits in 128 VGPRs): launches that fill every CU with
-                                                        // 512-rotation workgroups; +12 % over 8 waves (profiles/r1/nw_sweep.txt)
-#ifndef RNF_NW_FP
-#define RNF_NW_FP 8
-#endif
-constexpr int NW_INV_BIG = 4;                           // inverse with 64 < K <= 128: one wave per SIMD
-constexpr int NW_FP = RNF_NW_FP;                        // waves per workgroup of the feature projection (workgroups per CU: 8 / NW_FP)
-#ifndef RNF_CHUNK_LOG2
-#define RNF_CHUNK_LOG2 18           // (17 / 16 measured and not better: profiles/r6/ab_chunk_C4.jsonl)
-#endif
-constexpr long long CHUNK_SAMPLES = 1LL << RNF_CHUNK_LOG2;   // samples per launch when a feature projection scratch is needed
-// head of the workspace: [0, 2048) block partials of the primary launch, [2048, 4095) partials of the exact-fp32 re-run, double 4095 =
-// two int32: {guard of the current chunk, sticky "a re-run happened in this call"} (flow_kernels.h FlowArgs::guard)
-constexpr size_t PARTIALS_BYTES = 4096 * sizeof(double);
-constexpr int PARTIALS_FB_AT = 2048, GUARD_AT = 4095;
+static_assert(klim::MAX_LAYERS == MAX_LAYERS && klim::MAX_SLOTS == MAX_SLOTS && klim::FP_KCHUNK == FP_KCHUNK && klim::FUSED_MAX_F == FUSED_MAX_F &&
+                  klim::FUSED_PA_FLOATS == FUSED_PA_FLOATS && klim::B3_REGION_FLOATS == Mlp<2>::REGION_FLOATS && klim::FP2_LDS_BYTES == FP2_LDS_BYTES &&
+                  sizeof(LayerEntry) == sizeof(int2),
+              "csrc/flow_plan.h and the kernel headers disagree");
 
 // Compute units of the CALLING THREAD'S CURRENT DEVICE (grids of the persistent kernels are sized by it).  Cached per device ordinal: one
 // process may drive several GPUs (nn.DataParallel, agent.py:22; round 5 cached the first device's count for the whole process -- VERDICT r5 #7).
@@ -617,95 +608,43 @@ static int device_cus() {
     return c;
 }
 
-extern "C" size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers) {
-    size_t bytes = PARTIALS_BYTES;
-    if (n_cond_layers > 0) {
-        long long chunk = n < CHUNK_SAMPLES ? n : CHUNK_SAMPLES;
-        long long groups = (chunk + 255) / 256 * 8;     // whole workgroup tiles, for either workgroup size
-        const long long g16 = (chunk + 32 * NW_FWD_WIDE - 1) / (32 * NW_FWD_WIDE) * NW_FWD_WIDE;
-        if (g16 > groups) groups = g16;
-        bytes += (size_t)n_cond_layers * groups * G_FLOATS_PER_GROUP * sizeof(float);
-    }
-    return bytes;
+extern "C" size_t rnf_workspace_bytes(int64_t n, int32_t n_cond_layers) { return conditioner_workspace(n, n_cond_layers); }
+
+// One kernel launch: raise the kernel's dynamic-LDS limit to what this launch asks for, launch, check.
+template <typename... P, typename... A>
+static int launch(void (*kernel)(P...), int grid, int block, size_t lds_bytes, hipStream_t stream, const A &...args) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds_bytes, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
-// The workspace rnf_flow_pass requires (rnf_flow_pass_workspace_bytes returns it, run_flow checks against it): the partials block, the
-// feature-projection scratch of n_slots conditional slots -- one 64-float record per (slot, feature row) with shared feature rows -- and
-// behind them, from *stash_at on, the per-wave stash of an inverse pass with K > 128 (the parameters of 64 segments per lane stay in
-// registers, flow_kernels.h mobius_inv_tiles).
-static size_t flow_workspace(const RnfFlowPass &p, int n_slots, bool any_mlp, size_t *stash_at) {
-    const bool shared = p.feature_div > 0 && n_slots > 0;
-    size_t bytes = shared ? PARTIALS_BYTES + (size_t)n_slots * (size_t)((p.n + p.feature_div - 1) / p.feature_div) * 64 * sizeof(float)
-                          : rnf_workspace_bytes(p.n, n_slots);
-    *stash_at = bytes;
-    const int KT = (p.segments + 7) / 8;
-    if (p.dir == 1 && any_mlp && KT > 16) bytes += (size_t)device_cus() * NW_INV_BIG * (size_t)(4 * (KT - 16)) * 64 * sizeof(float4);
-    return bytes;
-}
-
-template <typename K>
-static hipError_t allow_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-// RNF_WIDE=0 keeps the forward kernel at 8 waves per workgroup (measurement switch)
-static bool wide_allowed() {
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = std::getenv("RNF_WIDE");
-        mode = (e && e[0] == '0') ? 0 : 1;
-    }
-    return mode == 1;
-}
-
-// staging mode: DMA (LDS-DMA double-phase prefetch, needs segments <= 64) unless RNF_STAGING=sync
-static bool staging_dma() {
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = std::getenv("RNF_STAGING");
-        mode = (e && std::strcmp(e, "sync") == 0) ? 0 : 1;
-    }
-    return mode == 1;
-}
-
-// RNF_GUARD=0: no range guard / fp32 re-run behind split-precision calls (measurement switch)
-static bool guard_allowed() {
-#ifdef RNF_NO_GUARD
-    return false;
-#endif
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = std::getenv("RNF_GUARD");
-        mode = (e && e[0] == '0') ? 0 : 1;
-    }
-    return mode == 1;
-}
-
-// RNF_LEAN=0 keeps unconditional Moebius / affine stacks on the general instantiation (measurement switch)
-static bool lean_allowed() {
-#ifdef RNF_NO_LEAN
-    return false;
-#endif
-    static int mode = -1;
-    if (mode < 0) {
-        const char *e = std::getenv("RNF_LEAN");
-        mode = (e && e[0] == '0') ? 0 : 1;
-    }
-    return mode == 1;
-}
-
-// RNF_FUSED=1 / rnf_set_fused(1): conditional forward passes (every MLP layer conditional, F <= 256) run the FUSED instantiation of the
-// stack kernel -- feature projection inside, no scratch round trip (HBM traffic = the algorithmic bytes) -- instead of the pre-pass + stack
-// pair.  OFF by default: measured on C4 it is SLOWER (12.2 ms against 8.7 ms, profiles/r3/fused_c4.md): the features take 128 of the 256
-// registers an 8-wave workgroup has per lane, the rest of the layer does not fit beside them, and its projection phases run in lockstep
-// between workgroup barriers with nothing to overlap.
-static int g_fused = -1;
+static int g_fused = -1;                                // RNF_FUSED, read at its first use; rnf_set_fused overrides it
 static bool fused_allowed() {
-    if (g_fused < 0) {
-        const char *e = std::getenv("RNF_FUSED");
-        g_fused = (e && e[0] == '1') ? 1 : 0;
-    }
+    if (g_fused < 0) g_fused = env_flag("RNF_FUSED", false) ? 1 : 0;
     return g_fused == 1;
+}
+static Switches flow_switches() {                       // the others: read at the first flow pass
+    static const Switches env = [] {
+        Switches s;
+        s.wide = env_flag("RNF_WIDE", true);
+        const char *staging = std::getenv("RNF_STAGING"), *rf = std::getenv("RNF_RF_FIRST");
+        s.staging_dma = !(staging && std::strcmp(staging, "sync") == 0);
+        s.guard = env_flag("RNF_GUARD", true);
+        s.lean = env_flag("RNF_LEAN", true);
+#ifdef RNF_NO_GUARD
+        s.guard = false;
+#endif
+#ifdef RNF_NO_LEAN
+        s.lean = false;
+#endif
+        s.fair = env_flag("RNF_FAIR", true);
+        s.rf_first = rf ? (rf[0] == '4' ? 4 : (rf[0] == '3' ? 3 : 0)) : 0;
+        return s;
+    }();
+    Switches s = env;
+    s.fused = fused_allowed();
+    return s;
 }
 extern "C" int rnf_set_fused(int on) {
     const int old = fused_allowed() ? 1 : 0;
@@ -737,230 +676,60 @@ extern "C" int rnf_set_train_block(int rotations) {
     return prev;
 }
 
-// forward pass of a conditional flow with the feature projection inside the stack kernel (flow_kernels.h FUSED)
-#ifndef RNF_NW_FUSED
-#define RNF_NW_FUSED 8
-#endif
-constexpr int NW_FUSED = RNF_NW_FUSED;
-static int launch_fused(const FlowArgs &a, int grid, size_t lds_bytes, hipStream_t stream) {
-    auto kern = flow_stack_kernel<0, 0, NW_FUSED, true, 1, false, 2, true>;
-    HIP_TRY(allow_lds(kern, lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW_FUSED * 64), lds_bytes, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+static int launch_projection(const ProjPlan &j, const FeatProjArgs &fp, hipStream_t stream) {
+    void (*const kernels[])(FeatProjArgs) = {featproj_ksplit_kernel, featproj_kernel<NW_FP, 1, true>, featproj_kernel<NW_FP, 1>, featproj_kernel<NW_FP, 0>};   // (ProjKernel order)
+    return launch(kernels[j.kernel], j.grid, j.block, j.lds_bytes, stream, fp);
 }
 
-// `lean` picks the kernel FAMILY -- 1: Moebius + constant-affine layers only (BASELINE C1 / C2 / C3), 2: the conditional counterpart (Moebius +
-// constant-affine + Condition16Trans, every MLP conditional: C4), 0: the general kernel -- from the flow's structure and from whether the call
-// runs guarded, NEVER from the batch size: the families differ in arithmetic (one-piece softplus of the lean kernels, so3_math.h), the
-// workgroup widths of one family do not, so a rotation's result does not depend on the size of the launch (or chunk, or shard) it travels in.
-template <int DIR, int KT_INV, bool PIPE, int PREC, bool EXT = false, bool ROWS = false>
-static int launch_stack(const FlowArgs &a, int grid, size_t lds_bytes, hipStream_t stream, int nwk, int lean = 0) {
-#define RNF_STACK_GO(NW_, LEAN_)                                                                                \
-    do {                                                                                                        \
-        auto kern = flow_stack_kernel<DIR, KT_INV, NW_, PIPE, PREC, EXT, LEAN_, false, ROWS>;                   \
-        HIP_TRY(allow_lds(kern, lds_bytes));                                                                    \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW_ * 64), lds_bytes, stream, a);                             \
-        HIP_TRY(hipGetLastError());                                                                             \
-        return 0;                                                                                               \
-    } while (0)
-    if constexpr (ROWS && DIR == 0) {                   // shared feature rows, forward: the conditional-lean family only (run_flow checks)
-        if (lean != 2) return fail("internal: shared-row forward launches exist for the conditional-lean family only");
-        if (nwk == NW_FWD_WIDE) RNF_STACK_GO(NW_FWD_WIDE, 2);
-        if (nwk == NW_FWD_H) RNF_STACK_GO(NW_FWD_H, 2);
-        if (nwk == NW_FWD_NARROW) RNF_STACK_GO(NW_FWD_NARROW, 2);
-        return fail("internal: no %d-wave instantiation of the shared-row stack kernel", nwk);
-    } else if constexpr (DIR == 0 && PREC == 1 && PIPE && !EXT) {
-        if (lean == 2) {
-            if (nwk == NW_FWD_WIDE) RNF_STACK_GO(NW_FWD_WIDE, 2);
-            if (nwk == NW_FWD_H) RNF_STACK_GO(NW_FWD_H, 2);
-            if (nwk == NW_FWD_NARROW) RNF_STACK_GO(NW_FWD_NARROW, 2);
-        } else if (lean == 1) {
-            if (nwk == NW_FWD_WIDE) RNF_STACK_GO(NW_FWD_WIDE, 1);
-            if (nwk == NW_FWD_H) RNF_STACK_GO(NW_FWD_H, 1);
-            if (nwk == NW_FWD_NARROW) RNF_STACK_GO(NW_FWD_NARROW, 1);
-        } else {
-            if (nwk == NW_FWD_WIDE) RNF_STACK_GO(NW_FWD_WIDE, 0);
-            if (nwk == NW_FWD_NARROW) RNF_STACK_GO(NW_FWD_NARROW, 0);
-        }
-    }
-    if constexpr (DIR == 1 && PREC == 1 && PIPE && !EXT && KT_INV <= 8) {
-        // small inverse launches (round 5): 4-wave workgroups, one wave per SIMD, twice as many workgroups -- a launch that leaves half of
-        // the CUs empty at 8 waves is a latency chain per wave (2^15 rotations: 0.73 -> 0.57 ms); same arithmetic, bit-equal rows
-        if (nwk == NW_FWD_NARROW && !lean) RNF_STACK_GO(NW_FWD_NARROW, 0);
-    }
-    if constexpr (!(ROWS && DIR == 0)) {
-        constexpr int NWK = (DIR == 0 && PREC == 1) ? NW_FWD_H : NW;
-        if (nwk != NWK || lean) return fail("internal: no %d-wave instantiation of this stack kernel", nwk);
-        RNF_STACK_GO(NWK, 0);
-    }
-#undef RNF_STACK_GO
+// The kernel of a key: the table of the instantiations flow_plan.h BUILT lists -- nothing else is instantiated.
+using StackKernel = void (*)(FlowArgs);
+template <size_t... I>
+static StackKernel stack_kernel(int index, std::index_sequence<I...>) {
+    static const StackKernel table[] = {flow_stack_kernel<BUILT.k[I].dir, BUILT.k[I].kt_inv, BUILT.k[I].nw, BUILT.k[I].pipe, BUILT.k[I].prec, BUILT.k[I].ext,
+                                                          BUILT.k[I].lean, BUILT.k[I].fused, BUILT.k[I].rows>...};
+    return index < 0 ? nullptr : table[index];
 }
-
-// inverse with 64 < K <= 128 (flow_kernels.h mobius_inv_tiles: 16 tiles of segment parameters in registers, synchronous staging)
-template <int PREC, bool EXT = false>
-static int launch_big_inverse(const FlowArgs &a, int grid, size_t lds_bytes, hipStream_t stream) {
-    auto kern = flow_stack_kernel<1, 16, NW_INV_BIG, false, PREC, EXT>;
-    HIP_TRY(allow_lds(kern, lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW_INV_BIG * 64), lds_bytes, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+static int launch_stack(const KernelKey &key, const FlowArgs &a, int grid, size_t lds_bytes, hipStream_t stream) {
+    const StackKernel kernel = stack_kernel(key_index(key), std::make_index_sequence<N_BUILT>());
+    if (!kernel) return fail("internal: no %d-wave instantiation of this stack kernel", key.nw);
+    return launch(kernel, grid, key.nw * 64, lds_bytes, stream, a);
 }
 
 static int run_flow(const RnfFlowPass &o) {
-    const float *rot = o.rotation, *feat = o.feature, *blob = o.blob;
-    const int32_t *desc = o.desc;
-    const int64_t n = o.n;
-    const int32_t F = o.feature_dim, n_layers = o.n_layers, K = o.segments;
-    float *rot_out = o.rotation_out, *ldj_out = o.ldj_out;
-    void *ws = o.workspace;
-    const size_t ws_bytes = o.workspace_bytes;
     hipStream_t stream = reinterpret_cast<hipStream_t>(o.stream);
-    if (n < 0) return fail("n=%lld is negative", (long long)n);
-    if (n_layers <= 0 || n_layers > MAX_LAYERS) return fail("n_layers=%d outside [1,%d]", n_layers, MAX_LAYERS);
-    if (K <= 0) return fail("segments=%d must be positive", K);
-    if (!blob || !desc || (n > 0 && !rot)) return fail("null rotation / blob / desc pointer");
-    if (o.fisher_A && (o.fisher_B <= 0 || n % o.fisher_B)) return fail("n=%lld not divisible by fisher rows B=%lld (utils/fisher.py:226)", (long long)n, (long long)o.fisher_B);
-
-    FlowArgs a;
-    std::memset(&a, 0, sizeof(a));
-    FeatProjArgs fp;
-    std::memset(&fp, 0, sizeof(fp));
-    // exact-fp32 images of the same layers in the same blob (desc columns D_PARAM_FB / D_FEAT_FB): a split-precision call is guarded and
-    // re-run on them, on the device, when a sample comes out non-finite (an fp16 operand overflowed)
-    bool have_fb = !o.states;
-    std::vector<int> fbp(n_layers, -1), fbf(MAX_SLOTS, -1), fp_primary(MAX_SLOTS, -1);
-    int n_slots = 0;
-    int min_tiles = 1;                       // fc_last tiles the largest non-Moebius record needs resident in LDS
-    bool any_mlp = false, ext = false;       // ext: the flow contains a layer kind only the extended kernel instantiation carries
-    bool all_mlp_cond = true;                // every MLP layer consumes the feature vector (what the FUSED instantiation handles)
-    int prec = -1, fb_prec = -1, rf_code = 0;
-    bool lean = lean_allowed() && !o.states;   // Moebius + constant 4x4 affine layers only, nothing conditional, no saved states
-    bool lean2 = lean_allowed() && !o.states;  // the conditional counterpart: + Condition16Trans, every MLP layer conditional (checked below)
-    for (int l = 0; l < n_layers; ++l) {
-        const int32_t *d = desc + (size_t)l * D_STRIDE;
-        const int kind = d[D_KIND], perm = d[D_PERM], slot = d[D_SLOT];
-        if (kind < RNF_KIND_MOBIUS || kind > RNF_KIND_LAST) return fail("layer %d: unknown kind %d", l, kind);
-        if (perm < 0 || perm > 5) return fail("layer %d: perm_row %d outside [0,5]", l, perm);
-        if (d[D_PARAM] < 0 || (d[D_PARAM] % 4 && !kind_is_side(kind))) return fail("layer %d: param offset %d must be a non-negative multiple of 4", l, d[D_PARAM]);
-        if ((kind == RNF_KIND_COND16 || kind_is_cond9(kind) || kind == RNF_KIND_COND36) && slot < 0)
-            return fail("layer %d: a conditional affine layer needs a cond_slot", l);
-        if (kind_is_cond9(kind) || kind == RNF_KIND_COND36 || kind_is_side(kind)) ext = true;
-        if (kind_is_side(kind) && !o.side) return fail("layer %d takes per-sample matrices: RnfFlowPass.side is null", l);
-        if ((kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16) || slot >= 0) lean = false;
-        if (kind != RNF_KIND_MOBIUS && kind != RNF_KIND_AFFINE16 && kind != RNF_KIND_COND16) lean2 = false;
-        if (kind == RNF_KIND_COND36) min_tiles = 2;
-        if (slot >= 0) {
-            if (slot >= MAX_SLOTS) return fail("layer %d: cond_slot %d >= %d", l, slot, MAX_SLOTS);
-            if (d[D_FEAT] < 0 || d[D_FEAT] % 4) return fail("layer %d: feat offset %d invalid", l, d[D_FEAT]);
-            fp.feat_off[slot] = d[D_FEAT];
-            fp_primary[slot] = d[D_FEAT];
-            if (slot + 1 > n_slots) n_slots = slot + 1;
-        }
-        if (kind_has_mlp(kind)) {
-            any_mlp = true;
-            if (slot < 0) all_mlp_cond = false;
-            if (d[D_PARAM_FB] < 0 || d[D_PARAM_FB] % 4 || (slot >= 0 && (d[D_FEAT_FB] < 0 || d[D_FEAT_FB] % 4))) have_fb = false;
-            fbp[l] = d[D_PARAM_FB];
-            if (slot >= 0) fbf[slot] = d[D_FEAT_FB];
-            const int p = d[D_PREC] & 255, pfb = (d[D_PREC] >> 8) & 255;      // bits 8..15: arithmetic of the fallback records (0: fp32, 2: bf16x3)
-            if (kind == RNF_KIND_MOBIUS) {                                    // bits 16..17: first-pass order of the inverse root finder
-                const int rc = (d[D_PREC] >> 16) & 3;
-                if (rc == 3) return fail("layer %d: root-finder order code 3 is reserved", l);
-                if (rc > rf_code) rf_code = rc;
-            }
-            if (p != RNF_PREC_FP32 && p != RNF_PREC_F16X2 && p != RNF_PREC_BF16X3) return fail("layer %d: unknown precision %d", l, p);
-            if (pfb != RNF_PREC_FP32 && pfb != RNF_PREC_BF16X3) return fail("layer %d: fallback records must be RNF_PREC_FP32 or RNF_PREC_BF16X3, got %d", l, pfb);
-            if (fb_prec >= 0 && pfb != fb_prec) return fail("layer %d: all fallback records of a flow must share one precision", l);
-            fb_prec = pfb;
-            if (prec >= 0 && p != prec) return fail("layer %d: all MLP layers of a flow must be packed with the same precision", l);
-            prec = p;
-        }
-        a.layers[l] = make_int2(kind | (perm << 4) | ((slot + 1) << 8), d[D_PARAM]);
-    }
-    if (prec < 0) prec = 0;
-    if (fb_prec < 0) fb_prec = 0;
-    {   // bits 16..25 of x: iteration position + 1 of the next layer with an MLP image behind this one (0 = none), in the order the
-        // pass walks the layers -- saves the kernel a dependent chain of scalar loads per layer
-        int nxt = 0;
-        for (int pos = n_layers - 1; pos >= 0; --pos) {
-            const int l = o.dir ? n_layers - 1 - pos : pos;
-            a.layers[l].x |= nxt << 16;
-            if (kind_has_mlp(a.layers[l].x & 15)) nxt = pos + 1;
-        }
-    }
-    if (n_slots > 0) {
-        if (!feat) return fail("this flow consumes a feature vector but feature pointer is null (flow/mobiusflow.py:48-49)");
-        if (F <= 0 || F % 8) return fail("feature_dim=%d must be a positive multiple of 8 (pad on the host)", F);
-    }
-    if (n == 0) {
+    const int cus = device_cus();
+    FlowPlan p;
+    char err[sizeof(g_err)];
+    if (!plan_flow(o, cus, flow_switches(), p, err, sizeof(err))) return fail("%s", err);
+    if (p.empty) {
         if (o.sum_out) { hipLaunchKernelGGL(nll_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double *)nullptr, 0, 0.0, o.sum_out, 0); }
         return 0;
     }
-    const bool shared = o.feature_div > 0 && n_slots > 0;
-    const bool ext_layers = ext;                         // the flow holds a layer kind only the extended instantiation carries
-    if (shared) ext = true;                              // shared feature rows: the extended instantiation, unless a ROWS one fits (below)
-    if (shared && n % o.feature_div) return fail("n=%lld not divisible by feature_div=%lld", (long long)n, (long long)o.feature_div);
-    size_t stash_at;
-    const size_t ws_need = flow_workspace(o, n_slots, any_mlp, &stash_at);
-    const bool stash = ws_need > stash_at;               // overflow stash of the K > 128 inverse, behind everything else
-    if (stash && shared) return fail("inverse pass with segments > 128 is not built for shared feature rows; got %d", K);
-    if (n_slots > 0 || o.sum_out || stash) {
-        if (!ws) return fail("workspace pointer is null");
-        if (ws_bytes < ws_need) return fail("workspace of %zu bytes is smaller than the %zu needed (rnf_flow_pass_workspace_bytes)", ws_bytes, ws_need);
-    }
-    if (stash) a.inv_stash = reinterpret_cast<float4 *>(reinterpret_cast<char *>(ws) + stash_at);
-
-    const int KT = (K + 7) / 8;
-    // inverse: the segment parameters of a layer stay in registers through the root finder; instantiations hold 1, 2, 4, 8 tiles
-    // (8-wave workgroups) or 16 (K <= 128: 4-wave workgroups with the whole register file, fc_last staged in two halves)
-    const int kt_inv = KT <= 1 ? 1 : (KT <= 2 ? 2 : (KT <= 4 ? 4 : (KT <= 8 ? 8 : 16)));
-    // (round 4: inverse passes with more than 64 segments also run for conditional 3x3 / 6x6 layers, side layers and shared feature rows --
-    // flow/mobiusflow.py:7-14 takes any `segments` with any `rot` -- on the extended build of the 4-wave instantiation)
+    const int64_t n = o.n;
+    char *ws = reinterpret_cast<char *>(o.workspace);
     double *partials = reinterpret_cast<double *>(ws);
-    float *G = n_slots ? reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + PARTIALS_BYTES) : nullptr;
-    const int max_tiles = prec == 2 ? Lay<2>::MAX_TILES_IN_LDS : MOB_MAX_TILES_IN_LDS;
-    int tiles_in_lds = any_mlp ? (KT < max_tiles ? KT : max_tiles) : 0;
-    if (any_mlp && tiles_in_lds < min_tiles) tiles_in_lds = min_tiles;
-    size_t lds_bytes = !any_mlp ? 0 : sizeof(float) * (prec == 2 ? (size_t)3 * Mlp<2>::REGION_FLOATS      // three ring regions (flow_kernels.h RING)
-                                                                  : MOB_HEAD_FLOATS + (size_t)tiles_in_lds * MOB_LAST_TILE_FLOATS);
-    if (lds_bytes < NW_FWD_WIDE * sizeof(double) * 2) lds_bytes = NW_FWD_WIDE * sizeof(double) * 2;
-    {   // SIMD fairness governor (flow_kernels.h struct Fair): forward split-precision kernel; RNF_FAIR=0 switches it off
-        static int fair = -1;
-        if (fair < 0) { const char *e = std::getenv("RNF_FAIR"); fair = (e && e[0] == '0') ? 0 : 1; }
-        a.fair_off = -1;
-        if (fair && any_mlp && o.dir == 0 && prec == 1) {
-            a.fair_off = (int)(lds_bytes / sizeof(float));
-            lds_bytes += 64;
-        }
-    }
-    const int cus = device_cus();
-    const long long chunk_cap = (n_slots && !shared) ? CHUNK_SAMPLES : n;      // shared feature rows: the projection scratch is tiny
-    const long long feat_rows = shared ? n / o.feature_div : 0;
-    a.g_div = shared ? o.feature_div : 0;
-    a.g_rows = feat_rows;
+    float *G = p.n_slots ? reinterpret_cast<float *>(ws + PARTIALS_BYTES) : nullptr;
+    int *guard = p.guarded ? reinterpret_cast<int *>(partials + GUARD_AT) : nullptr;
 
-    a.blob = blob;
+    FlowArgs a;
+    std::memset(&a, 0, sizeof(a));
+    std::memcpy(a.layers, p.layers, sizeof(LayerEntry) * p.n_layers);
+    a.blob = o.blob;
 #ifdef RNF_STAMPS
     {   // diagnostic build: RNF_STAMPS_PTR=<device address of 8 zeroed uint64> (set by tools/phase_stamps.py)
         const char *sp = std::getenv("RNF_STAMPS_PTR");
         a.stamps = sp ? reinterpret_cast<unsigned long long *>(std::strtoull(sp, nullptr, 0)) : nullptr;
     }
 #endif
-    a.n_layers = n_layers;
-    a.KT = KT;
-    a.K = K;
-    a.min_wsum = kMinWeightSum * (float)K;
-    {   // Root finder of the inverse pass: order of its FIRST pass (flow_kernels.h mobius_inv_finish).  Third order (Halley) unless the flow
-        // asks for the fourth-order first pass -- bits 16..17 of desc column 5 on its Moebius layers (1: third, 2: fourth; 0: this default).
-        // The fourth order pays on sharply peaked conditioner outputs (a trained p(R | image): the third-order iteration then needs a third
-        // pass for most waves; trained_c4 10.02 -> 9.66 ms) and costs mild weights its four extra instructions per segment pair (BASELINE's
-        // synthetic C5q +4 %, C5 +0.9 %: profiles/r6/ab_centre.jsonl), so it is a property of the FLOW its owner sets (Flow.set_rootfinder_order,
-        // the checkpoint sidecar) -- one value per flow, never per launch.  RNF_RF_FIRST=3|4 forces one.
-        static int forced = -1;
-        if (forced < 0) { const char *e = std::getenv("RNF_RF_FIRST"); forced = e ? (e[0] == '4' ? 4 : (e[0] == '3' ? 3 : 0)) : 0; }
-        a.rf_first4 = forced ? (forced == 4) : (rf_code == 2);
-    }
+    a.n_layers = p.n_layers;
+    a.KT = p.KT;
+    a.K = p.K;
+    a.min_wsum = kMinWeightSum * (float)p.K;
+    a.rf_first4 = p.rf_first4;
+    a.tab_off = p.tab_off;
+    a.g_div = p.shared ? o.feature_div : 0;
+    a.g_rows = p.feat_rows;
+    a.G = G;
     a.side = o.side;
     a.side_n = n;
     a.states = o.states;
@@ -968,212 +737,70 @@ static int run_flow(const RnfFlowPass &o) {
     a.fisher_A = o.fisher_A;
     a.fisher_c = o.fisher_c;
     a.fisher_div = o.fisher_A ? n / o.fisher_B : 1;
-
-    const bool pipe = staging_dma() && KT <= MOB_MAX_TILES_IN_LDS && prec != 2;     // bf16x3: a K = 64 layer image is 171 KiB (layout.h Lay<2>): synchronous staging
-    a.tab_off = -1;
-    if ((pipe || prec == 2) && any_mlp) {                      // two LDS buffers for the blocks of constant-affine layers (flow_kernels.h stage_table)
-        lds_bytes = (lds_bytes + 15) / 16 * 16;
-        a.tab_off = (int)(lds_bytes / sizeof(float));
-        lds_bytes += sizeof(float) * 2 * AFF_TABLE_LDS_STRIDE;
+    a.guard = guard;
+    a.guard_mode = p.guarded ? 1 : 0;
+    if (p.ws_need > p.stash_at) a.inv_stash = reinterpret_cast<float4 *>(ws + p.stash_at);
+    if (p.fused) {
+        a.pa_off = p.pa_off;
+        a.feat_F = p.F;
+        a.feat_base = p.feat_off[0];
+        a.feat_stride = p.feat_stride;
     }
-    const int fair_off = a.fair_off;
-    // guarded split-precision call: every chunk is followed by the exact-fp32 kernels, which return at once unless the chunk's guard fired
-    // (an in-place call -- rotation_out == rotation -- cannot be re-run from its own overwritten input: it runs unguarded, on the kernel
-    // instantiations whose softplus is overflow-safe on its own; include/rnf_hip.h "aliasing")
-    const bool guarded = prec == 1 && any_mlp && have_fb && ws && ws_bytes >= PARTIALS_BYTES && guard_allowed() && !(rot_out && rot_out == rot);
-    int *guard = guarded ? reinterpret_cast<int *>(reinterpret_cast<double *>(ws) + GUARD_AT) : nullptr;
-    // FUSED: forward pass of a conditional flow whose every MLP layer is conditional, F <= 256, projection records equally spaced in the
-    // blob (both packers lay them out that way).  Guarded launches only: the instantiation uses the one-piece softplus.
-    bool fused = fused_allowed() && lean2 && o.dir == 0 && prec == 1 && pipe && any_mlp && n_slots > 0 && all_mlp_cond && !shared && !ext && !o.states &&
-                 F <= FUSED_MAX_F && guarded && a.tab_off >= 0;
-    int feat_stride = (int)((featproj_packed_floats(F) + 3) / 4 * 4);
-    if (fused && n_slots > 1) feat_stride = fp_primary[1] - fp_primary[0];
-    for (int sl = 0; fused && sl < n_slots; ++sl)
-        if (fp_primary[sl] != fp_primary[0] + sl * feat_stride) fused = false;
-    size_t lds_fused = 0;
-    if (fused) {
-        lds_fused = (lds_bytes + 15) / 16 * 16;
-        a.pa_off = (int)(lds_fused / sizeof(float));
-        lds_fused += sizeof(float) * FUSED_PA_FLOATS;
-        a.feat_F = F;
-        a.feat_base = fp_primary[0];
-        a.feat_stride = feat_stride;
-        if (lds_fused > 160 * 1024) fused = false;
+    FlowArgs b;                                            // the same call on the fallback records (guarded calls)
+    if (p.guarded) {
+        b = a;
+        for (int l = 0; l < p.n_layers; ++l)
+            if (kind_has_mlp(b.layers[l].x & 15)) b.layers[l].y = p.param_fb[l];
+        b.tab_off = p.tab_off_fb;
+        b.guard_mode = 2;
+        b.fair_off = -1;
     }
-    FlowArgs afb;
-    if (guarded) {
-        HIP_TRY(hipMemsetAsync(guard, 0, 2 * sizeof(int), stream));
-        afb = a;
-        for (int l = 0; l < n_layers; ++l)
-            if (kind_has_mlp(afb.layers[l].x & 15)) afb.layers[l].y = fbp[l];
-    }
-    // Shared feature rows on the fast kernels (round 5; pose estimation: agent.py:238-263 evaluates number_queries rotations per image
-    // feature): rows of >= 32 rotations, guarded split-precision call with DMA staging, and either a forward pass of the conditional-lean
-    // structure (SYMSOL-I: Condition16Trans + conditional Moebius + constant affine) or an inverse pass with K <= 64 segments of a flow
-    // without extended layers.  Decided by the flow and the call's row length, never by the batch size.  Everything else with shared rows
-    // stays on the extended instantiation.
-    const bool rows_lean2 = lean2 && all_mlp_cond && guarded && a.tab_off >= 0;
-    // GUARDED calls only, in both directions: the row records enter x0 through a matrix step (flow_kernels.h GFragRows), where a non-finite
-    // record of one image would also poison the rotations of the NEXT image that share its wave (NaN x 0 = NaN); the guard sees that and the
-    // exact-fp32 re-run, which reads the records per lane, restores per-image semantics.  Unguarded calls keep the extended instantiation.
-    const bool rows_fast = shared && !ext_layers && prec == 1 && pipe && any_mlp && o.feature_div >= 32 && n < (1LL << 31) &&
-                           feat_rows < (1LL << 24) && !o.states && guarded && (o.dir == 0 ? rows_lean2 : (KT <= 8));
-    if (rows_fast) ext = false;
-    bool first = true;
-    for (long long base = 0; base < n; base += chunk_cap) {
-        const long long cn = (n - base) < chunk_cap ? (n - base) : chunk_cap;
-        // waves per workgroup of the stack kernel: the forward split-precision kernel goes 16 wide once 8-wave workgroups would
-        // no longer fit the CUs in one round
-        const bool wide = !fused && o.dir == 0 && prec == 1 && pipe && !ext && wide_allowed() && cn > (long long)cus * NW_FWD_H * 32;
-        const bool narrow = !fused && o.dir == 0 && prec == 1 && pipe && !ext && wide_allowed() && cn <= (long long)cus * NW_FWD_NARROW * 32;
-        const bool big_inv = o.dir == 1 && any_mlp && KT > 8;                  // 4-wave instantiation (512 registers per lane)
-        const bool narrow_inv = o.dir == 1 && prec == 1 && pipe && !ext && any_mlp && KT <= 8 && wide_allowed() && cn <= (long long)cus * NW_FWD_NARROW * 32;
-        const int nwk = fused ? NW_FUSED : (big_inv ? NW_INV_BIG : (wide ? NW_FWD_WIDE : ((narrow || narrow_inv) ? NW_FWD_NARROW : ((o.dir == 0 && prec == 1) ? NW_FWD_H : NW))));
-        // kernel family of this call (launch_stack): fixed by the flow and by `guarded`, the same for every chunk and batch size
-        const int family = (guarded && a.tab_off >= 0 && o.dir == 0 && prec == 1 && pipe && !ext) ? (lean ? 1 : (lean2 && all_mlp_cond && n_slots > 0 && (!shared || rows_fast) ? 2 : 0)) : 0;
-        a.fair_off = (wide || narrow || family || (fused && NW_FUSED != 8)) ? -1 : fair_off;             // the governor pairs two waves per SIMD (general 8-wave kernel)
-        const long long ntiles = (cn + nwk * 32 - 1) / (nwk * 32);
-        const long long ntiles_fp = (cn + NW_FP * 32 - 1) / (NW_FP * 32);
-        const int nw_fb = (o.dir == 1 && any_mlp && KT > 8) ? NW_INV_BIG : NW;
-        const long long ntiles_fb = (cn + nw_fb * 32 - 1) / (nw_fb * 32);         // the exact-fp32 re-run uses NW-wave workgroups
-        long long groups = (ntiles * nwk > ntiles_fp * NW_FP) ? ntiles * nwk : ntiles_fp * NW_FP;
-        if (guarded && ntiles_fb * nw_fb > groups) groups = ntiles_fb * nw_fb;
-        if ((cn + 127) / 128 * 4 > groups) groups = (cn + 127) / 128 * 4;
-        if (guarded && base > 0) HIP_TRY(hipMemsetAsync(guard, 0, sizeof(int), stream));   // per-chunk guard; guard[1] stays
-        int grid = (int)(ntiles < cus ? ntiles : cus);
-        const int cus_fp = cus * (8 / NW_FP);
-        const int grid_fp = (int)(ntiles_fp < cus_fp ? ntiles_fp : cus_fp);
-        // feature projection of this chunk (shared rows: ONE projection of the feature rows, before the first chunk); `fb`: the
-        // exact-fp32 projection of a guarded call, which runs only if the guard fired (every chunk, also with shared rows)
-        auto project = [&](bool fb) -> int {
-            const long long pn = shared ? feat_rows : cn;
-            const long long pt = (pn + NW_FP * 32 - 1) / (NW_FP * 32);
-            const int grid_p = shared ? (int)(pt < cus_fp ? pt : cus_fp) : grid_fp;
-            fp.feat = shared ? feat : feat + base * F;
-            fp.blob = blob;
-            fp.G = G;
-            fp.n = pn;
-            fp.g_groups = groups;
-            fp.F = F;
-            fp.n_slots = n_slots;
-            fp.row_mode = shared ? 1 : 0;
-            fp.only_if = fb ? guard : nullptr;
-            if (fb) for (int sl = 0; sl < n_slots; ++sl) fp.feat_off[sl] = fbf[sl];
-            const int pprec = (fb || prec == 2) ? 0 : prec;       // bf16x3 flows: the exact-fp32 projection (their records hold the fp32 image)
-            const int kchunk = F < FP_KCHUNK ? F : FP_KCHUNK;
-            size_t fl = sizeof(float) * (pprec ? (size_t)2 * (FP_KCHUNK / 16) * 512 : (size_t)kchunk / 8 * 256);   // f16x2: two DMA buffers
-            if (pprec && F > FP_KCHUNK && F <= 2 * FP_KCHUNK) {     // K split over wave pairs: no partial sums through the scratch (featproj_kernel.h)
-                const long long pt2 = (pn + 127) / 128;
-                const int grid2 = (int)(pt2 < cus ? pt2 : cus);
-                auto kern = featproj_ksplit_kernel;
-                HIP_TRY(allow_lds(kern, FP2_LDS_BYTES));
-                hipLaunchKernelGGL(kern, dim3(grid2), dim3(8 * 64), FP2_LDS_BYTES, stream, fp);
-            } else if (pprec && F > FP_KCHUNK) {                    // F > 512: K-chunks whose partial sums pass through the scratch
-                auto kern = featproj_kernel<NW_FP, 1, true>;
-                HIP_TRY(allow_lds(kern, fl));
-                hipLaunchKernelGGL(kern, dim3(grid_p), dim3(NW_FP * 64), fl, stream, fp);
-            } else if (pprec) {
-                auto kern = featproj_kernel<NW_FP, 1>;
-                HIP_TRY(allow_lds(kern, fl));
-                hipLaunchKernelGGL(kern, dim3(grid_p), dim3(NW_FP * 64), fl, stream, fp);
-            } else {
-                auto kern = featproj_kernel<NW_FP, 0>;
-                HIP_TRY(allow_lds(kern, fl));
-                hipLaunchKernelGGL(kern, dim3(grid_p), dim3(NW_FP * 64), fl, stream, fp);
-            }
+    if (p.fused) a.stash = G;                              // grid * 8 waves * 8 KB <= the projection scratch the workspace is sized for
+    FeatProjArgs fp;
+    std::memset(&fp, 0, sizeof(fp));
+    fp.blob = o.blob;
+    fp.G = G;
+    fp.F = p.F;
+    fp.n_slots = p.n_slots;
+    fp.row_mode = p.shared ? 1 : 0;
+    return for_each_launch(p, cus, n, o.sum_out != nullptr, [&](const Launch &l) -> int {
+        const ChunkPlan &c = l.chunk;
+        switch (l.kind) {
+        case LAUNCH_GUARD_RESET:                           // guard[1] (a re-run happened in this call) stays across the chunks
+            HIP_TRY(hipMemsetAsync(guard, 0, (l.base ? 1 : 2) * sizeof(int), stream));
+            return 0;
+        case LAUNCH_PROJECTION: {
+            const ProjPlan j = plan_projection(p, cus, l.cn, l.fb);
+            fp.feat = p.shared ? o.feature : o.feature + l.base * p.F;
+            fp.n = j.rows;
+            fp.g_groups = c.groups;
+            fp.only_if = l.fb ? guard : nullptr;
+            std::memcpy(fp.feat_off, l.fb ? p.feat_off_fb : p.feat_off, sizeof(int) * p.n_slots);
+            return launch_projection(j, fp, stream);
+        }
+        case LAUNCH_STACK: {
+            FlowArgs &x = l.fb ? b : a;
+            x.rot_in = o.rotation + l.base * 9;
+            x.rot_out = o.rotation_out ? o.rotation_out + l.base * 9 : nullptr;
+            x.ldj_out = o.ldj_out ? o.ldj_out + l.base : nullptr;
+            x.logp_out = o.logp_out ? o.logp_out + l.base : nullptr;
+            x.partials = o.sum_out ? partials + (l.fb ? PARTIALS_FB_AT : 0) : nullptr;
+            x.n = l.cn;
+            x.sample_base = l.base;
+            x.g_groups = c.groups;
+            if (l.fb) return launch_stack(fallback_key(p), b, c.grid_fb, p.lds_fb, stream);
+            a.feat = p.fused ? o.feature + l.base * p.F : nullptr;
+            a.fair_off = c.fair_off;
+            return launch_stack(stack_key(p, c), a, c.grid, p.lds_bytes, stream);
+        }
+        case LAUNCH_FINALIZE:
+            hipLaunchKernelGGL(nll_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double *)partials, c.grid, (double)l.cn, o.sum_out, l.base == 0 ? 0 : 1,
+                               (const double *)(partials + PARTIALS_FB_AT), c.grid_fb, (const int *)guard);
             HIP_TRY(hipGetLastError());
             return 0;
-        };
-        if (n_slots && !fused && (!shared || base == 0)) {
-            if (int rc = project(false)) return rc;
         }
-        a.rot_in = rot + base * 9;
-        a.G = G;
-        a.rot_out = rot_out ? rot_out + base * 9 : nullptr;
-        a.ldj_out = ldj_out ? ldj_out + base : nullptr;
-        a.logp_out = o.logp_out ? o.logp_out + base : nullptr;
-        a.partials = o.sum_out ? partials : nullptr;
-        a.n = cn;
-        a.sample_base = base;
-        a.g_groups = groups;
-        a.guard = guard;
-        a.guard_mode = guarded ? 1 : 0;
-        int rc;
-        const bool rows_now = rows_fast;                   // (the exact-fp32 re-run below shadows it: shared rows there stay on the extended kernels)
-#define RNF_LAUNCH(DIR_, KT_)                                                                                   \
-    prec == 2 ? (ext ? launch_stack<DIR_, KT_, false, 2, true>(a, grid, lds_bytes, stream, nwk)                     \
-                     : launch_stack<DIR_, KT_, false, 2>(a, grid, lds_bytes, stream, nwk)) :                        \
-    rows_now ? launch_stack<DIR_, KT_, true, 1, false, true>(a, grid, lds_bytes, stream, nwk, family) :             \
-    ext ? (pipe ? (prec ? launch_stack<DIR_, KT_, true, 1, true>(a, grid, lds_bytes, stream, nwk)                   \
-                        : launch_stack<DIR_, KT_, true, 0, true>(a, grid, lds_bytes, stream, nwk))                  \
-                : (prec ? launch_stack<DIR_, KT_, false, 1, true>(a, grid, lds_bytes, stream, nwk)                  \
-                        : launch_stack<DIR_, KT_, false, 0, true>(a, grid, lds_bytes, stream, nwk))) :              \
-    (pipe ? (prec ? launch_stack<DIR_, KT_, true, 1>(a, grid, lds_bytes, stream, nwk, family)                        \
-                  : launch_stack<DIR_, KT_, true, 0>(a, grid, lds_bytes, stream, nwk))                              \
-          : (prec ? launch_stack<DIR_, KT_, false, 1>(a, grid, lds_bytes, stream, nwk)                              \
-                  : launch_stack<DIR_, KT_, false, 0>(a, grid, lds_bytes, stream, nwk)))
-        if (fused) {
-            a.feat = feat + base * F;
-            a.stash = G;                                   // grid * 8 waves * 8 KB <= the projection scratch the workspace is sized for
-            rc = launch_fused(a, grid, lds_fused, stream);
-        }
-        else if (o.dir == 0) rc = RNF_LAUNCH(0, 0);
-        else if (kt_inv == 1) rc = RNF_LAUNCH(1, 1);
-        else if (kt_inv == 2) rc = RNF_LAUNCH(1, 2);
-        else if (kt_inv == 4) rc = RNF_LAUNCH(1, 4);
-        else if (kt_inv == 8) rc = RNF_LAUNCH(1, 8);
-        else if (prec == 2) rc = ext ? launch_big_inverse<2, true>(a, grid, lds_bytes, stream) : launch_big_inverse<2>(a, grid, lds_bytes, stream);
-        else rc = ext ? (prec ? launch_big_inverse<1, true>(a, grid, lds_bytes, stream) : launch_big_inverse<0, true>(a, grid, lds_bytes, stream))
-                      : (prec ? launch_big_inverse<1>(a, grid, lds_bytes, stream) : launch_big_inverse<0>(a, grid, lds_bytes, stream));
-        if (rc) return rc;
-        int grid_fb = 0;
-        if (guarded) {                                   // the same chunk on the exact-fp32 kernels, skipped on the device unless the guard fired
-            if (n_slots) {
-                if (int rc2 = project(true)) return rc2;
-                for (int sl = 0; sl < n_slots; ++sl) fp.feat_off[sl] = fp_primary[sl];
-            }
-            FlowArgs b = afb;
-            b.rot_in = a.rot_in; b.G = a.G; b.rot_out = a.rot_out; b.ldj_out = a.ldj_out; b.logp_out = a.logp_out;
-            b.partials = a.partials ? partials + PARTIALS_FB_AT : nullptr;
-            b.n = cn; b.sample_base = base; b.g_groups = groups; b.guard = guard; b.guard_mode = 2; b.fair_off = -1;
-            grid_fb = (int)(ntiles_fb < cus ? ntiles_fb : cus);
-            const int grid_keep = grid;
-            const bool ext_fb = ext || shared;            // shared rows: the exact-fp32 re-run reads them on the extended instantiation
-            {
-                FlowArgs &a = b;                          // RNF_LAUNCH names `a`, `grid`, `prec`, `nwk`, `ext`, `rows_now`, `lds_bytes`
-                const int grid = grid_fb, prec = fb_prec, nwk = NW;
-                const bool ext = ext_fb, rows_now = false;
-                const int family = 0;                     // the strict kernels have no lean family
-                (void)family;
-                // bf16x3 fallback records (round 6: the guard's re-run target on host-packed flows -- 1.8x the guarded time instead of the
-                // 3.3x of the exact-fp32 MFMA): the ring-staged kernels with their own LDS layout (three regions + the affine blocks)
-                size_t lds_fb = lds_bytes;
-                if (fb_prec == 2) {
-                    lds_fb = sizeof(float) * (size_t)3 * Mlp<2>::REGION_FLOATS;
-                    a.tab_off = (int)(lds_fb / sizeof(float));
-                    lds_fb += sizeof(float) * 2 * AFF_TABLE_LDS_STRIDE;
-                }
-                const size_t lds_bytes = lds_fb;
-                if (o.dir == 0) rc = RNF_LAUNCH(0, 0);
-                else if (kt_inv == 1) rc = RNF_LAUNCH(1, 1);
-                else if (kt_inv == 2) rc = RNF_LAUNCH(1, 2);
-                else if (kt_inv == 4) rc = RNF_LAUNCH(1, 4);
-                else if (kt_inv == 8) rc = RNF_LAUNCH(1, 8);
-                else if (prec == 2) rc = ext ? launch_big_inverse<2, true>(a, grid, lds_bytes, stream) : launch_big_inverse<2>(a, grid, lds_bytes, stream);
-                else rc = ext ? launch_big_inverse<0, true>(a, grid, lds_bytes, stream) : launch_big_inverse<0>(a, grid, lds_bytes, stream);
-            }
-            (void)grid_keep;
-            if (rc) return rc;
-        }
-#undef RNF_LAUNCH
-        if (o.sum_out) {
-            hipLaunchKernelGGL(nll_finalize_kernel, dim3(1), dim3(256), 0, stream, (const double *)partials, grid, (double)cn, o.sum_out, first ? 0 : 1,
-                               (const double *)(partials + PARTIALS_FB_AT), grid_fb, (const int *)guard);
-            HIP_TRY(hipGetLastError());
-        }
-        first = false;
-    }
-    return 0;
+        return 0;
+    });
 }
 
 extern "C" int rnf_flow_pass(const RnfFlowPass *p) {
@@ -1196,15 +823,11 @@ extern "C" size_t rnf_flow_pass_workspace_bytes(const RnfFlowPass *p) {
         fail("RnfFlowPass.struct_bytes does not match the library's %zu", sizeof(RnfFlowPass));
         return 0;
     }
-    int n_slots = 0;                                     // counted as run_flow counts them
-    bool any_mlp = false;
-    for (int l = 0; p->desc && l < p->n_layers && l < MAX_LAYERS; ++l) {
-        const int32_t *d = p->desc + (size_t)l * D_STRIDE;
-        if (d[D_SLOT] + 1 > n_slots) n_slots = d[D_SLOT] + 1;
-        any_mlp = any_mlp || kind_has_mlp(d[D_KIND]);
-    }
+    int n_slots;
+    bool any_mlp;
+    desc_slots(p->desc, p->n_layers, &n_slots, &any_mlp);
     size_t stash_at;
-    return flow_workspace(*p, n_slots, any_mlp, &stash_at);
+    return flow_workspace(*p, n_slots, any_mlp, needs_stash(*p, any_mlp) ? device_cus() : 0, &stash_at);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1294,38 +917,11 @@ extern "C" int rnf_cond_mlp_forward(const float *feat, int64_t n, int32_t F, con
         std::memset(&fp, 0, sizeof(fp));
         fp.feat = feat + base * F; fp.blob = blob; fp.G = G; fp.n = cn; fp.g_groups = groups; fp.F = F; fp.n_slots = 1; fp.row_mode = 0;
         fp.feat_off[0] = feat_off;
-        const int cus_fp = cus * (8 / NW_FP);
-        const int grid_fp = (int)(ntiles_fp < cus_fp ? ntiles_fp : cus_fp);
-        const int kchunk = F < FP_KCHUNK ? F : FP_KCHUNK;
-        const size_t fl = sizeof(float) * (prec == RNF_PREC_F16X2 ? (size_t)2 * (FP_KCHUNK / 16) * 512 : (size_t)kchunk / 8 * 256);
         const int grid = (int)(ntiles < cus ? ntiles : cus);
-        if (prec == RNF_PREC_F16X2) {
-            if (F > FP_KCHUNK && F <= 2 * FP_KCHUNK) {
-                const long long pt2 = (cn + 127) / 128;
-                auto kp = featproj_ksplit_kernel;
-                HIP_TRY(allow_lds(kp, FP2_LDS_BYTES));
-                hipLaunchKernelGGL(kp, dim3((int)(pt2 < cus ? pt2 : cus)), dim3(8 * 64), FP2_LDS_BYTES, stream, fp);
-            } else if (F > FP_KCHUNK) {
-                auto kp = featproj_kernel<NW_FP, 1, true>;
-                HIP_TRY(allow_lds(kp, fl));
-                hipLaunchKernelGGL(kp, dim3(grid_fp), dim3(NW_FP * 64), fl, stream, fp);
-            } else {
-                auto kp = featproj_kernel<NW_FP, 1>;
-                HIP_TRY(allow_lds(kp, fl));
-                hipLaunchKernelGGL(kp, dim3(grid_fp), dim3(NW_FP * 64), fl, stream, fp);
-            }
-            auto kern = cond_mlp_kernel<NW, 1>;
-            HIP_TRY(allow_lds(kern, lds_bytes));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, (const float *)G, groups, cn, blob + layer_off, out + base * 16);
-        } else {                                                // exact fp32 and bf16x3: the exact-fp32 projection (as the flow pass projects)
-            auto kp = featproj_kernel<NW_FP, 0>;
-            HIP_TRY(allow_lds(kp, fl));
-            hipLaunchKernelGGL(kp, dim3(grid_fp), dim3(NW_FP * 64), fl, stream, fp);
-            auto kern = prec == RNF_PREC_BF16X3 ? cond_mlp_kernel<NW, 2> : cond_mlp_kernel<NW, 0>;
-            HIP_TRY(allow_lds(kern, lds_bytes));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, stream, (const float *)G, groups, cn, blob + layer_off, out + base * 16);
-        }
-        HIP_TRY(hipGetLastError());
+        // exact fp32 and bf16x3: the exact-fp32 projection (as the flow pass projects)
+        if (int rc = launch_projection(plan_projection_rows(cn, F, prec == RNF_PREC_F16X2 ? 1 : 0, cus), fp, stream)) return rc;
+        auto kern = prec == RNF_PREC_BF16X3 ? cond_mlp_kernel<NW, 2> : (prec ? cond_mlp_kernel<NW, 1> : cond_mlp_kernel<NW, 0>);
+        if (int rc = launch(kern, grid, NW * 64, lds_bytes, stream, (const float *)G, groups, cn, blob + layer_off, out + base * 16)) return rc;
     }
     return 0;
 }
@@ -1571,17 +1167,7 @@ extern "C" int rnf_flow_forward_train_plain(const float *rot, const float *feat,
     const long long nblocks = (n + b16::SB - 1) / b16::SB;
     const long long cap = (long long)device_cus() * 4;
     const dim3 grid((unsigned)(nblocks < cap ? nblocks : cap)), block(b16::WAVES * 64);
-    if (F) {
-        auto kern = b16::flow_train_forward16_kernel<true>;
-        HIP_TRY(allow_lds(kern, lds_bytes));
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, a);
-    } else {
-        auto kern = b16::flow_train_forward16_kernel<false>;
-        HIP_TRY(allow_lds(kern, lds_bytes));
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(F ? b16::flow_train_forward16_kernel<true> : b16::flow_train_forward16_kernel<false>, (int)grid.x, (int)block.x, lds_bytes, stream, a);
 }
 
 extern "C" int rnf_pack_flow_device(const float *plain, const int32_t *pdesc, int32_t n_layers, int32_t K, int32_t F, int32_t prec,
@@ -1713,31 +1299,16 @@ static int run_backward(const RnfFlowBackward &x, const float *g_out_ext = nullp
             const long long nblocks = (n + b16::SB - 1) / b16::SB;
             const long long cap = (long long)device_cus() * 4;
             const dim3 grid((unsigned)(nblocks < cap ? nblocks : cap)), block(b16::WAVES * 64);
-            auto launch16 = [&](auto kern) -> int {
-                HIP_TRY(allow_lds(kern, lds_bytes));
-                hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, a);
-                return 0;
-            };
-            int rc;
-            if (F) rc = rare ? launch16(b16::flow_train_backward16_kernel<true, true>) : launch16(b16::flow_train_backward16_kernel<true, false>);
-            else rc = rare ? launch16(b16::flow_train_backward16_kernel<false, true>) : launch16(b16::flow_train_backward16_kernel<false, false>);
-            if (rc) return rc;
+            auto kern = F ? (rare ? b16::flow_train_backward16_kernel<true, true> : b16::flow_train_backward16_kernel<true, false>)
+                          : (rare ? b16::flow_train_backward16_kernel<false, true> : b16::flow_train_backward16_kernel<false, false>);
+            if (int rc = launch(kern, (int)grid.x, (int)block.x, lds_bytes, stream, a)) return rc;
         } else {
             const size_t lds_bytes = sizeof(float) * (TR_LDS_HEAD_FLOATS + rows * LROW);
             const long long nblocks = (n + 63) / 64;
             const int cap = device_cus() * 4;
             const dim3 grid((unsigned)(nblocks < cap ? nblocks : cap)), block(TR_WAVES * 64);
-            if (F) {
-                auto kern = flow_train_backward_kernel<true>;
-                HIP_TRY(allow_lds(kern, lds_bytes));
-                hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, a);
-            } else {
-                auto kern = flow_train_backward_kernel<false>;
-                HIP_TRY(allow_lds(kern, lds_bytes));
-                hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, a);
-            }
+            if (int rc = launch(F ? flow_train_backward_kernel<true> : flow_train_backward_kernel<false>, (int)grid.x, (int)block.x, lds_bytes, stream, a)) return rc;
         }
-        HIP_TRY(hipGetLastError());
         if (a.n_layers) {
             hipLaunchKernelGGL(affine_logdet_grad_kernel, dim3((a.n_layers + 63) / 64), dim3(64), 0, stream, a);
             HIP_TRY(hipGetLastError());
@@ -2294,19 +1865,6 @@ extern "C" int rnf_conditioner_forward(const float *y, int64_t n, const float *l
     const size_t lds_bytes = sizeof(float) * (prec == RNF_PREC_BF16X3 ? B3Head::HEAD_TILE_FLOATS : MOB_HEAD_FLOATS + MOB_LAST_TILE_FLOATS);
     long long ntiles = (n + NW * 32 - 1) / (NW * 32);
     int grid = (int)(ntiles < device_cus() ? ntiles : device_cus());
-    if (prec == RNF_PREC_BF16X3) {
-        auto kern = conditioner_kernel<NW, 2>;
-        HIP_TRY(allow_lds(kern, lds_bytes));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);
-    } else if (prec) {
-        auto kern = conditioner_kernel<NW, 1>;
-        HIP_TRY(allow_lds(kern, lds_bytes));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);
-    } else {
-        auto kern = conditioner_kernel<NW, 0>;
-        HIP_TRY(allow_lds(kern, lds_bytes));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    auto kern = prec == RNF_PREC_BF16X3 ? conditioner_kernel<NW, 2> : (prec ? conditioner_kernel<NW, 1> : conditioner_kernel<NW, 0>);
+    return launch(kern, grid, NW * 64, lds_bytes, reinterpret_cast<hipStream_t>(stream), y, (long long)n, layer, (K + 7) / 8, K, out);
 }
