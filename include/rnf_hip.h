@@ -466,8 +466,11 @@ int rnf_fisher_log_const(const float *A_dev, int64_t B, float *c_out_dev, void *
 /* The same for either closed-form normaliser approximation of matrix_fisher_norm_N (utils/fisher.py:79-97):
  *   norm_type 1 (default): 1/sqrt(8 pi (s0+s1)(s1+s2)(s0+s2));
  *   norm_type 0: (1 + Q/6 + s0 s1 s2/6)/exp(s0+s1+s2), where the reference's `(S**2).sum()` has no `dim`: Q runs over ALL B matrices of
- *   the call (batch-coupled, reproduced as is).  Types 2 (Monte-Carlo over pytorch3d random rotations) and 3 (scipy ODE; indexes rows
- *   of the [B,3] tensor) are refused.  scratch_dev: rnf_fisher_scratch_bytes(B) bytes of device memory (16 suffice here). */
+ *   the call (batch-coupled, reproduced as is);
+ *   RNF_FISHER_NORM_EXACT (3): the exact integral that the reference's type 3 means (its scipy ODE indexes rows of the [B,3] tensor and
+ *   serves no batch), evaluated per row by rnf_fisher_exact's kernel; needs no scratch.
+ *   Type 2 (Monte-Carlo, below) is refused here.  scratch_dev: rnf_fisher_scratch_bytes(B) bytes of device memory (16 suffice here). */
+#define RNF_FISHER_NORM_EXACT 3
 size_t rnf_fisher_scratch_bytes(int64_t B);
 /* norm_type 2 (utils/fisher.py:98-101): Monte-Carlo normaliser over approx_num uniform rotations for ONE matrix (B must be 1: the
  * reference broadcasts [approx_num,3,3] against [N,3,3]); counter-based Philox stream keyed by `seed` (statistical parity with the
@@ -477,10 +480,23 @@ int rnf_fisher_log_const_mc(const float *A_dev, int64_t B, int64_t approx_num, u
 int rnf_fisher_log_const_nt(const float *A_dev, int64_t B, int32_t norm_type, void *scratch_dev, size_t scratch_bytes,
                             float *c_out_dev, void *stream);
 
+/* The exact log-normaliser of the matrix-Fisher density w.r.t. the Haar probability measure, and its derivative: with the proper singular
+ * values s0 >= s1 >= |s2| of A,
+ *   c(A) = s0+s1+s2 + log int_{-1}^{1} 1/2 i0e(1/2 (s0-s1)(1-u)) i0e(1/2 (s0+s1)(1+u)) exp(-(s1+s2)(1-u)) du,   dc/dA = U diag(dc/ds) V^T = E[R]
+ * (i0e(x) = exp(-x) I0(x)), by a fixed 224-node Gauss-Legendre rule in fp64, one wave per matrix (csrc/fisher_exact.h).  Finite and smooth
+ * for every finite A (A = 0: c = 0, E[R] = 0); a row's result is bit-identical whatever B and the row's position.  c_out_dev float[B],
+ * mean_out_dev float[B][9] row-major; either may be NULL, not both.  B = 0 is a no-op.  Stream-ordered, no host synchronisation,
+ * capturable in a HIP graph. */
+int rnf_fisher_exact(const float *A_dev, int64_t B, float *c_out_dev, float *mean_out_dev, void *stream);
+/* The entropy c - tr(A^T E[R]) of MF(A[b]) from the same kernel, summed in fp64 in a form without the cancellation of c against
+ * tr(A^T E[R]) (both ~ |s|, which the fp32 outputs of rnf_fisher_exact cannot carry).  entropy_out_dev float[B]. */
+int rnf_fisher_entropy(const float *A_dev, int64_t B, float *entropy_out_dev, void *stream);
+
 /* Gradient of MatrixFisherN._log_prob w.r.t. A (agent.py:57-65 keeps a network-predicted A in the autograd graph; the reference
  * differentiates torch.svd, utils/fisher.py:67-76,217-232):  g_A[b] = sum_i g_logp[i] R_i - (sum_i g_logp[i]) dc/dA_b over the n/B
  * samples of row b, dc/dA = U' diag(dc/ds) V'^T on the proper SVD (csrc/fisher_math.h), plus the batch coupling of norm_type 0.
- * rotation_dev float[n][9], g_A_dev float[B][9] (overwritten), scratch_dev: rnf_fisher_scratch_bytes(B) bytes.  fp64 accumulation. */
+ * rotation_dev float[n][9], g_A_dev float[B][9] (overwritten), scratch_dev: rnf_fisher_scratch_bytes(B) bytes.  fp64 accumulation.
+ * norm_type 0, 1 or RNF_FISHER_NORM_EXACT (dc/dA = E[R], smooth at repeated and cancelling singular values). */
 int rnf_fisher_log_prob_backward_param(const float *g_logp_dev, const float *rotation_dev, int64_t n, const float *A_dev, int64_t B,
                                    int32_t norm_type, void *scratch_dev, size_t scratch_bytes, float *g_A_dev, void *stream);
 

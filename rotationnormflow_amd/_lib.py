@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "librnf_hip.so")
 _lib = None
 ABI_VERSION = 8
 PREC_FP32, PREC_F16X2, PREC_BF16X3 = 0, 1, 2
+FISHER_NORM_EXACT = 3   # RNF_FISHER_NORM_EXACT
 
 c_f32p = C.c_void_p      # device or host float*, passed as integer addresses
 c_i32p = C.c_void_p
@@ -121,6 +122,8 @@ _SIGNATURES = {
     "rnf_fisher_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "rnf_fisher_log_const_mc": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, C.c_size_t, c_f32p, C.c_void_p]),
     "rnf_fisher_log_const_nt": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, c_f32p, C.c_void_p]),
+    "rnf_fisher_exact": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p]),
+    "rnf_fisher_entropy": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
     "rnf_fisher_log_prob_backward_param": (C.c_int, [c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, c_f32p,
                                                   C.c_void_p]),
     "rnf_fisher_sample": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_uint64, c_f32p, C.c_void_p, C.c_void_p]),

@@ -20,6 +20,7 @@
 #include "pack_device.h"
 #include "sampler_kernel.h"
 #include "fisher_math.h"
+#include "fisher_exact.h"
 #include "layout.h"
 #include "equalize.h"
 #include "svd4_lapack.h"
@@ -1601,6 +1602,62 @@ extern "C" int rnf_fisher_log_const(const float *A, int64_t B, float *c_out, voi
     return fisher_const_launch(A, B, 1, nullptr, c_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+// The exact log-normaliser (fisher_exact.h): c = sum s + log int f, its derivative dc/dA = E[R] and the entropy, by a fixed 224-node rule.
+// ONE WAVE PER MATRIX, four matrices per workgroup: every lane of the wave runs the (wave-uniform) proper SVD of its matrix once, lane l
+// sums nodes l, l + 64, .. (two scaled-Bessel pairs and one exp per node), and the xor butterfly leaves the five sums in every lane in one
+// fixed order -- a row's result depends on nothing but the row: not on B, the row's position or the launch shape.  Lanes 0..8 write the
+// entries of E[R]; with grad_acc (the fp64 sums T_b, G_b of fisher_grad_accum_kernel) they also finish d log p / dA = T - G dc/dA.
+__global__ __launch_bounds__(256) void fisher_exact_kernel(const float *A, long long B, float *c_out, float *mean_out, float *entropy_out,
+                                                           const double *grad_acc, float *g_A) {
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;                                                  // wave-uniform
+    double a[9], U[9], s[3], V[9], acc[5], dc[9], m[3], c, h;
+    for (int k = 0; k < 9; ++k) a[k] = A[b * 9 + k];
+    proper_svd3(a, U, s, V);
+    fisher_exact_lane(s, lane, acc);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    fisher_exact_finish(s, acc, c, m, h);
+    fisher_exact_mean(U, m, V, dc);
+    double mine = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) mine = lane == k ? dc[k] : mine;
+    if (lane < 9) {
+        if (mean_out) mean_out[b * 9 + lane] = (float)mine;
+        if (g_A) g_A[b * 9 + lane] = (float)(grad_acc[10 * b + lane] - grad_acc[10 * b + 9] * mine);
+    }
+    if (lane == 0) {
+        if (c_out) c_out[b] = (float)c;
+        if (entropy_out) entropy_out[b] = (float)h;
+    }
+}
+
+static int fisher_exact_launch(const char *who, const float *A, int64_t B, float *c_out, float *mean_out, float *entropy_out, const double *grad_acc,
+                               float *g_A, hipStream_t st) {
+    const long long blocks = ((long long)B + 3) / 4;
+    if (blocks > 0x7fffffffLL) return fail("%s: B=%lld is more than one launch serves", who, (long long)B);
+    hipLaunchKernelGGL(fisher_exact_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A, (long long)B, c_out, mean_out, entropy_out, grad_acc, g_A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int rnf_fisher_exact(const float *A, int64_t B, float *c_out, float *mean_out, void *stream) {
+    if (B < 0) return fail("rnf_fisher_exact: B=%lld", (long long)B);
+    if (!c_out && !mean_out) return fail("rnf_fisher_exact: c_out_dev and mean_out_dev are both null");
+    if (B == 0) return 0;
+    if (!A) return fail("rnf_fisher_exact: null pointer");
+    return fisher_exact_launch("rnf_fisher_exact", A, B, c_out, mean_out, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int rnf_fisher_entropy(const float *A, int64_t B, float *entropy_out, void *stream) {
+    if (B < 0) return fail("rnf_fisher_entropy: B=%lld", (long long)B);
+    if (B == 0) return 0;
+    if (!A || !entropy_out) return fail("rnf_fisher_entropy: null pointer");
+    return fisher_exact_launch("rnf_fisher_entropy", A, B, nullptr, nullptr, entropy_out, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
 // pytorch3d.transforms.matrix_to_quaternion (published 0.7.5 rule; call sites flow/squeezetrans.py:34, utils/fisher.py:243): real part first,
 // the candidate with the largest |q_i|, denominators floored at 0.1 (so3_math.h rot_to_quat).  rot [n][9] row-major -> quat [n][4].
 __global__ void matrix_to_quaternion_kernel(const float *rot, long long n, float *quat) {
@@ -1681,8 +1738,11 @@ extern "C" size_t rnf_fisher_scratch_bytes(int64_t B) { return (size_t)(2 + 10 *
 extern "C" int rnf_fisher_log_const_nt(const float *A, int64_t B, int32_t norm_type, void *scratch, size_t scratch_bytes, float *c_out, void *stream) {
     if (!A || !c_out) return fail("rnf_fisher_log_const_nt: null pointer");
     if (B <= 0) return fail("rnf_fisher_log_const_nt: B=%lld", (long long)B);
+    if (norm_type == RNF_FISHER_NORM_EXACT)
+        return fisher_exact_launch("rnf_fisher_log_const_nt", A, B, c_out, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
     if (norm_type != 0 && norm_type != 1)
-        return fail("rnf_fisher_log_const_nt: norm_type=%d -- only the closed-form approximations 0 and 1 are built (utils/fisher.py:88-97)", (int)norm_type);
+        return fail("rnf_fisher_log_const_nt: norm_type=%d -- the closed-form approximations 0 and 1 (utils/fisher.py:88-97) and the exact integral "
+                    "RNF_FISHER_NORM_EXACT are built", (int)norm_type);
     if (norm_type == 0 && (!scratch || scratch_bytes < 2 * sizeof(double))) return fail("rnf_fisher_log_const_nt: norm_type 0 needs 16 bytes of scratch");
     return fisher_const_launch(A, B, norm_type, static_cast<double *>(scratch), c_out, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1749,7 +1809,8 @@ extern "C" int rnf_fisher_log_prob_backward_param(const float *g_logp, const flo
                                               void *scratch, size_t scratch_bytes, float *g_A, void *stream) {
     if (!g_logp || !rot || !A || !g_A || !scratch) return fail("rnf_fisher_log_prob_backward_param: null pointer");
     if (B <= 0 || n % B) return fail("n=%lld not divisible by fisher rows B=%lld (utils/fisher.py:226)", (long long)n, (long long)B);
-    if (norm_type != 0 && norm_type != 1) return fail("rnf_fisher_log_prob_backward_param: norm_type=%d is not built", (int)norm_type);
+    if (norm_type != 0 && norm_type != 1 && norm_type != RNF_FISHER_NORM_EXACT)
+        return fail("rnf_fisher_log_prob_backward_param: norm_type=%d is not built", (int)norm_type);
     if (scratch_bytes < rnf_fisher_scratch_bytes(B)) return fail("rnf_fisher_log_prob_backward_param: scratch of %zu bytes, need %zu", scratch_bytes, rnf_fisher_scratch_bytes(B));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     double *sc = static_cast<double *>(scratch);
@@ -1769,6 +1830,8 @@ extern "C" int rnf_fisher_log_prob_backward_param(const float *g_logp, const flo
         if (blocks > 1024) blocks = 1024;
         hipLaunchKernelGGL(fisher_grad_w_kernel, dim3((int)blocks), dim3(256), 0, st, A, (long long)B, sc);
     }
+    // the exact normaliser finishes in its own wave-per-matrix kernel: the quadrature never runs serially in a thread-per-matrix kernel
+    if (norm_type == RNF_FISHER_NORM_EXACT) return fisher_exact_launch("rnf_fisher_log_prob_backward_param", A, B, nullptr, nullptr, nullptr, sc + 2, g_A, st);
     hipLaunchKernelGGL(fisher_grad_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, A, (long long)B, norm_type, sc, g_A);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -2,7 +2,8 @@
 
 log p(R) = tr(A^T R) - (s0+s1+s2) - log norm, norm = 1/sqrt(8 pi (s0+s1)(s1+s2)(s0+s2))   (utils/fisher.py:93-97,217-232; norm_type 1)
 with s the *proper* singular values of A (last one sign-flipped by det(U) det(V), utils/fisher.py:67-76); norm_type 0 is the
-small-s approximation of utils/fisher.py:88-91.  Differentiable w.r.t. the rotations and w.r.t. A.
+small-s approximation of utils/fisher.py:88-91.  norm_type "exact" is the exact normaliser (the integral the reference's type 3 means),
+per row on the device through rnf_fisher_exact: finite and smooth for every A.  Differentiable w.r.t. the rotations and w.r.t. A.
 """
 import math
 
@@ -36,6 +37,27 @@ def proper_singular_values(A):
     S = S.clone()
     S[:, 2] = S[:, 2] * torch.det(U) * torch.det(Vh)
     return S
+
+
+def device_fisher_exact(A, want="c"):
+    """A [B,3,3] on the GPU -> the exact log-normaliser c [B] (want="c"), the mean rotation E[R] = dc/dA [B,3,3] ("mean") or the entropy
+    c - tr(A^T E[R]) [B] ("entropy") of MF(A[b]), fp32 device tensors from the wave-per-matrix quadrature kernel (csrc/fisher_exact.h).
+    Stream-ordered, no host synchronisation, not differentiable."""
+    if not A.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): the exact normaliser needs A on the GPU")
+    A32 = A.detach().reshape(-1, 3, 3).to(torch.float32).contiguous()
+    B, dev = A32.shape[0], A32.device
+    out = torch.empty((B, 3, 3) if want == "mean" else (B,), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if want == "c":
+            _lib.check(L.rnf_fisher_exact(A32.data_ptr(), B, out.data_ptr(), None, stream))
+        elif want == "mean":
+            _lib.check(L.rnf_fisher_exact(A32.data_ptr(), B, None, out.data_ptr(), stream))
+        else:
+            _lib.check(L.rnf_fisher_entropy(A32.data_ptr(), B, out.data_ptr(), stream))
+    return out
 
 
 def quaternion_to_matrix(q):
@@ -130,10 +152,18 @@ class MatrixFisherN(torch.nn.Module):
 
     def __init__(self, A, norm_type=1, approx_num=None):
         super().__init__()
-        if norm_type not in (0, 1, 2):
+        if isinstance(norm_type, str) and norm_type == "exact":
+            # the exact normaliser, per row from the quadrature kernel; the C ABI knows it as RNF_FISHER_NORM_EXACT
+            self.norm_type, self._nt = "exact", _lib.FISHER_NORM_EXACT
+            self.A = A.reshape(-1, 3, 3)
+            self._c = device_fisher_exact(self.A, "c")
+            self._norm = None
+            return
+        if isinstance(norm_type, str) or norm_type not in (0, 1, 2):
             raise NotImplementedError("normaliser approximations 0, 1 (closed forms) and 2 (Monte-Carlo) are built; type 3 indexes ROWS of the "
-                                      "[N,3] singular values and cannot serve MatrixFisherN's batched A (utils/fisher.py:102-113)")
-        self.norm_type = int(norm_type)
+                                      "[N,3] singular values and cannot serve MatrixFisherN's batched A (utils/fisher.py:102-113) -- "
+                                      'norm_type="exact" evaluates the same integral per row')
+        self.norm_type = self._nt = int(norm_type)
         self.A = A.reshape(-1, 3, 3)
         if self.norm_type == 2:
             # utils/fisher.py:98-101: mean over approx_num uniform rotations, ONE matrix (the reference's broadcast); on the device with
@@ -174,7 +204,7 @@ class MatrixFisherN(torch.nn.Module):
         """The reference's ``self.norm`` (utils/fisher.py:215); computed lazily when A lives on the GPU (needs the singular values)."""
         if self._norm is None:
             S = proper_singular_values(self.A)
-            if self.norm_type == 2:                          # c = sum S + log norm
+            if self.norm_type in (2, "exact"):               # c = sum S + log norm
                 self._norm = (self._c.detach().to(S.device, torch.float64) - S.sum(-1)).exp().to(device=self.A.device, dtype=self.A.dtype)
             else:
                 self._norm = _norm_from_singular_values(S, self.norm_type).to(device=self.A.device, dtype=self.A.dtype)
@@ -195,7 +225,16 @@ class MatrixFisherN(torch.nn.Module):
         dev = inputs.device
         A = self.A.detach().to(device=dev, dtype=torch.float32).contiguous()
         c = self._c.to(dev).contiguous()
-        return _FisherLogProb.apply(inputs, self.A, A, c, self.norm_type)
+        return _FisherLogProb.apply(inputs, self.A, A, c, self._nt)
+
+    def mean_rotation(self):
+        """E[R] = dc/dA of MF(A[b]), [B,3,3] fp32: always from the exact kernel, whatever this instance's norm_type.  Not differentiable."""
+        return device_fisher_exact(self.A, "mean")
+
+    def entropy(self):
+        """The differential entropy c - tr(A^T E[R]) of MF(A[b]) w.r.t. the Haar probability measure, [B] fp32 (<= 0, 0 at A = 0): always
+        with the exact normaliser, summed in fp64 on the device.  Not differentiable."""
+        return device_fisher_exact(self.A, "entropy")
 
     def log_prob(self, inputs, context=None):
         return self._log_prob(inputs)
@@ -272,14 +311,16 @@ def proper_svd(A, clone=False):
 def matrix_fisher_norm_N(A, type_approx=0, approx_num=17890714):
     """The approximated normalising constant of MF(A), A [N,3,3] -> [N] (utils/fisher.py:79-115): type 0 / 1 closed forms (type 0 keeps
     the reference's batch-global ``(S**2).sum()``), type 2 Monte-Carlo over `approx_num` uniform rotations (ONE matrix, on the GPU).
-    Type 3 is refused, see MatrixFisherN."""
+    Type 3 is refused, see MatrixFisherN; "exact" is the exact normaliser per row (on the GPU)."""
     A = A.reshape(-1, 3, 3)
+    if isinstance(type_approx, str) and type_approx == "exact":
+        return MatrixFisherN(A, "exact").norm
     if type_approx in (0, 1):
         S = proper_svd_N(A)[1] if A.is_cuda else proper_singular_values(A).to(A.dtype)
         return _norm_from_singular_values(S, type_approx)
     if type_approx == 2:
         return MatrixFisherN(A, 2, approx_num).norm
-    raise NotImplementedError("matrix_fisher_norm_N: type_approx 0, 1 and 2 are built (type 3: see MatrixFisherN)")
+    raise NotImplementedError('matrix_fisher_norm_N: type_approx 0, 1, 2 and "exact" are built (type 3 serves no batch: use "exact")')
 
 
 def sample_matrix_fisher(A, num_samples, b=1.5, oversampling_ratio=8):
