@@ -564,13 +564,18 @@ RNF_HD void gs36_backward(const float *M, const Rot &R, const Rot &gRout, float 
 // dQ = Q Omega with Omega skew and Omega S + S Omega = Q^T dM - dM^T Q, hence for G = Q^T (dL/dQ):
 //     dL/dM = Q hat(z),   (tr(S) I - S) z = vee(G - G^T)          (hat(z) S + S hat(z) = hat((tr(S) I - S) z) for symmetric S)
 // Q given by its rows (polar3 of so3_math.h), gQ row-major.
+// Range: dL/dM is homogeneous of degree -1 in M, so the formula runs on M 2^-ex (the power of two polar3 itself divides out, largest
+// entry in [1, 2)) and the result is multiplied by 2^-ex, both exact: gM(2^k M) = 2^-k gM(M) bit for bit, and the cofactors of
+// T = tr(S) I - S (eigenvalues s_i + s_j of the scaled M, determinant ~ |M|^3 otherwise) stay in range for every finite M.
 // ---------------------------------------------------------------------------------------------------------------------
 RNF_HD void polar3_backward(const float (&M)[9], v3f p0, v3f p1, v3f p2, const float (&gQ)[9], float (&gM)[9]) {
     const float Q[9] = {p0.x, p0.y, p0.z, p1.x, p1.y, p1.z, p2.x, p2.y, p2.z};
-    float S[9], G[9];
+    const int ex = polar3_exponent(M);
+    float Ms[9], S[9], G[9];
+    for (int i = 0; i < 9; ++i) Ms[i] = ldexpf(M[i], -ex);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
-            S[3 * i + j] = Q[i] * M[j] + Q[3 + i] * M[3 + j] + Q[6 + i] * M[6 + j];            // Q^T M
+            S[3 * i + j] = Q[i] * Ms[j] + Q[3 + i] * Ms[3 + j] + Q[6 + i] * Ms[6 + j];         // Q^T M
             G[3 * i + j] = Q[i] * gQ[j] + Q[3 + i] * gQ[3 + j] + Q[6 + i] * gQ[6 + j];          // Q^T gQ
         }
     const float tr = S[0] + S[4] + S[8];
@@ -583,7 +588,7 @@ RNF_HD void polar3_backward(const float (&M)[9], v3f p0, v3f p1, v3f p2, const f
     const v3f z = v3f{Ti[0] * w.x + Ti[1] * w.y + Ti[2] * w.z, Ti[3] * w.x + Ti[4] * w.y + Ti[5] * w.z, Ti[6] * w.x + Ti[7] * w.y + Ti[8] * w.z};
     const float Z[9] = {0.f, -z.z, z.y, z.z, 0.f, -z.x, -z.y, z.x, 0.f};                       // hat(z)
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) gM[3 * i + j] = Q[3 * i] * Z[j] + Q[3 * i + 1] * Z[3 + j] + Q[3 * i + 2] * Z[6 + j];
+        for (int j = 0; j < 3; ++j) gM[3 * i + j] = ldexpf(Q[3 * i] * Z[j] + Q[3 * i + 1] * Z[3 + j] + Q[3 * i + 2] * Z[6 + j], -ex);
 }
 
 // One conditional 3x3 layer: forward from the saved input (so that the caller need not keep the output) and the reverse step.

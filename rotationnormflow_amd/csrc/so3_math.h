@@ -731,18 +731,50 @@ RNF_HD void smith3(const float (&m)[9], v3f &q0, v3f &q1, v3f &q2) {
     q2 = cross3(q0, q1);
 }
 
-// Orthogonal polar factor U V^T of M (calculate_9_l / calculate_9_r, rottrans.py:72-82 take it from a batched SVD) by the Newton
-// iteration X <- (X + X^-T) / 2, X^-T = cof(X) / det(X): quadratically convergent, M = I + MLP output is well conditioned.
-// Rows of the result in p0, p1, p2.
+// Orthogonal polar factor U V^T of M (calculate_9_l / calculate_9_r, rottrans.py:72-82 take it from a batched SVD) by Newton's iteration
+// with determinantal scaling (Byers), X <- (g X + X^-T / g) / 2, X^-T = cof(X) / det(X), g = |det X|^(-1/3), ten steps.  The scaling needs
+// nothing beyond the determinant the step forms anyway (no further live registers in the EXT stack kernels).
+// g is taken from hw_log2 / hw_exp2: v_log_f32 / v_exp_f32 on the device (about 1 ulp), log2f / exp2f on the host.  The fixed point does not
+// depend on g (any g > 0 leaves the polar factor of X unchanged; g only sets the speed, and det = 1 gives g = 1 exactly on both), so the
+// two builds differ by rounding only: the host figures of DESIGN 3.7a are the host build's, tests/test_gpu_polar3.py measures the device's.
+//   * M is first multiplied by 2^-polar3_exponent(M) (exact), which brings its largest entry into [1, 2): the cofactor products stay in
+//     range for every finite M, and polar3(2^k M) is bit-equal to polar3(M).
+//   * the scaling g puts the singular values on both sides of 1 in every step, so ten steps reach fp32 convergence for every
+//     cond(M) <= 1e3 (measured: up to 1e8).  The unscaled step only halves a large singular value and doubles a small one, which covers
+//     2^+-9 around 1 in ten steps.
+//   * what ten steps did not make orthogonal (rank-deficient M, cond(M) beyond ~1e6) is returned as NaN, never as a finite
+//     non-rotation: the callers' non-finite guard sees it.  A NaN or infinite entry gives NaN as well, and so does an exact det(M) = 0.
+// Domain, error figures against LAPACK's fp32 SVD and the trip count: DESIGN.md section 3.7a, tests/test_polar3_host.py.
+// Rows of the result in p0, p1, p2; det(result) has the sign of det(M).
+RNF_HD int polar3_exponent(const float (&m)[9]) {
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) amax = fmaxf(amax, fabsf(m[i]));
+    return (amax > 0.f && amax <= 3.402823466e38f) ? ilogbf(amax) : 0;      // subnormals included; 0 for M = 0 and for an infinite entry
+}
+constexpr float kPolar3Orth = 16.0f * 1.1920928955078125e-7f;                 // 16 * 2^-23; a converged iterate shows <= 4 * 2^-23
+
 RNF_HD void polar3(const float (&m)[9], v3f &p0, v3f &p1, v3f &p2) {
-    p0 = v3f{m[0], m[1], m[2]}; p1 = v3f{m[3], m[4], m[5]}; p2 = v3f{m[6], m[7], m[8]};
+    const int ex = polar3_exponent(m);
+    p0 = v3f{ldexpf(m[0], -ex), ldexpf(m[1], -ex), ldexpf(m[2], -ex)};
+    p1 = v3f{ldexpf(m[3], -ex), ldexpf(m[4], -ex), ldexpf(m[5], -ex)};
+    p2 = v3f{ldexpf(m[6], -ex), ldexpf(m[7], -ex), ldexpf(m[8], -ex)};
 #pragma unroll 1
     for (int it = 0; it < 10; ++it) {
         const v3f c0 = cross3(p1, p2), c1 = cross3(p2, p0), c2 = cross3(p0, p1);      // rows of the cofactor matrix
-        const float hid = 0.5f / dot3(p0, c0);
-        p0 = p0 * 0.5f + c0 * hid;
-        p1 = p1 * 0.5f + c1 * hid;
-        p2 = p2 * 0.5f + c2 * hid;
+        const float det = dot3(p0, c0);
+        const float g = hw_exp2(hw_log2(fabsf(det)) * (-1.0f / 3.0f));               // |det X|^(-1/3): det(g X) = +-1
+        const float a = 0.5f * g, b = 0.5f / (g * det);
+        p0 = p0 * a + c0 * b;
+        p1 = p1 * a + c1 * b;
+        p2 = p2 * a + c2 * b;
+    }
+    const float t = kPolar3Orth;                                                      // comparisons, not fmaxf: a NaN must fail them
+    const bool ok = fabsf(dot3(p0, p0) - 1.0f) <= t && fabsf(dot3(p1, p1) - 1.0f) <= t && fabsf(dot3(p2, p2) - 1.0f) <= t &&
+                    fabsf(dot3(p0, p1)) <= t && fabsf(dot3(p0, p2)) <= t && fabsf(dot3(p1, p2)) <= t;
+    if (!ok) {
+        const float q = __builtin_nanf("");
+        p0 = v3f{q, q, q}; p1 = p0; p2 = p0;
     }
 }
 
