@@ -492,6 +492,59 @@ int rnf_fisher_exact(const float *A_dev, int64_t B, float *c_out_dev, float *mea
  * tr(A^T E[R]) (both ~ |s|, which the fp32 outputs of rnf_fisher_exact cannot carry).  entropy_out_dev float[B]. */
 int rnf_fisher_entropy(const float *A_dev, int64_t B, float *entropy_out_dev, void *stream);
 
+/* Weighted moments of G groups of n rotations, M_g = sum_i w_gi R_gi, in fp64: the sufficient statistic of a matrix-Fisher fit.  With
+ * log_weights, w_g = softmax(log_weights[g]) over the n rows (maximum subtracted, exp and sums in fp64; a -inf row contributes 0);
+ * without, w = 1/n.  shared_rotations != 0: one set of rotations [n][9] serves every group (a grid and one row of log-densities per
+ * image); it needs log_weights.  A group whose weights are all -inf, or that holds a NaN, yields NaN.  Deterministic: chunks of 4096
+ * rows, fixed-order sums, no atomics -- a group's moment is bit-identical whatever G and the group's position.  Stream-ordered, no host
+ * synchronisation, capturable in a HIP graph. */
+typedef struct RnfRotationMoments {
+    size_t struct_bytes;        /* sizeof(RnfRotationMoments); any other value is refused */
+    const float *rotations;     /* dev float[G][n][9] row-major, or float[n][9] with shared_rotations */
+    const float *log_weights;   /* dev float[G][n], or NULL (w = 1/n) */
+    int64_t n;                  /* rotations per group, 1..2^40 */
+    int64_t G;                  /* groups, >= 1; G * ceil(n / 4096) <= 2^31 - 1 */
+    int32_t shared_rotations;   /* 0, or 1: rotations is [n][9] for every group */
+    double *moments_out;        /* dev double[G][9] row-major */
+    /* dev scratch, 8-byte aligned, of at least rnf_rotation_moments_workspace_bytes(this struct) bytes = G * ceil(n / 4096) * 88 */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfRotationMoments;
+int rnf_rotation_moments(const RnfRotationMoments *moments);
+/* The workspace rnf_rotation_moments requires for the same struct (the workspace fields are not read); 0 when struct_bytes, n or G are
+ * out of range. */
+size_t rnf_rotation_moments_workspace_bytes(const RnfRotationMoments *moments);
+
+/* The maximum-likelihood matrix-Fisher parameter of B moment matrices: A[b] with E_A[R] = dc/dA = moments[b] under the exact normaliser
+ * (csrc/fisher_fit.h).  With the proper SVD moments[b] = U diag(d) V^T, A = U diag(s) V^T where s solves grad c(s) = d by a damped
+ * Newton iteration with the analytic Hessian H = d2c/ds2 = Cov(Q_ii, Q_jj), one wave per matrix; a row's outputs are bit-identical
+ * whatever B and the row's position.  status_out bits:
+ *   RNF_FIT_CAPPED (1)         d on the boundary of conv{(1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1)} (one sample, identical samples), or a
+ *                              maximiser with s0 > max_concentration: the outputs are the maximiser of the likelihood over the box
+ *                              |s_i| <= max_concentration, finite and ordered, s0 == max_concentration;
+ *   RNF_FIT_NOT_CONVERGED (2)  the iteration cap was reached before |d - grad c(s)|_inf <= 5e-14: the last iterate;
+ *   RNF_FIT_INPUT (4)          d more than 1e-5 outside that tetrahedron, or a non-finite moment: every output of the row is NaN.
+ * moments = 0 gives A = 0 exactly.  The moments are fp64 because rounding d to fp32 moves s by ~6e-8 / lambda_min(H), which reaches
+ * 4e-3 at s = (300, 200, 100).  Stream-ordered, no host synchronisation, capturable in a HIP graph. */
+#define RNF_FIT_CAPPED 1
+#define RNF_FIT_NOT_CONVERGED 2
+#define RNF_FIT_INPUT 4
+typedef struct RnfFisherFit {
+    size_t struct_bytes;        /* sizeof(RnfFisherFit); any other value is refused */
+    const double *moments;      /* dev double[B][9] row-major */
+    int64_t B;                  /* >= 0 (0 is a no-op) */
+    double max_concentration;   /* 0 < cap <= 3e4 (the range rnf_fisher_exact is tested on) */
+    int32_t max_iterations;     /* 0: the library's cap of 64 Newton iterations; 1..64: a smaller one */
+    float *A_out;               /* dev float[B][9] row-major */
+    double *s_out;              /* dev double[B][3] the proper singular values of A, or NULL */
+    double *hessian_out;        /* dev double[B][6]: H at s as (00, 01, 02, 11, 12, 22), or NULL */
+    int32_t *iterations_out;    /* dev int32[B] Newton iterations used, or NULL */
+    int32_t *status_out;        /* dev int32[B], or NULL */
+    void *stream;
+} RnfFisherFit;
+int rnf_fisher_fit(const RnfFisherFit *fit);
+
 /* Gradient of MatrixFisherN._log_prob w.r.t. A (agent.py:57-65 keeps a network-predicted A in the autograd graph; the reference
  * differentiates torch.svd, utils/fisher.py:67-76,217-232):  g_A[b] = sum_i g_logp[i] R_i - (sum_i g_logp[i]) dc/dA_b over the n/B
  * samples of row b, dc/dA = U' diag(dc/ds) V'^T on the proper SVD (csrc/fisher_math.h), plus the batch coupling of norm_type 0.

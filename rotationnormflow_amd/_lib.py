@@ -65,6 +65,22 @@ class GridBeamSelect(_Pass):
                 ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class RotationMoments(_Pass):
+    """RnfRotationMoments (include/rnf_hip.h): fp64 weighted moments of groups of rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("rotations", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64), ("G", C.c_int64),
+                ("shared_rotations", C.c_int32), ("moments_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class FisherFit(_Pass):
+    """RnfFisherFit (include/rnf_hip.h): the maximum-likelihood matrix-Fisher parameter of moment matrices."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("moments", C.c_void_p), ("B", C.c_int64), ("max_concentration", C.c_double),
+                ("max_iterations", C.c_int32), ("A_out", C.c_void_p), ("s_out", C.c_void_p), ("hessian_out", C.c_void_p),
+                ("iterations_out", C.c_void_p), ("status_out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+FIT_CAPPED, FIT_NOT_CONVERGED, FIT_INPUT = 1, 2, 4   # RNF_FIT_*
+
 _SIGNATURES = {
     "rnf_abi_version": (C.c_int, []),
     "rnf_last_error": (C.c_char_p, []),
@@ -124,6 +140,9 @@ _SIGNATURES = {
     "rnf_fisher_log_const_nt": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, c_f32p, C.c_void_p]),
     "rnf_fisher_exact": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_entropy": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),
+    "rnf_rotation_moments": (C.c_int, [C.POINTER(RotationMoments)]),
+    "rnf_rotation_moments_workspace_bytes": (C.c_size_t, [C.POINTER(RotationMoments)]),
+    "rnf_fisher_fit": (C.c_int, [C.POINTER(FisherFit)]),
     "rnf_fisher_log_prob_backward_param": (C.c_int, [c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, c_f32p,
                                                   C.c_void_p]),
     "rnf_fisher_sample": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_uint64, c_f32p, C.c_void_p, C.c_void_p]),

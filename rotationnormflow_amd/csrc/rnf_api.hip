@@ -21,6 +21,7 @@
 #include "sampler_kernel.h"
 #include "fisher_math.h"
 #include "fisher_exact.h"
+#include "fisher_fit.h"
 #include "layout.h"
 #include "equalize.h"
 #include "svd4_lapack.h"
@@ -1656,6 +1657,202 @@ extern "C" int rnf_fisher_entropy(const float *A, int64_t B, float *entropy_out,
     if (B == 0) return 0;
     if (!A || !entropy_out) return fail("rnf_fisher_entropy: null pointer");
     return fisher_exact_launch("rnf_fisher_entropy", A, B, nullptr, nullptr, entropy_out, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The maximum-likelihood matrix-Fisher parameter of B moment matrices (fisher_fit.h): ONE WAVE PER MATRIX, four per workgroup, as
+// fisher_exact_kernel.  Every lane runs the same (wave-uniform) Newton iteration on the same s; an evaluation of the 14 integrals is a
+// lane sum over nodes l, l + 64, .. and the xor butterfly, which leaves identical sums in every lane -- so the iteration count, the
+// backtracking and the result of a row depend on nothing but the row.
+struct FisherFitWaveEval {
+    int lane;
+    __device__ void operator()(const double s[3], double acc[kFisherFitSums]) const {
+        fisher_fit_lane(s, lane, acc);
+#pragma unroll
+        for (int k = 0; k < kFisherFitSums; ++k)
+            for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    }
+};
+
+__global__ __launch_bounds__(256) void fisher_fit_kernel(const double *moments, long long B, double cap, int max_iter, float *A_out, double *s_out,
+                                                         double *H_out, int *iter_out, int *status_out) {
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;                                                  // wave-uniform
+    double m[9], A[9], s[3], H[6];
+    int iters, status;
+    for (int k = 0; k < 9; ++k) m[k] = moments[b * 9 + k];
+    fisher_fit_matrix(m, cap, max_iter, FisherFitWaveEval{lane}, A, s, H, iters, status);
+    double a = 0.0, sv = 0.0, hv = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a = lane == k ? A[k] : a;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sv = lane == k ? s[k] : sv;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) hv = lane == k ? H[k] : hv;
+    if (lane < 9) A_out[b * 9 + lane] = (float)a;
+    if (s_out && lane < 3) s_out[b * 3 + lane] = sv;
+    if (H_out && lane < 6) H_out[b * 6 + lane] = hv;
+    if (lane == 0) {
+        if (iter_out) iter_out[b] = iters;
+        if (status_out) status_out[b] = status;
+    }
+}
+
+extern "C" int rnf_fisher_fit(const RnfFisherFit *p) {
+    if (!p || p->struct_bytes != sizeof(RnfFisherFit)) return fail("RnfFisherFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherFit));
+    if (p->B < 0) return fail("RnfFisherFit.B=%lld", (long long)p->B);
+    if (!(p->max_concentration > 0.0 && p->max_concentration <= 3e4))
+        return fail("RnfFisherFit.max_concentration=%g outside (0, 3e4]", p->max_concentration);
+    if (p->max_iterations < 0 || p->max_iterations > kFisherFitMaxIter)
+        return fail("RnfFisherFit.max_iterations=%d outside 0..%d (0: %d)", p->max_iterations, kFisherFitMaxIter, kFisherFitMaxIter);
+    if (p->B == 0) return 0;
+    if (!p->moments || !p->A_out) return fail("RnfFisherFit: null moments or A_out");
+    const long long blocks = ((long long)p->B + 3) / 4;
+    if (blocks > 0x7fffffffLL) return fail("RnfFisherFit.B=%lld is more than one launch serves", (long long)p->B);
+    hipLaunchKernelGGL(fisher_fit_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(p->stream), p->moments, (long long)p->B,
+                       p->max_concentration, p->max_iterations > 0 ? (int)p->max_iterations : kFisherFitMaxIter, p->A_out, p->s_out, p->hessian_out,
+                       p->iterations_out, p->status_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Weighted moments M_g = sum_i w_gi R_gi of G groups of n rotations, in fp64 and in ONE fixed order: a group is cut into chunks of 4096 rows
+// (a function of n alone), a 256-thread workgroup per (group, chunk) stages tiles of 256 rows through LDS (dwordx4 loads where the tile is
+// 16-byte aligned, dword loads otherwise -- the same values either way), thread t adds rows t, t + 256, .. of its chunk in that order,
+// the wave's xor butterfly and then waves 0, 1, 2, 3 in turn combine them, and one wave per group adds the chunk partials c, c + 64, ..
+// and its butterfly.  Nothing depends on G, on the group's position or on the launch, and there are no atomics: a group's moment is
+// bit-identical however it is batched.  With log-weights w = exp(lw - max lw) / sum (fp64 exp; the maximum is exact in any order);
+// workspace per (group, chunk): 10 partial sums (9 entries, the weight) and the chunk's maximum.
+namespace rmom {
+constexpr int THREADS = 256, TILE = 256, CHUNK = 4096, SLOTS = 11;
+static inline long long chunks_for(long long n) { return (n + CHUNK - 1) / CHUNK; }
+
+__device__ inline float block_max(float m, float *smax) {
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+}
+
+__global__ __launch_bounds__(THREADS) void rotation_moments_max_kernel(const float *lw, long long n, long long G, long long nchunk, double *ws) {
+    __shared__ float smax[4];
+    const long long g = blockIdx.x % G, ch = blockIdx.x / G;
+    const long long lo = ch * CHUNK, hi = lo + CHUNK < n ? lo + CHUNK : n;
+    float m = -INFINITY;
+    for (long long i = lo + threadIdx.x; i < hi; i += THREADS) m = fmaxf(m, lw[g * n + i]);
+    m = block_max(m, smax);
+    if (threadIdx.x == 0) ws[(g * nchunk + ch) * SLOTS + 10] = (double)m;
+}
+
+__global__ __launch_bounds__(THREADS) void rotation_moments_kernel(const float *rot, long long group_stride, const float *lw, long long n, long long G,
+                                                                   long long nchunk, double *ws) {
+    __shared__ __attribute__((aligned(16))) float tile[TILE * 9];
+    __shared__ float smax[4];
+    __shared__ double red[4][10];
+    const int tid = threadIdx.x;
+    const long long g = blockIdx.x % G, ch = blockIdx.x / G;
+    const long long lo = ch * CHUNK, hi = lo + CHUNK < n ? lo + CHUNK : n;
+    double gmax = 0.0;
+    if (lw) {
+        float m = -INFINITY;
+        for (long long c = tid; c < nchunk; c += THREADS) m = fmaxf(m, (float)ws[(g * nchunk + c) * SLOTS + 10]);
+        gmax = (double)block_max(m, smax);
+    }
+    double acc[10];
+    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+    for (long long t0 = lo; t0 < hi; t0 += TILE) {
+        const int rows = (int)(hi - t0 < TILE ? hi - t0 : TILE), nelem = rows * 9;
+        const float *src = rot + g * group_stride + t0 * 9;
+        __syncthreads();                                                 // the previous tile has been read
+        if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const int nq = nelem >> 2;
+            for (int q = tid; q < nq; q += THREADS) reinterpret_cast<float4 *>(tile)[q] = reinterpret_cast<const float4 *>(src)[q];
+            for (int e = 4 * nq + tid; e < nelem; e += THREADS) tile[e] = src[e];
+        } else {
+            for (int e = tid; e < nelem; e += THREADS) tile[e] = src[e];
+        }
+        __syncthreads();
+        if (tid < rows) {
+            const double w = lw ? exp((double)lw[g * n + t0 + tid] - gmax) : 1.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) acc[k] += w * (double)tile[tid * 9 + k];     // stride 9: conflict-free
+            acc[9] += w;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    if ((tid & 63) == 0)
+        for (int k = 0; k < 10; ++k) red[tid >> 6][k] = acc[k];
+    __syncthreads();
+    if (tid < 10) ws[(g * nchunk + ch) * SLOTS + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+__global__ __launch_bounds__(64) void rotation_moments_final_kernel(const double *ws, long long nchunk, double *out) {
+    const long long g = blockIdx.x;
+    const int lane = threadIdx.x;
+    double acc[10];
+    for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+    for (long long c = lane; c < nchunk; c += 64)
+        for (int k = 0; k < 10; ++k) acc[k] += ws[(g * nchunk + c) * SLOTS + k];
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    double mine = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) mine = lane == k ? acc[k] : mine;
+    if (lane < 9) out[g * 9 + lane] = mine / acc[9];
+}
+}  // namespace rmom
+
+static const char *rotation_moments_check(const RnfRotationMoments *p) {
+    static thread_local char msg[256];
+    if (!p || p->struct_bytes != sizeof(RnfRotationMoments)) {
+        snprintf(msg, sizeof(msg), "RnfRotationMoments.struct_bytes does not match the library's %zu", sizeof(RnfRotationMoments));
+        return msg;
+    }
+    if (p->G < 1) snprintf(msg, sizeof(msg), "RnfRotationMoments.G=%lld must be >= 1", (long long)p->G);
+    else if (p->n < 1 || p->n > (1LL << 40)) snprintf(msg, sizeof(msg), "RnfRotationMoments.n=%lld outside 1..2^40", (long long)p->n);
+    else if ((double)p->G * (double)rmom::chunks_for(p->n) > 2147483647.0)
+        snprintf(msg, sizeof(msg), "RnfRotationMoments: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G,
+                 rmom::chunks_for(p->n));
+    else return nullptr;
+    return msg;
+}
+
+extern "C" size_t rnf_rotation_moments_workspace_bytes(const RnfRotationMoments *p) {
+    if (const char *e = rotation_moments_check(p)) {
+        fail("%s", e);
+        return 0;
+    }
+    return (size_t)p->G * (size_t)rmom::chunks_for(p->n) * rmom::SLOTS * sizeof(double);
+}
+
+extern "C" int rnf_rotation_moments(const RnfRotationMoments *p) {
+    if (const char *e = rotation_moments_check(p)) return fail("%s", e);
+    if (!p->rotations || !p->moments_out) return fail("RnfRotationMoments: null rotations or moments_out");
+    if (p->shared_rotations && !p->log_weights) return fail("RnfRotationMoments.shared_rotations needs log_weights (every group would get the same moment)");
+    const size_t need = rnf_rotation_moments_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfRotationMoments.workspace of %zu bytes is smaller than the %zu needed (rnf_rotation_moments_workspace_bytes)", p->workspace_bytes,
+                    need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfRotationMoments.workspace must be 8-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    const long long nchunk = rmom::chunks_for(p->n);
+    const unsigned blocks = (unsigned)(p->G * nchunk);
+    double *ws = (double *)p->workspace;
+    if (p->log_weights) {
+        hipLaunchKernelGGL(rmom::rotation_moments_max_kernel, dim3(blocks), dim3(rmom::THREADS), 0, s, p->log_weights, (long long)p->n, (long long)p->G,
+                           nchunk, ws);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(rmom::rotation_moments_kernel, dim3(blocks), dim3(rmom::THREADS), 0, s, p->rotations,
+                       p->shared_rotations ? 0LL : (long long)p->n * 9, p->log_weights, (long long)p->n, (long long)p->G, nchunk, ws);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rmom::rotation_moments_final_kernel, dim3((unsigned)p->G), dim3(64), 0, s, (const double *)ws, nchunk, p->moments_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // pytorch3d.transforms.matrix_to_quaternion (published 0.7.5 rule; call sites flow/squeezetrans.py:34, utils/fisher.py:243): real part first,

@@ -529,6 +529,44 @@ def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, se
     return out
 
 
+def grid_pose_fisher(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None, base=None,
+                     images_per_launch: int = None) -> dict:
+    """The matrix-Fisher distribution that matches each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same
+    launches): the grid moment M_b = sum_i softmax(log p_b)_i R_i in fp64 (``rnf_rotation_moments`` on the shared grid) and its
+    maximum-likelihood A_b (``rnf_fisher_fit``), i.e. the Fisher with E[R] = M_b -- the moment projection of the grid posterior.
+    ``mode`` = U V^T of A's proper SVD is its most likely rotation, ``s`` its three concentrations; ``mean_rotation`` and ``entropy`` come
+    from the exact kernel on the fitted A.  ``status`` [B] int32 as ``fit_matrix_fisher`` (1: capped at the default max_concentration 1e4,
+    e.g. all mass on one grid point).  Flows with batch-coupled layers are refused as in ``grid_beam_estimate_rotations``.
+    -> dict(A [B,3,3], mean_rotation [B,3,3], mode [B,3,3], s [B,3] fp64, entropy [B], status [B], moments [B,3,3] fp64, offset [3,3])"""
+    from .utils import sd
+    from .utils import fisher
+    who = "grid_pose_fisher"
+    coupled = sorted({type(m).__name__ for m in flow.modules() if getattr(m, "_rnf_batch_coupled", False)})
+    if coupled:
+        raise ValueError(f"{who}: batch-coupled layers ({', '.join(coupled)}) take their matrices from a launch's first rows, so an image's "
+                         "density would depend on the launch; use grid_estimate_rotations")
+    feature, dev, B, level, offset, A, c = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        Q = grid.shape[0]
+        moments, whole = [], None
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, who):
+            if lp.shape[1] < Q:                                 # one image in chunks: gather them first
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            moments.append(fisher.rotation_moments(grid, lp))
+        moments = moments[0] if len(moments) == 1 else torch.cat(moments)
+        fit = fisher.fit_matrix_fisher(moments)
+        U, V, _, _ = fisher.device_proper_svd(fit["A"])
+        mf = fisher.MatrixFisherN(fit["A"], "exact")
+        return dict(A=fit["A"], mean_rotation=mf.mean_rotation(), mode=U @ V.transpose(-1, -2), s=fit["s"], entropy=mf.entropy(),
+                    status=fit["status"], moments=moments, offset=offset)
+
+
 def grid_children(parents: torch.Tensor, level: int, offset=None, rotations: bool = True):
     """``rnf_so3_grid_children``: the 12 level-(``level`` + 1) children of each level-``level`` grid row in ``parents`` [..., m] (int64, on
     the device; a row outside the level, e.g. -1, has children -1) -> (rows [..., m * 12] int64, rotations [..., m * 12, 3, 3] or None).

@@ -4,6 +4,8 @@ log p(R) = tr(A^T R) - (s0+s1+s2) - log norm, norm = 1/sqrt(8 pi (s0+s1)(s1+s2)(
 with s the *proper* singular values of A (last one sign-flipped by det(U) det(V), utils/fisher.py:67-76); norm_type 0 is the
 small-s approximation of utils/fisher.py:88-91.  norm_type "exact" is the exact normaliser (the integral the reference's type 3 means),
 per row on the device through rnf_fisher_exact: finite and smooth for every A.  Differentiable w.r.t. the rotations and w.r.t. A.
+``MatrixFisherN.fit`` / ``fit_matrix_fisher`` estimate A from rotations (the inverse of ``mean_rotation``), ``rotation_moments`` is their
+sufficient statistic.
 """
 import math
 
@@ -58,6 +60,71 @@ def device_fisher_exact(A, want="c"):
         else:
             _lib.check(L.rnf_fisher_entropy(A32.data_ptr(), B, out.data_ptr(), stream))
     return out
+
+
+def rotation_moments(rotations, log_weights=None):
+    """Weighted moments M_g = sum_i w_gi R_gi of groups of rotations, fp64 [G,3,3] on the device (rnf_rotation_moments): the sufficient
+    statistic of ``fit_matrix_fisher``.  ``rotations`` [n,3,3] (one group), [G,n,3,3], or [n,3,3] with ``log_weights`` [G,n] (one set
+    of rotations shared by G weightings -- a grid and one row of log-densities per image).  w_g = softmax(log_weights[g]) (fp64; a -inf
+    row contributes 0), or 1/n without log-weights.  Fixed summation order: a group's moment is bit-identical however it is batched.
+    A group whose weights are all -inf, or that holds a NaN, yields NaN.  Stream-ordered, no host synchronisation."""
+    if not rotations.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): rotation_moments needs the rotations on the GPU")
+    if rotations.dim() not in (3, 4) or tuple(rotations.shape[-2:]) != (3, 3):
+        raise ValueError(f"rotation_moments: rotations {tuple(rotations.shape)}, expected [n,3,3] or [G,n,3,3]")
+    dev = rotations.device
+    R = rotations.detach().to(torch.float32).contiguous()
+    n = R.shape[-3]
+    lw = None
+    if log_weights is not None:
+        lw = log_weights.detach().to(device=dev, dtype=torch.float32)
+        lw = lw.reshape(1, -1) if lw.dim() == 1 else lw
+        if lw.dim() != 2 or lw.shape[1] != n or (R.dim() == 4 and lw.shape[0] != R.shape[0]):
+            raise ValueError(f"rotation_moments: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
+        lw = lw.contiguous()
+    shared = R.dim() == 3 and lw is not None
+    G = lw.shape[0] if shared else (R.shape[0] if R.dim() == 4 else 1)
+    if n < 1 or G < 1:
+        raise ValueError(f"rotation_moments: {G} groups of {n} rotations")
+    out = torch.empty(G, 3, 3, dtype=torch.float64, device=dev)
+    args = _lib.RotationMoments(rotations=R.data_ptr(), log_weights=lw.data_ptr() if lw is not None else None, n=n, G=G,
+                                shared_rotations=int(shared), moments_out=out.data_ptr())
+    L = _lib.lib()
+    need = L.rnf_rotation_moments_workspace_bytes(_lib.C.byref(args))
+    if need == 0:
+        _lib.check(1)
+    ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.rnf_rotation_moments(_lib.C.byref(args)))
+    return out
+
+
+def fit_matrix_fisher(moments, max_concentration=1e4, max_iterations=0):
+    """The maximum-likelihood matrix-Fisher parameters of moment matrices ``moments`` [B,3,3] (fp64 on the device, e.g. from
+    ``rotation_moments``): A with E_A[R] = moments under the exact normaliser (rnf_fisher_fit, csrc/fisher_fit.h).
+    -> dict(A [B,3,3] fp32, s [B,3] fp64 proper singular values of A, hessian [B,6] fp64 = d2c/ds2 as (00, 01, 02, 11, 12, 22),
+    iterations [B] int32, status [B] int32), all on the device.  status bits: 1 CAPPED (no finite maximiser, or s0 > max_concentration:
+    the likelihood's maximiser over |s_i| <= max_concentration, with s0 == max_concentration), 2 NOT_CONVERGED (the last iterate),
+    4 INPUT (a moment outside the convex hull of SO(3), or non-finite: NaN).  ``max_iterations`` 0 is the library's cap.
+    Stream-ordered, no host synchronisation: reading ``status`` on the host is what waits."""
+    if not moments.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): fit_matrix_fisher needs the moments on the GPU")
+    dev = moments.device
+    M = moments.detach().reshape(-1, 3, 3).to(torch.float64).contiguous()
+    B = M.shape[0]
+    A = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+    s = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    H = torch.empty(B, 6, dtype=torch.float64, device=dev)
+    it = torch.empty(B, dtype=torch.int32, device=dev)
+    st = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        args = _lib.FisherFit(moments=M.data_ptr(), B=B, max_concentration=float(max_concentration), max_iterations=int(max_iterations),
+                              A_out=A.data_ptr(), s_out=s.data_ptr(), hessian_out=H.data_ptr(), iterations_out=it.data_ptr(),
+                              status_out=st.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().rnf_fisher_fit(_lib.C.byref(args)))
+    return dict(A=A, s=s, hessian=H, iterations=it, status=st)
 
 
 def quaternion_to_matrix(q):
@@ -226,6 +293,22 @@ class MatrixFisherN(torch.nn.Module):
         A = self.A.detach().to(device=dev, dtype=torch.float32).contiguous()
         c = self._c.to(dev).contiguous()
         return _FisherLogProb.apply(inputs, self.A, A, c, self._nt)
+
+    @classmethod
+    def fit(cls, rotations, log_weights=None, norm_type="exact", max_concentration=1e4):
+        """The maximum-likelihood MatrixFisherN of rotations on the device: ``rotations`` [n,3,3] (one distribution), [G,n,3,3] (G of
+        them), or [n,3,3] with ``log_weights`` [G,n] (G weightings of one set, e.g. a grid and each image's log-density on it; the
+        weights are softmax(log_weights) per row).  Moments in fp64 (``rotation_moments``), then ``fit_matrix_fisher``: the A whose mean
+        rotation under the exact normaliser is the sample moment.  The fitted model is always the exact one (``norm_type`` other than
+        "exact" is refused).  ``fit_status`` [G] int32 on the device (bits as ``fit_matrix_fisher``), ``fit_s`` and ``fit_iterations``
+        are attached; nothing here waits for the device, reading ``fit_status`` on the host does.  Not differentiable."""
+        if norm_type != "exact":
+            raise NotImplementedError('MatrixFisherN.fit: the fitted model is the exact one (norm_type="exact"); the closed-form normalisers '
+                                      "0 / 1 and the Monte-Carlo 2 have other maximisers")
+        fit = fit_matrix_fisher(rotation_moments(rotations, log_weights), max_concentration)
+        out = cls(fit["A"], "exact")
+        out.fit_status, out.fit_s, out.fit_iterations = fit["status"], fit["s"], fit["iterations"]
+        return out
 
     def mean_rotation(self):
         """E[R] = dc/dA of MF(A[b]), [B,3,3] fp32: always from the exact kernel, whatever this instance's norm_type.  Not differentiable."""
