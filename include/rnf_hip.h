@@ -545,6 +545,57 @@ typedef struct RnfFisherFit {
 } RnfFisherFit;
 int rnf_fisher_fit(const RnfFisherFit *fit);
 
+/* EM for a K-component mixture of matrix-Fishers per group of rotations (csrc/fisher_mixture.h), w.r.t. the Haar probability measure:
+ *   log p(R) = logsumexp_k( log_pi_k + tr(A_k^T R) - c(A_k) ),   c the exact log-normaliser of rnf_fisher_exact.
+ * Rows, weights, groups and shared_rotations as RnfRotationMoments.  One iteration: responsibilities r_ik in fp64 from the fp32 inputs,
+ * pi_k = sum_i w_i r_ik, M_k = sum_i w_i r_ik R_i / pi_k, A_k = the fit of rnf_fisher_fit to M_k rounded to fp32, c_k from the rounded
+ * A_k.  The state between iterations is exactly (A_out fp32, log_pi_out fp64): a call with iterations = T equals T chained calls with
+ * iterations = 1 (tol = 0), bit for bit; A_init may be A_out and log_pi_init may be log_pi_out.  Sums in the fixed order of
+ * rnf_rotation_moments: a group's outputs do not depend on G, its position or shared_rotations, and for K = 1 one iteration gives the
+ * A, s and status of rnf_rotation_moments + rnf_fisher_fit bit for bit.
+ * A group stops once 0 <= L_t - L_(t-1) <= tol (tol = 0: every iteration runs), L_t = sum_i w_i log p(R_i) under the parameters before
+ * iteration t.  status_out per component: the RNF_FIT_* bits of its last solve (CAPPED is legitimate: a component that collapses onto
+ * one row is bounded by max_concentration), or RNF_MIX_EMPTY: log_pi = -inf on entry or pi_k underflowed to 0 -- the component keeps
+ * its A, has log_pi = -inf and adds an exact +0.0 to every sum.  A group whose weights are all -inf, that holds a NaN, or whose
+ * components are all empty is NaN in every output with status RNF_FIT_INPUT; only that group.
+ * 2 * iterations + 3 launches (+ 1 with log_weights) whatever the data: stream-ordered, no host synchronisation, no atomics,
+ * capturable in a HIP graph as a linear chain. */
+#define RNF_MIX_EMPTY 8
+typedef struct RnfFisherMixtureFit {
+    size_t struct_bytes;        /* sizeof(RnfFisherMixtureFit); any other value is refused */
+    const float *rotations;     /* dev float[G][n][9] row-major, or float[n][9] with shared_rotations */
+    const float *log_weights;   /* dev float[G][n], or NULL (w = 1/n) */
+    int64_t n;                  /* rotations per group, 1..2^40 */
+    int64_t G;                  /* groups, >= 1; G * ceil(n / 4096) <= 2^31 - 1 */
+    int32_t shared_rotations;   /* 0, or 1: rotations is [n][9] for every group (needs log_weights) */
+    int32_t K;                  /* components, 1..8 */
+    const float *A_init;        /* dev float[G][K][9] */
+    const double *log_pi_init;  /* dev double[G][K], or NULL: uniform, log(1/K) */
+    int32_t iterations;         /* 1..256 */
+    double tol;                 /* >= 0 */
+    double max_concentration;   /* 0 < cap <= 3e4, as RnfFisherFit */
+    float *A_out;               /* dev float[G][K][9] */
+    double *log_pi_out;         /* dev double[G][K] */
+    double *s_out;              /* dev double[G][K][3]: the proper singular values of the component's last solve (NaN before one), or NULL */
+    double *loglik_out;         /* dev double[G][iterations + 1]: entry t = L before iteration t, the last used one = L of the outputs, then NaN */
+    double *weight_entropy_out; /* dev double[G]: -sum_i w_i log w_i, or NULL */
+    float *log_resp_out;        /* dev float[G][K][n]: log r_ik under the outputs, or NULL */
+    int32_t *status_out;        /* dev int32[G][K] */
+    int32_t *iterations_out;    /* dev int32[G]: EM iterations run */
+    void *workspace;            /* dev scratch, 8-byte aligned, of at least rnf_fisher_mixture_fit_workspace_bytes(this struct) bytes */
+    size_t workspace_bytes;
+    void *stream;
+} RnfFisherMixtureFit;
+int rnf_fisher_mixture_fit(const RnfFisherMixtureFit *fit);
+/* 8 * (G * ceil(n / 4096) * (10 K + 14) + G * K + G) bytes; 0 when struct_bytes, n, G, K or iterations are out of range. */
+size_t rnf_fisher_mixture_fit_workspace_bytes(const RnfFisherMixtureFit *fit);
+
+/* log p of n rotations under ONE fitted mixture -- A_dev float[K][9], log_pi_dev double[K], rotation_dev float[n][9] -> logp_out_dev
+ * float[n] and, unless NULL, log_resp_out_dev float[K][n] (log responsibilities) -- by the row function of the E-step above.  K in 1..8;
+ * a component with log_pi = -inf is left out (log r = -inf).  n = 0 is a no-op.  Stream-ordered, capturable; no gradient. */
+int rnf_fisher_mixture_log_prob(const float *A_dev, const double *log_pi_dev, int32_t K, const float *rotation_dev, int64_t n,
+                                float *logp_out_dev, float *log_resp_out_dev, void *stream);
+
 /* Gradient of MatrixFisherN._log_prob w.r.t. A (agent.py:57-65 keeps a network-predicted A in the autograd graph; the reference
  * differentiates torch.svd, utils/fisher.py:67-76,217-232):  g_A[b] = sum_i g_logp[i] R_i - (sum_i g_logp[i]) dc/dA_b over the n/B
  * samples of row b, dc/dA = U' diag(dc/ds) V'^T on the proper SVD (csrc/fisher_math.h), plus the batch coupling of norm_type 0.

@@ -79,6 +79,16 @@ class FisherFit(_Pass):
                 ("iterations_out", C.c_void_p), ("status_out", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class FisherMixtureFit(_Pass):
+    """RnfFisherMixtureFit (include/rnf_hip.h): EM for mixtures of matrix-Fishers, per group of rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("rotations", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64), ("G", C.c_int64),
+                ("shared_rotations", C.c_int32), ("K", C.c_int32), ("A_init", C.c_void_p), ("log_pi_init", C.c_void_p),
+                ("iterations", C.c_int32), ("tol", C.c_double), ("max_concentration", C.c_double), ("A_out", C.c_void_p),
+                ("log_pi_out", C.c_void_p), ("s_out", C.c_void_p), ("loglik_out", C.c_void_p), ("weight_entropy_out", C.c_void_p),
+                ("log_resp_out", C.c_void_p), ("status_out", C.c_void_p), ("iterations_out", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 FIT_CAPPED, FIT_NOT_CONVERGED, FIT_INPUT = 1, 2, 4   # RNF_FIT_*
 
 _SIGNATURES = {
@@ -143,6 +153,9 @@ _SIGNATURES = {
     "rnf_rotation_moments": (C.c_int, [C.POINTER(RotationMoments)]),
     "rnf_rotation_moments_workspace_bytes": (C.c_size_t, [C.POINTER(RotationMoments)]),
     "rnf_fisher_fit": (C.c_int, [C.POINTER(FisherFit)]),
+    "rnf_fisher_mixture_fit": (C.c_int, [C.POINTER(FisherMixtureFit)]),
+    "rnf_fisher_mixture_fit_workspace_bytes": (C.c_size_t, [C.POINTER(FisherMixtureFit)]),
+    "rnf_fisher_mixture_log_prob": (C.c_int, [c_f32p, C.c_void_p, C.c_int32, c_f32p, C.c_int64, c_f32p, c_f32p, C.c_void_p]),
     "rnf_fisher_log_prob_backward_param": (C.c_int, [c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, c_f32p,
                                                   C.c_void_p]),
     "rnf_fisher_sample": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_uint64, c_f32p, C.c_void_p, C.c_void_p]),

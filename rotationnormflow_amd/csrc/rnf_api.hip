@@ -22,6 +22,7 @@
 #include "fisher_math.h"
 #include "fisher_exact.h"
 #include "fisher_fit.h"
+#include "fisher_mixture.h"
 #include "layout.h"
 #include "equalize.h"
 #include "svd4_lapack.h"
@@ -1851,6 +1852,331 @@ extern "C" int rnf_rotation_moments(const RnfRotationMoments *p) {
                        p->shared_rotations ? 0LL : (long long)p->n * 9, p->log_weights, (long long)p->n, (long long)p->G, nchunk, ws);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rmom::rotation_moments_final_kernel, dim3((unsigned)p->G), dim3(64), 0, s, (const double *)ws, nchunk, p->moments_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// EM for mixtures of matrix-Fishers (fisher_mixture.h).  Per iteration two launches: mixture_accumulate_kernel, one 256-thread workgroup
+// per (group, chunk) with the K parameter sets in LDS, adds the 10 K + 3 sums of its chunk in the order of rotation_moments_kernel
+// (same tiles, same loads, same butterfly) into the workspace; mixture_finalise_kernel, one workgroup per group and one wave per
+// component, adds the chunk partials as rotation_moments_final_kernel does and runs the M-step of its component on fisher_fit_matrix
+// with the wave evaluator.  The state is A_out (fp32) and log_pi_out (fp64) themselves; c_k and the group's finished flag live in the
+// workspace.  Workgroups of a finished group return at once (workgroup-uniform: the flag is read before the barrier that precedes
+// any write of it).  No atomics, no host synchronisation; the launches depend on `iterations` alone.
+namespace rmix {
+constexpr int THREADS = 256, TILE = 256;
+
+// c of one rounded fp32 parameter matrix by a whole wave, as fisher_exact_kernel computes it
+__device__ __forceinline__ double wave_c(const float *A32, int lane) {
+    double a[9], s[3], acc[5], m[3], c, h;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a[k] = (double)A32[k];
+    proper_singular_values3(a, s);
+    fisher_exact_lane(s, lane, acc);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    fisher_exact_finish(s, acc, c, m, h);
+    return c;
+}
+
+// one workgroup per group, wave k = component k: the state copied to the outputs, c_k, and every output that a later kernel only
+// writes in part
+__global__ __launch_bounds__(64 * kMixMaxK) void mixture_prepare_kernel(const float *A_init, const double *log_pi_init, int K, int iterations,
+                                                                        float *A_out, double *log_pi_out, double *s_out, double *loglik_out,
+                                                                        double *went_out, int *status_out, int *iter_out, double *c_ws,
+                                                                        int *flag_ws) {
+    const long long g = blockIdx.x;
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long row = g * K + k;
+    float a[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) a[j] = A_init[row * 9 + j];
+    const double lp = log_pi_init ? log_pi_init[row] : -log((double)K);
+    const double c = wave_c(a, lane);
+    float mine = 0.f;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) mine = lane == j ? a[j] : mine;
+    if (lane < 9) A_out[row * 9 + lane] = mine;
+    if (s_out && lane < 3) s_out[row * 3 + lane] = NAN;
+    if (lane == 0) {
+        log_pi_out[row] = lp;
+        c_ws[row] = c;
+        status_out[row] = lp == -INFINITY ? kMixEmpty : 0;
+    }
+    for (int t = threadIdx.x; t <= iterations; t += blockDim.x) loglik_out[g * (iterations + 1) + t] = NAN;
+    if (threadIdx.x == 0) {
+        if (went_out) went_out[g] = NAN;
+        iter_out[g] = 0;
+        flag_ws[g] = 0;
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(THREADS) void mixture_accumulate_kernel(const float *rot, long long group_stride, const float *lw, long long n, long long G,
+                                                                     long long nchunk, const float *A, const double *log_pi, const double *c_ws,
+                                                                     const int *flag_ws, int ignore_finished, const double *max_ws, double *part_ws,
+                                                                     float *log_resp) {
+    constexpr int S = mix_slots(K);
+    __shared__ __attribute__((aligned(16))) float tile[TILE * 9];
+    __shared__ float smax[4];
+    __shared__ double pA[9 * K], pl[K], pc[K];
+    __shared__ double red[4][S];
+    const int tid = threadIdx.x;
+    const long long g = blockIdx.x % G, ch = blockIdx.x / G;
+    if (!ignore_finished && flag_ws[g]) return;                           // workgroup-uniform
+    const long long lo = ch * kMixChunk, hi = lo + kMixChunk < n ? lo + kMixChunk : n;
+    if (tid < 9 * K) pA[tid] = (double)A[g * 9 * K + tid];
+    if (tid < K) {
+        pl[tid] = log_pi[g * K + tid];
+        pc[tid] = c_ws[g * K + tid];
+    }
+    double gmax = 0.0;
+    if (lw) {
+        float m = -INFINITY;
+        for (long long c = tid; c < nchunk; c += THREADS) m = fmaxf(m, (float)max_ws[(g * nchunk + c) * rmom::SLOTS + 10]);
+        gmax = (double)rmom::block_max(m, smax);
+    }
+    double acc[S];
+#pragma unroll
+    for (int q = 0; q < S; ++q) acc[q] = 0.0;
+    for (long long t0 = lo; t0 < hi; t0 += TILE) {
+        const int rows = (int)(hi - t0 < TILE ? hi - t0 : TILE), nelem = rows * 9;
+        const float *src = rot + g * group_stride + t0 * 9;
+        __syncthreads();                                                 // the previous tile has been read; the parameters are in LDS
+        if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const int nq = nelem >> 2;
+            for (int q = tid; q < nq; q += THREADS) reinterpret_cast<float4 *>(tile)[q] = reinterpret_cast<const float4 *>(src)[q];
+            for (int e = 4 * nq + tid; e < nelem; e += THREADS) tile[e] = src[e];
+        } else {
+            for (int e = tid; e < nelem; e += THREADS) tile[e] = src[e];
+        }
+        __syncthreads();
+        if (tid < rows) {
+            const double d = lw ? (double)lw[g * n + t0 + tid] - gmax : 0.0, u = lw ? exp(d) : 1.0, e = u > 0.0 ? u * d : 0.0;
+            fisher_mixture_add_row<K>(tile + tid * 9, u, e, pA, pl, pc, acc, log_resp ? log_resp + g * K * n + t0 + tid : nullptr, n);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < S; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < S; ++q) red[tid >> 6][q] = acc[q];
+    }
+    __syncthreads();
+    if (tid < S) part_ws[(g * nchunk + ch) * S + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+__global__ __launch_bounds__(64 * kMixMaxK) void mixture_finalise_kernel(int K, int t, int iterations, int last, double tol, double cap, int weighted,
+                                                                         long long nchunk, const double *part_ws, double *c_ws, int *flag_ws,
+                                                                         float *A_out, double *log_pi_out, double *s_out, double *loglik_out,
+                                                                         double *went_out, int *status_out, int *iter_out, float *log_resp,
+                                                                         long long n) {
+    const long long g = blockIdx.x;
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63, S = mix_slots(K);
+    const long long row = g * K + k;
+    const int finished = flag_ws[g];
+    __syncthreads();                                                     // every wave has read the flag before wave 0 may set it
+    if (finished) return;
+    double acc[13];                                                      // the component's ten sums, then Z, sum u lse, sum u (lw - max)
+#pragma unroll
+    for (int q = 0; q < 13; ++q) acc[q] = 0.0;
+    for (long long c = lane; c < nchunk; c += 64) {
+        const double *p = part_ws + (g * nchunk + c) * S;
+#pragma unroll
+        for (int q = 0; q < 10; ++q) acc[q] += p[10 * k + q];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[10 + q] += p[10 * K + q];
+    }
+#pragma unroll
+    for (int q = 0; q < 13; ++q)
+        for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_xor(acc[q], o, 64);
+    double L, went;
+    double *ll = loglik_out + g * (iterations + 1);
+    if (!fisher_mixture_group(acc[10], acc[11], acc[12], weighted != 0, L, went)) {        // a NaN group: NaN throughout, status INPUT
+        if (lane < 9) A_out[row * 9 + lane] = NAN;
+        if (s_out && lane < 3) s_out[row * 3 + lane] = NAN;
+        if (lane == 0) {
+            log_pi_out[row] = NAN;
+            status_out[row] = kFisherFitInput;
+        }
+        if (log_resp)                                                   // the last pass: what the accumulate launch before it wrote
+            for (long long i = lane; i < n; i += 64) log_resp[row * n + i] = NAN;
+        if (k == 0) {
+            for (int q = lane; q <= iterations; q += 64) ll[q] = NAN;
+            if (lane == 0) {
+                if (went_out) went_out[g] = NAN;
+                iter_out[g] = t;
+                flag_ws[g] = 1;
+            }
+        }
+        return;
+    }
+    const double prev = t > 0 ? ll[t - 1] : 0.0;
+    if (k == 0 && lane == 0) {
+        ll[t] = L;
+        if (went_out) went_out[g] = went;
+        iter_out[g] = t;
+    }
+    if (last) return;
+    if (t > 0 && tol > 0.0 && L - prev >= 0.0 && L - prev <= tol) {
+        if (k == 0 && lane == 0) flag_ws[g] = 1;
+        return;
+    }
+    bool live = log_pi_out[row] != -INFINITY;                           // wave-uniform from here on
+    double lp = 0.0, s[3];
+    float A32[9];
+    int status = 0;
+    if (live) live = fisher_mixture_mstep(acc, acc[10], cap, FisherFitWaveEval{lane}, lp, A32, s, status);
+    if (!live) {
+        if (lane == 0) {
+            log_pi_out[row] = -INFINITY;
+            status_out[row] = kMixEmpty;
+        }
+        return;
+    }
+    const double c = wave_c(A32, lane);
+    float a = 0.f;
+    double sv = 0.0;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) a = lane == j ? A32[j] : a;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sv = lane == j ? s[j] : sv;
+    if (lane < 9) A_out[row * 9 + lane] = a;
+    if (s_out && lane < 3) s_out[row * 3 + lane] = sv;
+    if (lane == 0) {
+        log_pi_out[row] = lp;
+        c_ws[row] = c;
+        status_out[row] = status;
+    }
+}
+
+// log p and the log-responsibilities of n rotations under one mixture: the row function of the E-step.  Every workgroup computes the K
+// normalisers itself (waves k, k + 4, ..), so no workspace is needed.
+template <int K>
+__global__ __launch_bounds__(THREADS) void mixture_log_prob_kernel(const float *A, const double *log_pi, const float *rot, long long n, float *logp,
+                                                                   float *log_resp) {
+    __shared__ double pA[9 * K], pl[K], pc[K];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int k = wave; k < K; k += 4) {
+        const double c = wave_c(A + 9 * k, lane);
+        if (lane == 0) pc[k] = c;
+    }
+    if (tid < 9 * K) pA[tid] = (double)A[tid];
+    if (tid < K) pl[tid] = log_pi[tid];
+    __syncthreads();
+    for (long long i = (long long)blockIdx.x * THREADS + tid; i < n; i += (long long)gridDim.x * THREADS) {
+        float R[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) R[j] = rot[i * 9 + j];
+        double l[K], lse;
+        fisher_mixture_row<K>(R, pA, pl, pc, l, lse);
+        logp[i] = (float)lse;
+        if (log_resp) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) log_resp[k * n + i] = (float)(l[k] - lse);
+        }
+    }
+}
+
+static inline long long chunks_for(long long n) { return (n + kMixChunk - 1) / kMixChunk; }
+}  // namespace rmix
+
+#define RNF_MIX_DISPATCH(K, ...)                                                                                                  \
+    switch (K) {                                                                                                                    \
+        case 1: { constexpr int KK = 1; __VA_ARGS__; } break;                                                                              \
+        case 2: { constexpr int KK = 2; __VA_ARGS__; } break;                                                                              \
+        case 3: { constexpr int KK = 3; __VA_ARGS__; } break;                                                                              \
+        case 4: { constexpr int KK = 4; __VA_ARGS__; } break;                                                                              \
+        case 5: { constexpr int KK = 5; __VA_ARGS__; } break;                                                                              \
+        case 6: { constexpr int KK = 6; __VA_ARGS__; } break;                                                                              \
+        case 7: { constexpr int KK = 7; __VA_ARGS__; } break;                                                                              \
+        default: { constexpr int KK = 8; __VA_ARGS__; } break;                                                                             \
+    }
+
+static const char *fisher_mixture_check(const RnfFisherMixtureFit *p) {
+    static thread_local char msg[256];
+    if (!p || p->struct_bytes != sizeof(RnfFisherMixtureFit)) {
+        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherMixtureFit));
+        return msg;
+    }
+    if (p->G < 1 || p->G > 0x7fffffffLL) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.G=%lld outside 1..2^31-1", (long long)p->G);
+    else if (p->n < 1 || p->n > (1LL << 40)) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.n=%lld outside 1..2^40", (long long)p->n);
+    else if (p->K < 1 || p->K > kMixMaxK) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.K=%d outside 1..%d", (int)p->K, kMixMaxK);
+    else if (p->iterations < 1 || p->iterations > kMixMaxIterations)
+        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.iterations=%d outside 1..%d", (int)p->iterations, kMixMaxIterations);
+    else if ((double)p->G * (double)rmix::chunks_for(p->n) > 2147483647.0)
+        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G,
+                 rmix::chunks_for(p->n));
+    else return nullptr;
+    return msg;
+}
+
+// workspace, in doubles: chunk partials [G][nchunk][10 K + 3] | chunk maxima in the layout of rotation_moments_max_kernel [G][nchunk][11] |
+// c [G][K] | finished flags [G] (int32, one per 8 bytes)
+extern "C" size_t rnf_fisher_mixture_fit_workspace_bytes(const RnfFisherMixtureFit *p) {
+    if (const char *e = fisher_mixture_check(p)) {
+        fail("%s", e);
+        return 0;
+    }
+    const size_t cells = (size_t)p->G * (size_t)rmix::chunks_for(p->n);
+    return (cells * (size_t)(mix_slots(p->K) + rmom::SLOTS) + (size_t)p->G * (size_t)p->K + (size_t)p->G) * sizeof(double);
+}
+
+extern "C" int rnf_fisher_mixture_fit(const RnfFisherMixtureFit *p) {
+    if (const char *e = fisher_mixture_check(p)) return fail("%s", e);
+    if (!p->rotations || !p->A_init || !p->A_out || !p->log_pi_out || !p->loglik_out || !p->status_out || !p->iterations_out)
+        return fail("RnfFisherMixtureFit: null rotations, A_init, A_out, log_pi_out, loglik_out, status_out or iterations_out");
+    if (p->shared_rotations && !p->log_weights) return fail("RnfFisherMixtureFit.shared_rotations needs log_weights (every group would be the same)");
+    if (!(p->tol >= 0.0)) return fail("RnfFisherMixtureFit.tol=%g must be >= 0", p->tol);
+    if (!(p->max_concentration > 0.0 && p->max_concentration <= 3e4))
+        return fail("RnfFisherMixtureFit.max_concentration=%g outside (0, 3e4]", p->max_concentration);
+    const size_t need = rnf_fisher_mixture_fit_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfFisherMixtureFit.workspace of %zu bytes is smaller than the %zu needed (rnf_fisher_mixture_fit_workspace_bytes)",
+                    p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfFisherMixtureFit.workspace must be 8-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(p->stream);
+    const int K = p->K, T = p->iterations;
+    const long long G = p->G, n = p->n, nchunk = rmix::chunks_for(n);
+    const size_t cells = (size_t)G * (size_t)nchunk;
+    double *part_ws = (double *)p->workspace, *max_ws = part_ws + cells * mix_slots(K), *c_ws = max_ws + cells * rmom::SLOTS;
+    int *flag_ws = reinterpret_cast<int *>(c_ws + (size_t)G * K);
+    const unsigned blocks = (unsigned)cells;
+    const long long stride = p->shared_rotations ? 0LL : n * 9;
+    if (p->log_weights) {
+        hipLaunchKernelGGL(rmom::rotation_moments_max_kernel, dim3(blocks), dim3(rmom::THREADS), 0, st, p->log_weights, n, G, nchunk, max_ws);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(rmix::mixture_prepare_kernel, dim3((unsigned)G), dim3(64 * K), 0, st, p->A_init, p->log_pi_init, K, T, p->A_out, p->log_pi_out,
+                       p->s_out, p->loglik_out, p->weight_entropy_out, p->status_out, p->iterations_out, c_ws, flag_ws);
+    HIP_TRY(hipGetLastError());
+    for (int t = 0; t <= T; ++t) {
+        const int last = t == T;
+        RNF_MIX_DISPATCH(K, hipLaunchKernelGGL(rmix::mixture_accumulate_kernel<KK>, dim3(blocks), dim3(rmix::THREADS), 0, st, p->rotations, stride,
+                                               p->log_weights, n, G, nchunk, (const float *)p->A_out, (const double *)p->log_pi_out,
+                                               (const double *)c_ws, (const int *)flag_ws, last, (const double *)max_ws, part_ws,
+                                               last ? p->log_resp_out : (float *)nullptr));
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rmix::mixture_finalise_kernel, dim3((unsigned)G), dim3(64 * K), 0, st, K, t, T, last, p->tol, p->max_concentration,
+                           p->log_weights ? 1 : 0, nchunk, (const double *)part_ws, c_ws, flag_ws, p->A_out, p->log_pi_out, p->s_out, p->loglik_out,
+                           p->weight_entropy_out, p->status_out, p->iterations_out, last ? p->log_resp_out : (float *)nullptr, n);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int rnf_fisher_mixture_log_prob(const float *A, const double *log_pi, int32_t K, const float *rotations, int64_t n, float *logp_out,
+                                           float *log_resp_out, void *stream) {
+    if (K < 1 || K > kMixMaxK) return fail("rnf_fisher_mixture_log_prob: K=%d outside 1..%d", (int)K, kMixMaxK);
+    if (n < 0) return fail("rnf_fisher_mixture_log_prob: n=%lld", (long long)n);
+    if (n == 0) return 0;
+    if (!A || !log_pi || !rotations || !logp_out) return fail("rnf_fisher_mixture_log_prob: null pointer");
+    long long blocks = ((long long)n + rmix::THREADS - 1) / rmix::THREADS;
+    if (blocks > 1024) blocks = 1024;
+    RNF_MIX_DISPATCH(K, hipLaunchKernelGGL(rmix::mixture_log_prob_kernel<KK>, dim3((unsigned)blocks), dim3(rmix::THREADS), 0,
+                                           reinterpret_cast<hipStream_t>(stream), A, log_pi, rotations, (long long)n, logp_out, log_resp_out));
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -567,6 +567,55 @@ def grid_pose_fisher(flow: Flow, feature: torch.Tensor = None, number_queries: i
                     status=fit["status"], moments=moments, offset=offset)
 
 
+def grid_pose_mixture(flow: Flow, feature: torch.Tensor = None, components: int = 4, separation_deg: float = 15.0, iterations: int = 64,
+                      tol: float = 1e-9, number_queries: int = None, recursion_level: int = None, offset=None, base=None,
+                      images_per_launch: int = None, max_concentration: float = 1e4) -> dict:
+    """A ``components``-component mixture of matrix-Fishers for each image's density on the grid of ``grid_estimate_rotations`` (same
+    inputs, same launches as ``grid_pose_fisher``): EM on the shared grid with the image's log-densities as log-weights
+    (``rnf_fisher_mixture_fit``), started from the image's ``grid_modes`` (``fisher.mixture_init_from_modes``: component k on mode k,
+    weight = the mode's share of the mass; a mode that does not exist is an empty component, status 8, weight 0).  ``kl`` = log Q -
+    weight_entropy - log_likelihood is the KL divergence from the grid-normalised posterior (mass softmax(log p)_i on cell i, i.e. density
+    Q softmax(log p)_i w.r.t. Haar) to the mixture: >= 0 up to rounding, the smaller the better the summary; with ``components=1`` it is
+    the same quantity for the single Fisher of ``grid_pose_fisher``, whose A, s and status that call reproduces bit for bit.
+    ``mode`` = U V^T of each A's proper SVD.  Flows with batch-coupled layers are refused as in ``grid_pose_fisher``.
+    -> dict(A [B,K,3,3], weight [B,K] fp64, mode [B,K,3,3], s [B,K,3] fp64, log_likelihood [B] fp64, kl [B] fp64, status [B,K],
+    iterations [B], loglik [B,iterations+1] fp64 (the trace: entry t before iteration t, NaN after the last used one), offset [3,3])"""
+    from .utils import sd
+    from .utils import fisher
+    who = "grid_pose_mixture"
+    if not 1 <= int(components) <= 8:
+        raise ValueError(f"{who}: components={components} outside 1..8")
+    if not 0.0 < float(separation_deg) <= 180.0:
+        raise ValueError(f"{who}: separation_deg={separation_deg} outside (0, 180]")
+    coupled = sorted({type(m).__name__ for m in flow.modules() if getattr(m, "_rnf_batch_coupled", False)})
+    if coupled:
+        raise ValueError(f"{who}: batch-coupled layers ({', '.join(coupled)}) take their matrices from a launch's first rows, so an image's "
+                         "density would depend on the launch; use grid_estimate_rotations")
+    K, sep = int(components), float(np.deg2rad(np.float64(separation_deg)))
+    feature, dev, B, level, offset, A, c = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        Q = grid.shape[0]
+        fits, whole = [], None
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, who):
+            if lp.shape[1] < Q:                                 # one image in chunks: gather them first
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            index, _, mass, _, _ = grid_modes(lp, grid, K, sep)
+            A0, lp0 = fisher.mixture_init_from_modes(grid, index, mass, sep)
+            fits.append(fisher.fit_matrix_fisher_mixture(grid, lp, A0, lp0, iterations, tol, max_concentration))
+        fit = fits[0] if len(fits) == 1 else {k: torch.cat([f[k] for f in fits]) for k in fits[0]}
+        U, V, _, _ = fisher.device_proper_svd(fit["A"])
+        L = fit["loglik"].gather(1, fit["iterations"].long()[:, None])[:, 0]
+        return dict(A=fit["A"], weight=fit["log_pi"].exp(), mode=(U @ V.transpose(-1, -2)).reshape(B, K, 3, 3), s=fit["s"], log_likelihood=L,
+                    kl=float(np.log(Q)) - fit["weight_entropy"] - L, status=fit["status"], iterations=fit["iterations"], loglik=fit["loglik"],
+                    offset=offset)
+
+
 def grid_children(parents: torch.Tensor, level: int, offset=None, rotations: bool = True):
     """``rnf_so3_grid_children``: the 12 level-(``level`` + 1) children of each level-``level`` grid row in ``parents`` [..., m] (int64, on
     the device; a row outside the level, e.g. -1, has children -1) -> (rows [..., m * 12] int64, rotations [..., m * 12, 3, 3] or None).

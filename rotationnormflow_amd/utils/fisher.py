@@ -5,7 +5,8 @@ with s the *proper* singular values of A (last one sign-flipped by det(U) det(V)
 small-s approximation of utils/fisher.py:88-91.  norm_type "exact" is the exact normaliser (the integral the reference's type 3 means),
 per row on the device through rnf_fisher_exact: finite and smooth for every A.  Differentiable w.r.t. the rotations and w.r.t. A.
 ``MatrixFisherN.fit`` / ``fit_matrix_fisher`` estimate A from rotations (the inverse of ``mean_rotation``), ``rotation_moments`` is their
-sufficient statistic.
+sufficient statistic.  ``MatrixFisherMixture`` / ``fit_matrix_fisher_mixture`` fit and evaluate K-component mixtures of exact matrix-Fishers
+by EM on the device (csrc/fisher_mixture.h).
 """
 import math
 
@@ -125,6 +126,174 @@ def fit_matrix_fisher(moments, max_concentration=1e4, max_iterations=0):
                               status_out=st.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.lib().rnf_fisher_fit(_lib.C.byref(args)))
     return dict(A=A, s=s, hessian=H, iterations=it, status=st)
+
+
+MIX_EMPTY = 8        # RNF_MIX_EMPTY, beside the RNF_FIT_* bits of fit_matrix_fisher
+
+
+def fit_matrix_fisher_mixture(rotations, log_weights, A_init, log_pi_init=None, iterations=64, tol=1e-9, max_concentration=1e4,
+                              log_resp=False):
+    """EM for K-component mixtures of exact matrix-Fishers on the device (rnf_fisher_mixture_fit, csrc/fisher_mixture.h):
+    log p(R) = logsumexp_k(log_pi_k + tr(A_k^T R) - c(A_k)) w.r.t. the Haar probability measure.  ``rotations`` / ``log_weights`` as
+    ``rotation_moments`` ([n,3,3], [G,n,3,3], or [n,3,3] shared by ``log_weights`` [G,n]; None: w = 1/n); ``A_init`` [G,K,3,3] (or
+    [K,3,3] for one group), ``log_pi_init`` [G,K] fp64 or None (uniform; -inf marks an empty component).  At most ``iterations`` EM
+    iterations (1..256); a group stops once 0 <= L_t - L_(t-1) <= tol (tol = 0: every iteration runs).
+    -> dict(A [G,K,3,3] fp32, log_pi [G,K] fp64, s [G,K,3] fp64, loglik [G,iterations+1] fp64 (entry t: L before iteration t; NaN after
+    the last used one), weight_entropy [G] fp64, status [G,K] int32 (RNF_FIT_* bits of the component's last solve, 8: empty),
+    iterations [G] int32, log_resp [G,K,n] fp32 with ``log_resp=True``), all on the device.  The state between iterations is exactly
+    (A, log_pi): T iterations equal T chained calls of one.  A group's outputs are bit-identical however it is batched; K = 1 gives the
+    A, s and status of ``rotation_moments`` + ``fit_matrix_fisher``.  A group with all weights -inf, a NaN, or no live component is NaN
+    with status 4.  Stream-ordered, no host synchronisation, capturable."""
+    if not rotations.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): fit_matrix_fisher_mixture needs the rotations on the GPU")
+    if rotations.dim() not in (3, 4) or tuple(rotations.shape[-2:]) != (3, 3):
+        raise ValueError(f"fit_matrix_fisher_mixture: rotations {tuple(rotations.shape)}, expected [n,3,3] or [G,n,3,3]")
+    dev = rotations.device
+    R = rotations.detach().to(torch.float32).contiguous()
+    n = R.shape[-3]
+    lw = None
+    if log_weights is not None:
+        lw = log_weights.detach().to(device=dev, dtype=torch.float32)
+        lw = lw.reshape(1, -1) if lw.dim() == 1 else lw
+        if lw.dim() != 2 or lw.shape[1] != n or (R.dim() == 4 and lw.shape[0] != R.shape[0]):
+            raise ValueError(f"fit_matrix_fisher_mixture: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
+        lw = lw.contiguous()
+    shared = R.dim() == 3 and lw is not None
+    G = lw.shape[0] if shared else (R.shape[0] if R.dim() == 4 else 1)
+    A0 = A_init.detach().to(device=dev, dtype=torch.float32)
+    if A0.dim() not in (3, 4) or tuple(A0.shape[-2:]) != (3, 3) or A0.numel() % (9 * G) or (A0.dim() == 4 and A0.shape[0] != G):
+        raise ValueError(f"fit_matrix_fisher_mixture: A_init {tuple(A_init.shape)} for {G} groups, expected [G,K,3,3]")
+    A0 = A0.reshape(G, -1, 3, 3).contiguous()
+    K = A0.shape[1]
+    if not 1 <= K <= 8:
+        raise ValueError(f"fit_matrix_fisher_mixture: {K} components outside 1..8")
+    if not 1 <= int(iterations) <= 256:
+        raise ValueError(f"fit_matrix_fisher_mixture: iterations={iterations} outside 1..256")
+    lp0 = None
+    if log_pi_init is not None:
+        lp0 = log_pi_init.detach().to(device=dev, dtype=torch.float64)
+        if lp0.numel() != G * K:
+            raise ValueError(f"fit_matrix_fisher_mixture: log_pi_init {tuple(log_pi_init.shape)}, expected [{G},{K}]")
+        lp0 = lp0.reshape(G, K).contiguous()
+    T = int(iterations)
+    out = dict(A=torch.empty(G, K, 3, 3, dtype=torch.float32, device=dev), log_pi=torch.empty(G, K, dtype=torch.float64, device=dev),
+               s=torch.empty(G, K, 3, dtype=torch.float64, device=dev), loglik=torch.empty(G, T + 1, dtype=torch.float64, device=dev),
+               weight_entropy=torch.empty(G, dtype=torch.float64, device=dev), status=torch.empty(G, K, dtype=torch.int32, device=dev),
+               iterations=torch.empty(G, dtype=torch.int32, device=dev))
+    if log_resp:
+        out["log_resp"] = torch.empty(G, K, n, dtype=torch.float32, device=dev)
+    args = _lib.FisherMixtureFit(rotations=R.data_ptr(), log_weights=lw.data_ptr() if lw is not None else None, n=n, G=G,
+                                 shared_rotations=int(shared), K=K, A_init=A0.data_ptr(), log_pi_init=lp0.data_ptr() if lp0 is not None else None,
+                                 iterations=T, tol=float(tol), max_concentration=float(max_concentration), A_out=out["A"].data_ptr(),
+                                 log_pi_out=out["log_pi"].data_ptr(), s_out=out["s"].data_ptr(), loglik_out=out["loglik"].data_ptr(),
+                                 weight_entropy_out=out["weight_entropy"].data_ptr(),
+                                 log_resp_out=out["log_resp"].data_ptr() if log_resp else None, status_out=out["status"].data_ptr(),
+                                 iterations_out=out["iterations"].data_ptr())
+    L = _lib.lib()
+    need = L.rnf_fisher_mixture_fit_workspace_bytes(_lib.C.byref(args))
+    if need == 0:
+        _lib.check(1)
+    ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.rnf_fisher_mixture_fit(_lib.C.byref(args)))
+    return out
+
+
+def mixture_init_from_modes(grid, index, mass, separation_rad):
+    """The start of a mixture fit from ``harness.grid_modes``: component k sits on mode k with A_k = kappa0 R_k, kappa0 = 2 /
+    separation_rad^2 (MF(kappa R) has an angular standard deviation of 1 / sqrt(2 kappa) per axis: half the separation), log_pi_k the log
+    of the mode's share of the modes' mass; a missing mode (index -1) or one without mass is an empty component (log_pi = -inf, A = 0).
+    grid [Q,3,3], index [g,K] int64, mass [g,K] -> (A_init [g,K,3,3] fp32, log_pi_init [g,K] fp64)."""
+    kappa0 = 2.0 / float(separation_rad) ** 2
+    have = index >= 0
+    A = grid.reshape(-1, 3, 3).to(torch.float32)[index.clamp(min=0)] * kappa0
+    A = torch.where(have[..., None, None], A, torch.zeros_like(A))
+    m = torch.where(have, mass.to(torch.float64), torch.zeros_like(mass, dtype=torch.float64))
+    return A.contiguous(), torch.log(m / m.sum(-1, keepdim=True))
+
+
+class MatrixFisherMixture(torch.nn.Module):
+    """A K-component mixture of exact matrix-Fishers: log p(R) = logsumexp_k(log_weight_k + tr(A_k^T R) - c(A_k)) w.r.t. the Haar
+    probability measure.  ``A`` [K,3,3] (fp32) and ``log_weight`` [K] (fp64; -inf drops a component) are registered buffers: they move
+    with ``.to()`` and are what ``state_dict()`` stores.  No autograd."""
+
+    def __init__(self, A, log_weight):
+        super().__init__()
+        if not A.is_cuda:
+            raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): construct MatrixFisherMixture with A on the GPU")
+        self.register_buffer("A", A.detach().reshape(-1, 3, 3).to(torch.float32).contiguous().clone())
+        self.register_buffer("log_weight", log_weight.detach().reshape(-1).to(device=self.A.device, dtype=torch.float64).contiguous().clone())
+        if not 1 <= self.A.shape[0] <= 8 or self.log_weight.shape[0] != self.A.shape[0]:
+            raise ValueError(f"MatrixFisherMixture: A {tuple(A.shape)} and log_weight {tuple(log_weight.shape)}, expected [K,3,3] and [K], K in 1..8")
+
+    def _evaluate(self, rotations, want_resp):
+        if not rotations.is_cuda:
+            raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        if rotations.dim() != 3 or tuple(rotations.shape[-2:]) != (3, 3):
+            raise ValueError(f"MatrixFisherMixture: rotations {tuple(rotations.shape)}, expected [n,3,3]")
+        if not self.A.is_cuda:
+            raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): move the MatrixFisherMixture to the GPU")
+        dev = self.A.device
+        A = self.A.to(torch.float32).contiguous()                       # a module-wide .double() / .half() must not change what the kernel reads
+        log_weight = self.log_weight.to(torch.float64).contiguous()
+        R = rotations.detach().to(device=dev, dtype=torch.float32).contiguous()
+        n, K = R.shape[0], A.shape[0]
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+        resp = torch.empty(K, n, dtype=torch.float32, device=dev) if want_resp else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().rnf_fisher_mixture_log_prob(A.data_ptr(), log_weight.data_ptr(), K, R.data_ptr(), n, logp.data_ptr(),
+                                                              resp.data_ptr() if want_resp else None, torch.cuda.current_stream(dev).cuda_stream))
+        return logp, resp
+
+    def log_prob(self, rotations):
+        """[n,3,3] -> log p [n] fp32 (rnf_fisher_mixture_log_prob: the row function of the E-step)."""
+        return self._evaluate(rotations, False)[0]
+
+    def log_responsibilities(self, rotations):
+        """[n,3,3] -> log r [n,K] fp32: each row's log posterior membership in each component (-inf for a dropped one)."""
+        return self._evaluate(rotations, True)[1].t()
+
+    def responsibilities(self, rotations):
+        """[n,3,3] -> r [n,K] fp32, rows summing to 1."""
+        return self.log_responsibilities(rotations).exp()
+
+    def components(self):
+        """The K components as one ``MatrixFisherN(A [K,3,3], "exact")``."""
+        return MatrixFisherN(self.A, "exact")
+
+    @classmethod
+    def fit(cls, rotations, log_weights=None, components=4, init=None, separation_deg=15.0, iterations=64, tol=1e-9, max_concentration=1e4):
+        """EM fit of one mixture to ``rotations`` [n,3,3] with weights softmax(``log_weights`` [n]) (None: 1/n), by
+        ``fit_matrix_fisher_mixture``.  ``init``: A_init [K,3,3], or (A_init, log_pi_init [K]); None with log-weights given starts from
+        ``harness.grid_modes`` of the log-weights on the rotations (``components`` modes at least ``separation_deg`` apart, see
+        ``mixture_init_from_modes``); None without log-weights is refused.  The result carries ``fit_status`` [K], ``fit_s`` [K,3],
+        ``fit_iterations``, ``log_likelihood`` (fp64 scalars on the device) and ``fit`` (the whole output dict)."""
+        if rotations.dim() != 3:
+            raise ValueError(f"MatrixFisherMixture.fit: rotations {tuple(rotations.shape)}, expected one group [n,3,3]")
+        lw = None
+        if log_weights is not None:
+            lw = log_weights.reshape(1, -1)
+            if lw.shape[1] != rotations.shape[0]:
+                raise ValueError(f"MatrixFisherMixture.fit: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
+        if init is None:
+            if lw is None:
+                raise ValueError("MatrixFisherMixture.fit: without log_weights there are no modes to start from; pass init")
+            if not 1 <= int(components) <= 8:
+                raise ValueError(f"MatrixFisherMixture.fit: components={components} outside 1..8")
+            from .. import harness
+            sep = math.radians(float(separation_deg))
+            index, _, mass, _, _ = harness.grid_modes(lw.to(device=rotations.device, dtype=torch.float32), rotations, int(components), sep)
+            A0, lp0 = mixture_init_from_modes(rotations, index, mass, sep)
+        else:
+            A0, lp0 = init if isinstance(init, (tuple, list)) else (init, None)
+            A0 = A0.reshape(1, -1, 3, 3)
+        fit = fit_matrix_fisher_mixture(rotations, lw, A0, lp0, iterations, tol, max_concentration)
+        out = cls(fit["A"][0], fit["log_pi"][0])
+        out.fit_status, out.fit_s, out.fit_iterations, out.fit = fit["status"][0], fit["s"][0], fit["iterations"][0], fit
+        out.log_likelihood = fit["loglik"][0].gather(0, fit["iterations"][0].reshape(1).long())[0]
+        return out
 
 
 def quaternion_to_matrix(q):
