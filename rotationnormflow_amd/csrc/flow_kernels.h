@@ -1669,13 +1669,7 @@ __device__ __forceinline__ void cond9_finish(int kind, const f32x16 &o, int h, R
     }
     m[0] += 1.f; m[4] += 1.f; m[8] += 1.f;
     if (kind == RNF_KIND_COND9_GS) {                       // Condition9Trans (squeezetrans.py:239-247)
-        if (INVERSE) {
-            float mi[9];
-            inv3(m, mi);
-            gs9_apply(mi, R, ldj);
-        } else {
-            gs9_apply(m, R, ldj);
-        }
+        cond_gs9_apply(m, INVERSE, R, ldj);            // scaled by a power of two; the inverse pass needs no inverse (so3_math.h)
     } else if (kind == RNF_KIND_COND9_SMITH) {             // Condition9RotRSmith (rottrans.py:173-181): R GS(M), inverse R GS(M)^T
         v3f q0, q1, q2;
         smith3(m, q0, q1, q2);
@@ -2126,8 +2120,7 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                     float M9[9];
 #pragma unroll
                     for (int i = 0; i < 9; ++i) M9[i] = m[i];
-                    if (DIR) { float Mi[9]; inv3(M9, Mi); gs9_apply(Mi, R, ldj); }
-                    else gs9_apply(M9, R, ldj);
+                    cond_gs9_apply(M9, DIR != 0, R, ldj);
                 } else {
                     float M[16], Mi[16];
 #pragma unroll

@@ -439,7 +439,8 @@ RNF_HD void gs9_backward(const float (&M)[9], const Rot &R, const Rot &gRout, fl
     const float iu00 = 1.0f / sqrtf(dot3(x0, x0));
     const v3f q0 = x0 * iu00;
     const float d = dot3(q0, x1);
-    const v3f b1 = x1 - q0 * d;
+    v3f b1 = x1 - q0 * d;
+    b1 = b1 - q0 * dot3(q0, b1);                           // the second projection of so3_math.h gram_schmidt3: the same b1, to rounding
     const float iu11 = 1.0f / sqrtf(dot3(b1, b1));
     const v3f q1 = b1 * iu11;
     const v3f q2 = cross3(q0, q1);
@@ -591,22 +592,42 @@ RNF_HD void polar3_backward(const float (&M)[9], v3f p0, v3f p1, v3f p2, const f
         for (int j = 0; j < 3; ++j) gM[3 * i + j] = ldexpf(Q[3 * i] * Z[j] + Q[3 * i + 1] * Z[3 + j] + Q[3 * i + 2] * Z[6 + j], -ex);
 }
 
+// calculate_9 with a per-sample M (Condition9Trans, Condition9TransLU; inverse: the layer applied M^-1) and its reverse step.  R' and ldj
+// are homogeneous of degree 0 in M and dL/dM of degree -1, so the formulas run on Ms = M 2^-ex (the power of two cond_gs9_apply divides
+// out, so3_math.h) and dL/dM is multiplied by 2^-ex, both exact: gM(2^k M) = 2^-k gM(M) bit for bit, dL/dR does not change, and the cubic
+// cofactor determinant of inv3 stays in range for every finite M.  gM is written, not accumulated into.
+RNF_HD void cond_gs9_backward(const float (&M)[9], bool inverse, const Rot &Rin, const Rot &gRout, float g_ldj, float (&gM)[9], Rot &gRin) {
+    const int ex = polar3_exponent(M);
+    float Ms[9], g[9];
+    scale3_pow2(M, -ex, Ms);
+    for (int i = 0; i < 9; ++i) g[i] = 0.f;
+    if (inverse) {
+        float Mi[9], gMi[9];
+        inv3(Ms, Mi);
+        float E[9];                                        // one Newton step from the left, Mi <- (2 I - Mi Ms) Mi: the cofactor inverse errs by
+        for (int i = 0; i < 3; ++i)                        // 2^-23 cond |Mi| in no particular direction, which Gram-Schmidt of Mi R magnifies by
+            for (int j = 0; j < 3; ++j)                    // cond once more; after the step Mi = (I + D) M^-1 with |D| ~ 2^-23 cond, which it does not
+                E[3 * i + j] = (i == j ? 2.0f : 0.0f) - (Mi[3 * i] * Ms[j] + Mi[3 * i + 1] * Ms[3 + j] + Mi[3 * i + 2] * Ms[6 + j]);
+        float Mn[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Mn[3 * i + j] = E[3 * i] * Mi[j] + E[3 * i + 1] * Mi[3 + j] + E[3 * i + 2] * Mi[6 + j];
+        for (int i = 0; i < 9; ++i) { Mi[i] = Mn[i]; gMi[i] = 0.f; }
+        gs9_backward(Mi, Rin, gRout, g_ldj, gMi, gRin);
+        inverse_matrix_grad<3>(Mi, gMi, g);
+    } else {
+        gs9_backward(Ms, Rin, gRout, g_ldj, g, gRin);
+    }
+    scale3_pow2(g, -ex, gM);
+}
+
 // One conditional 3x3 layer: forward from the saved input (so that the caller need not keep the output) and the reverse step.
 // kind: RNF_KIND_COND9_*; inverse: the layer ran inside Flow.inverse.  gM is dL/d(net output) (the identity is a constant).
 RNF_HD void cond9_backward(int kind, bool inverse, const float (&M)[9], const Rot &Rin, const Rot &gRout, float g_ldj, float (&gM)[9], Rot &gRin) {
-    for (int i = 0; i < 9; ++i) gM[i] = 0.f;
     if (kind == RNF_KIND_COND9_GS) {                       // Condition9Trans (squeezetrans.py:234-247): inverse pass applies M^-1
-        if (inverse) {
-            float Mi[9], gMi[9];
-            inv3(M, Mi);
-            for (int i = 0; i < 9; ++i) gMi[i] = 0.f;
-            gs9_backward(Mi, Rin, gRout, g_ldj, gMi, gRin);
-            inverse_matrix_grad<3>(Mi, gMi, gM);
-        } else {
-            gs9_backward(M, Rin, gRout, g_ldj, gM, gRin);
-        }
+        cond_gs9_backward(M, inverse, Rin, gRout, g_ldj, gM, gRin);
         return;
     }
+    for (int i = 0; i < 9; ++i) gM[i] = 0.f;
     const v3f rc[3] = {Rin.c0, Rin.c1, Rin.c2}, gc[3] = {gRout.c0, gRout.c1, gRout.c2};
     auto rin = [&](int i, int j) { const v3f c = rc[j]; return i == 0 ? c.x : (i == 1 ? c.y : c.z); };      // R[i][j]
     auto gout = [&](int i, int j) { const v3f c = gc[j]; return i == 0 ? c.x : (i == 1 ? c.y : c.z); };
@@ -640,7 +661,7 @@ RNF_HD void cond9_backward(int kind, bool inverse, const float (&M)[9], const Ro
         Rot I, gq, dump;
         I.c0 = v3f{1.f, 0.f, 0.f}; I.c1 = v3f{0.f, 1.f, 0.f}; I.c2 = v3f{0.f, 0.f, 1.f};
         gq.c0 = v3f{gF[0], gF[3], gF[6]}; gq.c1 = v3f{gF[1], gF[4], gF[7]}; gq.c2 = v3f{gF[2], gF[5], gF[8]};
-        gs9_backward(M, I, gq, 0.f, gM, dump);
+        cond_gs9_backward(M, false, I, gq, 0.f, gM, dump);
     } else {
         polar3_backward(M, p0, p1, p2, gF, gM);
     }

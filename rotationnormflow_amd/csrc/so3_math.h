@@ -676,20 +676,96 @@ RNF_HD v3f mat3_mul(const float *M, v3f a) {          // row-major 3x3 times vec
                fmaf(M[8], a.z, fmaf(M[7], a.y, M[6] * a.x))};
 }
 
+// ---- what the per-sample 3x3 routines share (polar3, smith3, the calculate_9 family): range and "rotation or NaN" ----------------
+// 2^polar3_exponent(M) is the power of two that brings the largest entry of M into [1, 2).  The per-sample routines multiply M by its
+// inverse first (exact), so that squares and cofactors stay in range for every finite M and f(2^k M) is bit-equal to f(M).
+RNF_HD int polar3_exponent(const float (&m)[9]) {
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) amax = fmaxf(amax, fabsf(m[i]));
+    return (amax > 0.f && amax <= 3.402823466e38f) ? ilogbf(amax) : 0;      // subnormals included; 0 for M = 0 and for an infinite entry
+}
+RNF_HD void scale3_pow2(const float (&m)[9], int e, float (&o)[9]) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o[i] = ldexpf(m[i], e);
+}
+constexpr float kPolar3Orth = 16.0f * 1.1920928955078125e-7f;                 // 16 * 2^-23; a converged iterate shows <= 4 * 2^-23
+// rows (or columns) orthonormal to kPolar3Orth.  Comparisons, not fmaxf: a NaN must fail them.
+RNF_HD bool orth3_ok(v3f p0, v3f p1, v3f p2) {
+    const float t = kPolar3Orth;
+    return fabsf(dot3(p0, p0) - 1.0f) <= t && fabsf(dot3(p1, p1) - 1.0f) <= t && fabsf(dot3(p2, p2) - 1.0f) <= t &&
+           fabsf(dot3(p0, p1)) <= t && fabsf(dot3(p0, p2)) <= t && fabsf(dot3(p1, p2)) <= t;
+}
+
+RNF_HD v3f nan_unless(bool ok, v3f v) {                  // scalar selects: a select between two structs goes through memory
+    const float q = __builtin_nanf("");
+    return v3f{ok ? v.x : q, ok ? v.y : q, ok ? v.z : q};
+}
+
+// Gram-Schmidt rotation [q0 q1 q0 x q1] of two columns x0, x1.  b1 = x1 - (q0.x1) q0 is left with a component of about 2^-23 |x1| along q0,
+// which normalising magnifies by |x1| / |b1| (up to the condition number): it is projected out a second time ("twice is enough"), so
+// that q0 . q1 stays at rounding level whatever the angle between the columns.  Returns false where the result is not a rotation to
+// kPolar3Orth (a zero, NaN or infinite column) or where |b1| < 2^-20 |x1|: there cancellation has left fewer than three significant bits
+// of b1's direction.  The caller then returns NaN (nan_unless), so that the kernels' non-finite guard sees it, not a well-formed
+// arbitrary rotation.
+constexpr float kGsRank = 9.094947017729282379e-13f;                           // 2^-40 = (2^-20)^2, against squared lengths
+RNF_HD bool gram_schmidt3(v3f x0, v3f x1, v3f &q0, v3f &q1, v3f &q2) {
+    const float m1 = kGsRank * dot3(x1, x1);
+    q0 = x0 * hw_rsq(dot3(x0, x0));
+    v3f b1 = x1 - q0 * dot3(q0, x1);
+    const float n1 = dot3(b1, b1);
+    b1 = b1 - q0 * dot3(q0, b1);
+    q1 = b1 * hw_rsq(dot3(b1, b1));
+    q2 = cross3(q0, q1);
+    // q0, q1 unit and normal to each other to t = kPolar3Orth make q2 = q0 x q1 unit and normal to both to the same order (|q2|^2 =
+    // |q0|^2 |q1|^2 - (q0.q1)^2), so three of orth3_ok's six comparisons decide.  Comparisons, not fmaxf: a NaN must fail them.
+    const float t = kPolar3Orth;
+    return n1 >= m1 && fabsf(dot3(q0, q0) - 1.0f) <= t && fabsf(dot3(q1, q1) - 1.0f) <= t && fabsf(dot3(q0, q1)) <= t;
+}
+
 // calculate_9 (squeezetrans.py:199-231): Gram-Schmidt of X = M R.  With X = Q U (U upper triangular, u00 = |x0|, u22 = q2 . x2) the
 // reference's tangent-space determinant (three directions R G_k pushed through normalise / project / normalise / cross) is, in closed
 // form,  ldj = 2 log|u22| - 2 log u00  (checked against the forward-mode restatement in oracle.gs9 to 1e-14 in fp64,
 // tests/test_oracle_golden.py); only the 6x6 variant needs the tangent machinery above.
+// R' and ldj are both NaN where gram_schmidt3 refuses, or where |u22| < 2^-20 |x2| (the third column lies in the plane of the first two
+// to rounding, and ldj would be the logarithm of a rounding error).  M is used as it is given: the per-sample callers go through
+// cond_gs9_apply below, which scales it first.
+RNF_HD void gs9_finish(bool ok, v3f q0, v3f q1, v3f q2, float u, float n0, float n2, Rot &R, float &ldj) {
+    ok = ok && u * u >= kGsRank * n2;
+    R.c0 = nan_unless(ok, q0); R.c1 = nan_unless(ok, q1); R.c2 = nan_unless(ok, q2);
+    ldj += ok ? 0.693147180559945309f * hw_log2(u * u * hw_rcp(n0)) : __builtin_nanf("");
+}
 RNF_HD void gs9_apply(const float *M, Rot &R, float &ldj) {
     const v3f x0 = mat3_mul(M, R.c0), x1 = mat3_mul(M, R.c1), x2 = mat3_mul(M, R.c2);
-    const float n0 = dot3(x0, x0);
-    const v3f q0 = x0 * hw_rsq(n0);
-    const v3f b1 = x1 - q0 * dot3(q0, x1);
-    const v3f q1 = b1 * hw_rsq(dot3(b1, b1));
-    const v3f q2 = cross3(q0, q1);
-    const float u22 = dot3(q2, x2);
-    R.c0 = q0; R.c1 = q1; R.c2 = q2;
-    ldj += 0.693147180559945309f * hw_log2(u22 * u22 * hw_rcp(n0));
+    v3f q0, q1, q2;
+    const bool ok = gram_schmidt3(x0, x1, q0, q1, q2);
+    gs9_finish(ok, q0, q1, q2, dot3(q2, x2), dot3(x0, x0), dot3(x2, x2), R, ldj);
+}
+
+// gs9_apply(M^-1, R, ldj) without the inverse (the inverse pass of the per-sample layers).  X = M^-1 R = Q U gives X^-T = M^T R = Q L with
+// L = U^-T LOWER triangular, l_ii = 1 / u_ii: the same Q comes out of Gram-Schmidt on the columns of Y = M^T R taken from the last to the
+// first, and  ldj = 2 log|u22| - 2 log u00 = 2 log l00 - 2 log|y2|.  u00, u11 > 0 and q2 = q0 x q1 fix the signs: l00 = q0 . y0 > 0, and
+// q2 = +-y2 / |y2| with the sign of det M.  Backward stable like the forward pass (error ~ 2^-23 cond(M)), where Gram-Schmidt of a
+// computed inverse carries cond(M) twice.
+RNF_HD v3f mat3t_mul(const float *M, v3f a) {         // transpose of a row-major 3x3 times vector
+    return v3f{fmaf(M[6], a.z, fmaf(M[3], a.y, M[0] * a.x)), fmaf(M[7], a.z, fmaf(M[4], a.y, M[1] * a.x)),
+               fmaf(M[8], a.z, fmaf(M[5], a.y, M[2] * a.x))};
+}
+RNF_HD void gs9_apply_inverse(const float *M, Rot &R, float &ldj) {
+    const v3f y0 = mat3t_mul(M, R.c0), y1 = mat3t_mul(M, R.c1), y2 = mat3t_mul(M, R.c2);
+    v3f a, q1, c;                                      // a = y2 / |y2|, c = a x q1
+    const bool ok = gram_schmidt3(y2, y1, a, q1, c);
+    const float s = dot3(c, y0);                       // q0 = -+c, whichever gives q0 . y0 > 0; q2 = q0 x q1 = +-a
+    const float sg = s > 0.f ? 1.0f : -1.0f;
+    gs9_finish(ok, c * sg, q1, a * -sg, s, dot3(y2, y2), dot3(y0, y0), R, ldj);
+}
+
+// The per-sample calculate_9 layers (Condition9Trans, Condition9TransLU): M 2^-polar3_exponent(M) in place of M.  R' and ldj do not depend
+// on the scale of M, so nothing is multiplied back, and cond_gs9_apply(2^k M) is bit-equal to cond_gs9_apply(M).
+// Domain and error figures against LAPACK's fp32 QR: DESIGN.md section 3.7b, tests/test_gs3_host.py.
+RNF_HD void cond_gs9_apply(float (&m)[9], bool inverse, Rot &R, float &ldj) {          // m is scaled in place
+    scale3_pow2(m, -polar3_exponent(m), m);
+    if (inverse) gs9_apply_inverse(m, R, ldj); else gs9_apply(m, R, ldj);
 }
 
 // calculate_36: (r0 (+) r1) as a 6-vector times M [6][6]; tangent directions G_k R (left multiplication):
@@ -722,13 +798,14 @@ RNF_HD void inv3(const float (&m)[9], float (&o)[9]) {
     o[6] = c02 * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
-// Gram-Schmidt rotation of the COLUMNS of M (calculate_9_r_smith, rottrans.py:85-91), returned as columns q0, q1, q2
+// Gram-Schmidt rotation of the COLUMNS of M (calculate_9_r_smith, rottrans.py:85-91), returned as columns q0, q1, q2: gram_schmidt3 of
+// the first two columns of M 2^-polar3_exponent(M).  A rotation to kPolar3Orth, with det = +1 whatever the sign of det M, or NaN;
+// smith3(2^k M) is bit-equal to smith3(M).  Figures: DESIGN.md section 3.7b.
 RNF_HD void smith3(const float (&m)[9], v3f &q0, v3f &q1, v3f &q2) {
-    const v3f a0 = v3f{m[0], m[3], m[6]}, a1 = v3f{m[1], m[4], m[7]};
-    q0 = a0 * hw_rsq(dot3(a0, a0));
-    const v3f b1 = a1 - q0 * dot3(q0, a1);
-    q1 = b1 * hw_rsq(dot3(b1, b1));
-    q2 = cross3(q0, q1);
+    const int e = -polar3_exponent(m);
+    const v3f a0 = v3f{ldexpf(m[0], e), ldexpf(m[3], e), ldexpf(m[6], e)}, a1 = v3f{ldexpf(m[1], e), ldexpf(m[4], e), ldexpf(m[7], e)};
+    const bool ok = gram_schmidt3(a0, a1, q0, q1, q2);
+    q0 = nan_unless(ok, q0); q1 = nan_unless(ok, q1); q2 = nan_unless(ok, q2);
 }
 
 // Orthogonal polar factor U V^T of M (calculate_9_l / calculate_9_r, rottrans.py:72-82 take it from a batched SVD) by Newton's iteration
@@ -746,14 +823,6 @@ RNF_HD void smith3(const float (&m)[9], v3f &q0, v3f &q1, v3f &q2) {
 //     non-rotation: the callers' non-finite guard sees it.  A NaN or infinite entry gives NaN as well, and so does an exact det(M) = 0.
 // Domain, error figures against LAPACK's fp32 SVD and the trip count: DESIGN.md section 3.7a, tests/test_polar3_host.py.
 // Rows of the result in p0, p1, p2; det(result) has the sign of det(M).
-RNF_HD int polar3_exponent(const float (&m)[9]) {
-    float amax = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) amax = fmaxf(amax, fabsf(m[i]));
-    return (amax > 0.f && amax <= 3.402823466e38f) ? ilogbf(amax) : 0;      // subnormals included; 0 for M = 0 and for an infinite entry
-}
-constexpr float kPolar3Orth = 16.0f * 1.1920928955078125e-7f;                 // 16 * 2^-23; a converged iterate shows <= 4 * 2^-23
-
 RNF_HD void polar3(const float (&m)[9], v3f &p0, v3f &p1, v3f &p2) {
     const int ex = polar3_exponent(m);
     p0 = v3f{ldexpf(m[0], -ex), ldexpf(m[1], -ex), ldexpf(m[2], -ex)};
@@ -769,10 +838,7 @@ RNF_HD void polar3(const float (&m)[9], v3f &p0, v3f &p1, v3f &p2) {
         p1 = p1 * a + c1 * b;
         p2 = p2 * a + c2 * b;
     }
-    const float t = kPolar3Orth;                                                      // comparisons, not fmaxf: a NaN must fail them
-    const bool ok = fabsf(dot3(p0, p0) - 1.0f) <= t && fabsf(dot3(p1, p1) - 1.0f) <= t && fabsf(dot3(p2, p2) - 1.0f) <= t &&
-                    fabsf(dot3(p0, p1)) <= t && fabsf(dot3(p0, p2)) <= t && fabsf(dot3(p1, p2)) <= t;
-    if (!ok) {
+    if (!orth3_ok(p0, p1, p2)) {
         const float q = __builtin_nanf("");
         p0 = v3f{q, q, q}; p1 = p0; p2 = p0;
     }

@@ -266,17 +266,8 @@ RNF_RARE_FN void rare_side(int kind, int dir, const float *m, const Rot *Rin, co
                 if (kind == RNF_KIND_SIDE9) {             // Condition9TransLU (squeezetrans.py:264-277): calculate_9, inverse pass M^-1
                     float M9[9], g9[9];
 #pragma unroll
-                    for (int i = 0; i < 9; ++i) { M9[i] = m[i]; g9[i] = 0.f; }
-                    if (dir) {
-                        float Mi[9], gMi[9];
-                        inv3(M9, Mi);
-#pragma unroll
-                        for (int i = 0; i < 9; ++i) gMi[i] = 0.f;
-                        gs9_backward(Mi, RinV, gRV, g_ldj, gMi, gRin);
-                        inverse_matrix_grad<3>(Mi, gMi, g9);
-                    } else {
-                        gs9_backward(M9, RinV, gRV, g_ldj, g9, gRin);
-                    }
+                    for (int i = 0; i < 9; ++i) M9[i] = m[i];
+                    cond_gs9_backward(M9, dir != 0, RinV, gRV, g_ldj, g9, gRin);
 #pragma unroll
                     for (int i = 0; i < 9; ++i) gM[i] = g9[i];
                 } else {

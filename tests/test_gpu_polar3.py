@@ -47,12 +47,13 @@ def as_features(M):
 
 
 @functools.lru_cache(maxsize=None)
-def steering(side, inverse):
-    """(cfg, weights, index of the 3x3 layer).  inverse: the flow whose INVERSE pass applies the 3x3 layer last."""
+def steering_net(rot, kind, inverse):
+    """(cfg, weights, index of the 3x3 layer) of the steering flow whose 3x3 layer is `kind` (make_config's rot=`rot`).  inverse: the flow
+    whose INVERSE pass applies the 3x3 layer last.  Shared with tests/test_gpu_gs3.py."""
     extra = dict(last_affine=1, first_affine=0) if inverse else {}
-    cfg = make_config(layers=1, segments=16, condition=1, feature_dim=FD, rot="9TransLSVD" if side == "L" else "9TransRSVD", **extra)
+    cfg = make_config(layers=1, segments=16, condition=1, feature_dim=FD, rot=rot, **extra)
     kinds = orc.layer_kinds(cfg)
-    assert kinds == (["csvdl9" if side == "L" else "csvdr9", "mobius"] if inverse else ["mobius", "csvdl9" if side == "L" else "csvdr9"])
+    assert kinds == ([kind, "mobius"] if inverse else ["mobius", kind])
     w = synth.fill_state_dict(orc.state_shapes(cfg), seed=31, regime="trained")
     i9, im = (0, 1) if inverse else (1, 0)
     pre = f"layers.{i9}.net"
@@ -66,6 +67,11 @@ def steering(side, inverse):
         w[f"{pre}.fc_last.weight"][i, 9 + i] = -1.0
     w[f"layers.{im}.conditioner.fc_first.weight"][:, 3:] = 0.0            # the Moebius layer does not see the features
     return cfg, w, i9
+
+
+def steering(side, inverse):
+    """(cfg, weights, index of the 3x3 layer).  inverse: the flow whose INVERSE pass applies the 3x3 layer last."""
+    return steering_net("9TransLSVD" if side == "L" else "9TransRSVD", "csvdl9" if side == "L" else "csvdr9", inverse)
 
 
 def assert_net_returns_D(side, inverse, feat, seen):
