@@ -454,6 +454,51 @@ int rnf_grid_modes(const RnfGridModes *modes);
  * out of range. */
 size_t rnf_grid_modes_workspace_bytes(const RnfGridModes *modes);
 
+/* Highest-density credible sets of g images' densities on one grid, and the HPD level of query log-densities (csrc/grid_credible.h).
+ * Per image, with m the maximum of its log p (the first arg-max, a NaN winning), w_i = expf(lp_i - m) (the fp32 exponential of
+ * rnf_grid_modes), the fixed-point mass W_i = rint(w_i 2^S) as an unsigned 64-bit integer and T = sum_i W_i:
+ *   threshold_j    the largest value tau among the image's log p with sum_{lp_i >= tau} W_i >= ceil(alpha_j T): the set is {lp_i >= tau},
+ *                  so ties with tau are all inside; -0 and +0 tie, and a zero threshold is reported as +0;
+ *   count_j        the number of cells with lp_i >= threshold_j (count_j / Q is the set's volume as a fraction of SO(3));
+ *   mass_j         sum_{lp_i >= tau} W_i / T;
+ *   query_mass_q   sum_{lp_i > v_q} W_i / T, a strict inequality: the HPD level of a point whose log-density is v_q (0 at the mode);
+ *   query_count_q  the number of cells with lp_i > v_q;
+ *   log_norm       m + log(T / 2^S) - log Q, rnf_grid_modes' log_norm to 1e-6.
+ * Fixed point: S = 62 - ceil(log2 Q).  w_i <= 1, so W_i <= 2^S and T <= Q 2^S <= 2^62: no sum can overflow, and integer sums do not
+ * depend on the order they are taken in -- the select's histograms are exact.  Each W_i is off by at most 1/2 and T >= 2^S (the maximum's
+ * own cell), so every reported mass fraction is within eps_fix(Q) = Q 2^-(S + 1) of the one with real-valued w_i: 1.1e-6 at level 5
+ * (Q = 72 8^5, S = 40), 6.9e-5 at level 6 (S = 37); Q is limited to 2^26 (level 6).
+ * A NaN in the image's log p, or a maximum of +inf: every threshold, mass and query mass is NaN, every count -1, log_norm NaN.  No finite
+ * value in the image: log_norm -inf, thresholds and masses NaN, counts -1.  -inf cells elsewhere weigh 0 and are never inside a set.  A NaN
+ * query has mass NaN and count -1.  Deterministic: bit-identical from run to run and whatever g.  Stream-ordered, no host
+ * synchronisation, capturable in a HIP graph. */
+typedef struct RnfGridCredible {
+    size_t struct_bytes;        /* sizeof(RnfGridCredible); any other value is refused (header and library differ) */
+    const float *logp;          /* dev float[g][Q]: image b's log p on grid row i */
+    int64_t Q;                  /* 1..2^26 */
+    int32_t g;                  /* images, 1..65535 */
+    const double *levels;       /* HOST double[n_levels]: 0 < alpha_j < 1 (read during the call) */
+    int32_t n_levels;           /* J, 1..8 */
+    const float *queries;       /* dev float[g][n_queries] log-densities, or NULL with n_queries = 0 */
+    int32_t n_queries;          /* G, 0..16 */
+    float *threshold_out;       /* dev float[g][J] */
+    int64_t *count_out;         /* dev int64[g][J] */
+    float *mass_out;            /* dev float[g][J] */
+    float *log_norm_out;        /* dev float[g] */
+    float *query_mass_out;      /* dev float[g][G]; required with n_queries > 0 */
+    int64_t *query_count_out;   /* dev int64[g][G]; required with n_queries > 0 */
+    /* dev scratch, 8-byte aligned, of at least rnf_grid_credible_workspace_bytes(this struct) bytes: with nb = min(ceil(Q / 8192), 512)
+     * blocks per image (a function of Q alone), g * (16 min(ceil(Q / 2048), 2048) + 20 + 128 J + nb (3072 J + 12 G)) rounded up to 16:
+     * the maximum's partials, the select's state and one pass's per-block histograms */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfGridCredible;
+int rnf_grid_credible(const RnfGridCredible *credible);
+/* The workspace rnf_grid_credible requires for the same struct (the pointers are not read); 0 when struct_bytes, g, Q, n_levels or
+ * n_queries are out of range. */
+size_t rnf_grid_credible_workspace_bytes(const RnfGridCredible *credible);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

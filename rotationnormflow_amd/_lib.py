@@ -52,6 +52,14 @@ class GridModes(_Pass):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class GridCredible(_Pass):
+    """RnfGridCredible (include/rnf_hip.h): highest-density credible sets and HPD levels on an SO(3) grid."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("logp", C.c_void_p), ("Q", C.c_int64), ("g", C.c_int32), ("levels", C.c_void_p),
+                ("n_levels", C.c_int32), ("queries", C.c_void_p), ("n_queries", C.c_int32), ("threshold_out", C.c_void_p),
+                ("count_out", C.c_void_p), ("mass_out", C.c_void_p), ("log_norm_out", C.c_void_p), ("query_mass_out", C.c_void_p),
+                ("query_count_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 class GridChildren(_Pass):
     """RnfGridChildren (include/rnf_hip.h): the 12 children of SO(3) grid rows one level down, and their rotations."""
     _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("parents", C.c_void_p), ("n", C.c_int64), ("offset", C.c_void_p),
@@ -137,6 +145,8 @@ _SIGNATURES = {
     "rnf_so3_healpix_grid": (C.c_int, [C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "rnf_grid_modes": (C.c_int, [C.POINTER(GridModes)]),
     "rnf_grid_modes_workspace_bytes": (C.c_size_t, [C.POINTER(GridModes)]),
+    "rnf_grid_credible": (C.c_int, [C.POINTER(GridCredible)]),
+    "rnf_grid_credible_workspace_bytes": (C.c_size_t, [C.POINTER(GridCredible)]),
     "rnf_so3_grid_children": (C.c_int, [C.POINTER(GridChildren)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),

@@ -29,6 +29,7 @@
 #include "grid_modes.h"
 #include "so3_grid.h"
 #include "grid_beam.h"
+#include "grid_credible.h"
 
 using namespace rnf;
 
@@ -1532,6 +1533,87 @@ extern "C" int rnf_grid_modes(const RnfGridModes *p) {
                        k, p->gt ? 1 : 0, (const long long *)p->index_out, (const float *)p->logp_out, p->mass_out, p->log_norm_out,
                        p->spread_out);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Credible sets on the grid (csrc/grid_credible.h): the row maximum by grid_modes.h's arg-max pass, then 4 histogram passes of the radix
+// select, each followed by its finalise.
+static const char *grid_credible_check(const RnfGridCredible *p) {
+    static thread_local char msg[256];
+    if (!p || p->struct_bytes != sizeof(RnfGridCredible)) {
+        snprintf(msg, sizeof(msg), "RnfGridCredible.struct_bytes does not match the library's %zu", sizeof(RnfGridCredible));
+        return msg;
+    }
+    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridCredible.g=%d outside 1..65535", p->g);
+    else if (p->Q < 1 || p->Q > gc::MAX_Q) snprintf(msg, sizeof(msg), "RnfGridCredible.Q=%lld outside 1..2^26", (long long)p->Q);
+    else if (p->n_levels < 1 || p->n_levels > gc::MAX_LEVELS)
+        snprintf(msg, sizeof(msg), "RnfGridCredible.n_levels=%d outside 1..%d", p->n_levels, gc::MAX_LEVELS);
+    else if (p->n_queries < 0 || p->n_queries > gc::MAX_QUERIES)
+        snprintf(msg, sizeof(msg), "RnfGridCredible.n_queries=%d outside 0..%d", p->n_queries, gc::MAX_QUERIES);
+    else return nullptr;
+    return msg;
+}
+
+extern "C" size_t rnf_grid_credible_workspace_bytes(const RnfGridCredible *p) {
+    if (const char *e = grid_credible_check(p)) {
+        fail("%s", e);
+        return 0;
+    }
+    return gc::carve(nullptr, p->Q, p->g, p->n_levels, p->n_queries).bytes;
+}
+
+extern "C" int rnf_grid_credible(const RnfGridCredible *p) {
+    if (const char *e = grid_credible_check(p)) return fail("%s", e);
+    if (!p->levels) return fail("RnfGridCredible: null levels");
+    gc::Levels levels = {};
+    for (int j = 0; j < p->n_levels; ++j) {
+        if (!(p->levels[j] > 0.0 && p->levels[j] < 1.0)) return fail("RnfGridCredible.levels[%d]=%g outside (0, 1)", j, p->levels[j]);
+        levels.a[j] = p->levels[j];
+    }
+    if (!p->logp || !p->threshold_out || !p->count_out || !p->mass_out || !p->log_norm_out)
+        return fail("RnfGridCredible: null logp or output pointer");
+    const int J = p->n_levels, G = p->n_queries;
+    if (G > 0 && (!p->queries || !p->query_mass_out || !p->query_count_out))
+        return fail("RnfGridCredible: null queries, query_mass_out or query_count_out with n_queries=%d", G);
+    const size_t need = rnf_grid_credible_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfGridCredible.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_credible_workspace_bytes)",
+                    p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridCredible.workspace must be 8-byte aligned");
+    const gc::Workspace w = gc::carve(p->workspace, p->Q, p->g, J, G);
+    const long long Q = p->Q;
+    const int nbm = (int)gm::blocks_for(Q), nb = (int)gc::blocks_for(Q), S = gc::fixed_point_shift(Q);
+    const double scale = ldexp(1.0, S);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
+                       (const long long *)w.max_index, (const float *)w.max_value, w.max_part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
+                       w.max_index, w.max_value);
+    HIP_TRY(hipGetLastError());
+    for (int pass = 0; pass < gc::PASSES; ++pass) {
+        const gc::State *prev = pass ? w.state + (size_t)(pass - 1) * p->g * J : nullptr;
+        gc::State *next = w.state + (size_t)pass * p->g * J;
+        if (pass == 0) {
+            auto first = gc::grid_credible_first_kernel<gc::MAX_QUERIES>;
+            switch (gc::query_slots(G)) {
+                case 0: first = gc::grid_credible_first_kernel<0>; break;
+                case 1: first = gc::grid_credible_first_kernel<1>; break;
+                case 4: first = gc::grid_credible_first_kernel<4>; break;
+            }
+            hipLaunchKernelGGL(first, dim3(nb, p->g), dim3(gc::THREADS), 0, s, p->logp, Q, J, p->queries, G, scale,
+                               (const float *)w.max_value, w.hist_mass, w.hist_count, w.query_mass, w.query_count);
+        } else {
+            hipLaunchKernelGGL(gc::grid_credible_pass_kernel, dim3(nb, p->g), dim3(gc::THREADS), 0, s, p->logp, Q, J, pass, scale,
+                               (const float *)w.max_value, prev, w.hist_mass, w.hist_count);
+        }
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(gc::grid_credible_final_kernel, dim3(J, p->g), dim3(gc::FINAL_THREADS), 0, s, Q, J, G, pass, nb, S, levels, p->queries,
+                           (const float *)w.max_value, (const gc::u64 *)w.hist_mass, (const unsigned *)w.hist_count,
+                           (const gc::u64 *)w.query_mass, (const unsigned *)w.query_count, prev, next, w.total, p->threshold_out,
+                           (long long *)p->count_out, p->mass_out, p->log_norm_out, p->query_mass_out, (long long *)p->query_count_out);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

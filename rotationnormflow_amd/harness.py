@@ -529,6 +529,130 @@ def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, se
     return out
 
 
+GRID_CREDIBLE_MAX_ROWS = 1 << 26                   # rnf_grid_credible's fixed point (include/rnf_hip.h): level 6 fits
+GRID_CREDIBLE_MAX_LEVELS = 8
+GRID_CREDIBLE_MAX_QUERIES = 16
+GRID_GT_ROW = 32                                    # the shortest shared row on the fast shared-row kernels (csrc/flow_plan.h)
+
+
+def _credible_levels(levels, who: str):
+    lv = [float(a) for a in (levels if isinstance(levels, (tuple, list)) else np.asarray(levels, np.float64).reshape(-1))]
+    if not 1 <= len(lv) <= GRID_CREDIBLE_MAX_LEVELS:
+        raise ValueError(f"{who}: {len(lv)} levels (1 to {GRID_CREDIBLE_MAX_LEVELS})")
+    for a in lv:
+        if not 0.0 < a < 1.0:
+            raise ValueError(f"{who}: level {a} outside (0, 1)")
+    return lv
+
+
+def grid_credible(logp: torch.Tensor, levels, queries: torch.Tensor = None):
+    """``rnf_grid_credible`` on g images' log-densities ``logp`` [g,Q] (float32, on the device): per level alpha the highest-density
+    credible set {log p >= threshold}, the smallest such set of grid cells with mass >= alpha, and per query log-density v [g,G] the mass
+    and number of the cells with log p > v (include/rnf_hip.h).
+    -> (threshold [g,J], count [g,J] int64, mass [g,J], log_norm [g], query_mass [g,G] or None, query_count [g,G] int64 or None)"""
+    from . import _lib
+    lv = _credible_levels(levels, "grid_credible")
+    g, Q = logp.shape
+    if Q > GRID_CREDIBLE_MAX_ROWS:
+        raise ValueError(f"grid_credible: {Q} grid rows (at most 2^26)")
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    J, G = len(lv), 0
+    if queries is not None:
+        queries = queries.reshape(g, -1).to(device=dev, dtype=torch.float32).contiguous()
+        G = queries.shape[1]
+        if not 1 <= G <= GRID_CREDIBLE_MAX_QUERIES:
+            raise ValueError(f"grid_credible: {G} queries per image (at most {GRID_CREDIBLE_MAX_QUERIES})")
+    threshold = torch.empty(g, J, dtype=torch.float32, device=dev)
+    count = torch.empty(g, J, dtype=torch.int64, device=dev)
+    mass = torch.empty(g, J, dtype=torch.float32, device=dev)
+    log_norm = torch.empty(g, dtype=torch.float32, device=dev)
+    query_mass = torch.empty(g, G, dtype=torch.float32, device=dev) if G else None
+    query_count = torch.empty(g, G, dtype=torch.int64, device=dev) if G else None
+    host_levels = (C.c_double * J)(*lv)
+    args = _lib.GridCredible(logp=lp.data_ptr(), Q=Q, g=g, levels=C.addressof(host_levels), n_levels=J,
+                             queries=queries.data_ptr() if G else None, n_queries=G, threshold_out=threshold.data_ptr(),
+                             count_out=count.data_ptr(), mass_out=mass.data_ptr(), log_norm_out=log_norm.data_ptr(),
+                             query_mass_out=query_mass.data_ptr() if G else None, query_count_out=query_count.data_ptr() if G else None)
+    L = _lib.lib()
+    need = L.rnf_grid_credible_workspace_bytes(C.byref(args))
+    if need == 0:
+        _lib.check(1)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(dev):
+        args.stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.rnf_grid_credible(C.byref(args)))
+    return threshold, count, mass, log_norm, query_mass, query_count
+
+
+def grid_pose_credible(flow: Flow, feature: torch.Tensor = None, levels=(0.5, 0.9, 0.95), number_queries: int = None,
+                       recursion_level: int = None, offset=None, base=None, gt_rotation=None, images_per_launch: int = None) -> dict:
+    """Highest-density credible sets of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the
+    chunk gathering of ``grid_pose_modes``): per level alpha the smallest set of grid cells {log p >= threshold} that carries mass alpha
+    under the grid-normalised density, its number of cells ``count`` and its ``volume`` = count / Q as a fraction of SO(3).  Cell masses
+    are fixed-point integers, so the sets are exact order statistics, bit-identical from run to run and for any grouping; a reported mass is
+    within Q 2^-(S+1), S = 62 - ceil(log2 Q), of the real-valued one (``rnf_grid_credible``, include/rnf_hip.h; 1.1e-6 at level 5).
+    ``gt_rotation`` [B,3,3] or [B,K,3,3] (K <= 16 symmetric ground truths) adds the calibration statistics: the flow's log-density at the
+    ground truths themselves (the densest of an image's K), evaluated like a grid row -- a ground truth that is a grid row gets that row's
+    log p bit for bit, except in flows with batch-coupled layers, whose matrices come from the first rows of a launch: there the ground
+    truths' own launch (one per image) builds them from the ground truths, not from the grid's first rows; ``gt_level`` = the mass of the
+    cells denser than it, its HPD level, uniform on [0, 1] for a calibrated model; and ``gt_inside`` [B,J] = gt_log_prob >= threshold.
+    ``gt_inside.float().mean(0)`` is the coverage curve: the fraction of images whose alpha-set holds the ground truth, alpha when
+    calibrated.  Grids above 2^26 rows (level 7) are refused.
+    -> dict(threshold [B,J], count [B,J] int64, volume [B,J], mass [B,J], log_norm [B], offset [3,3]; with gt_rotation: gt_log_prob [B],
+    gt_level [B], gt_inside [B,J] bool)"""
+    from .utils import sd
+    lv = _credible_levels(levels, "grid_pose_credible")
+    level = int(recursion_level) if recursion_level is not None else sd.closest_grid_level(500 if number_queries is None else number_queries)
+    if sd.grid_size(level) > GRID_CREDIBLE_MAX_ROWS:
+        raise ValueError(f"grid_pose_credible: level {level} has {sd.grid_size(level)} grid rows (at most 2^26)")
+    if gt_rotation is not None and gt_rotation.dim() == 4 and gt_rotation.shape[1] > GRID_CREDIBLE_MAX_QUERIES:
+        raise ValueError(f"grid_pose_credible: {gt_rotation.shape[1]} ground truths per image (at most {GRID_CREDIBLE_MAX_QUERIES})")
+    feature, dev, B, level, offset, A, c = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_pose_credible")
+    gt = None
+    if gt_rotation is not None:
+        gt = gt_rotation.reshape(B, -1, 3, 3).to(device=dev, dtype=torch.float32).contiguous()
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        Q = grid.shape[0]
+        gt_log_prob = None
+        if gt is not None:
+            # The images at their ground truths: shared rows through run_log_prob, each image's K padded with its first one to GRID_GT_ROW
+            # rotations -- rows that long run on the kernels the grid's rows run on (csrc/flow_plan.h), so a ground truth that is a grid row
+            # gets that row's log p bit for bit.  Launches hold the rows _grid_launches allows; batch-coupled flows take one image per
+            # launch, as their grids do (their matrices then come from the ground truths: see the docstring).
+            K = gt.shape[1]
+            packed = flow._packed(dev, feature)
+            coupled = any(getattr(m, "_rnf_batch_coupled", False) for m in flow.modules())
+            step = 1 if coupled else max(1, (GRID_SIDE_LAUNCH_ROWS if packed.side_layers else GRID_LAUNCH_ROWS) // GRID_GT_ROW)
+            pad = torch.cat([gt, gt[:, :1].expand(-1, GRID_GT_ROW - K, -1, -1)], dim=1)
+            parts = []
+            for b0 in range(0, B, step):
+                b1 = min(B, b0 + step)
+                rows = (A, c) if A is None or A.shape[0] == 1 else (A[b0:b1], c[b0:b1])
+                at = runtime.run_log_prob(flow, packed, pad[b0:b1].reshape(-1, 3, 3), feature[b0:b1] if feature is not None else None,
+                                          *rows, feature_repeat=GRID_GT_ROW)["logp"]
+                parts.append(at.reshape(b1 - b0, GRID_GT_ROW)[:, :K].max(dim=1).values)
+            gt_log_prob = parts[0] if len(parts) == 1 else torch.cat(parts)
+        outs, whole = [], None
+        for b0, b1, lo, lp in _grid_launches(flow, feature, grid, B, A, c, images_per_launch, "grid_pose_credible"):
+            if lp.shape[1] < Q:                                 # one image in chunks: gather them first
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            outs.append(grid_credible(lp, lv, gt_log_prob[b0:b1, None] if gt is not None else None)[:5])
+        threshold, count, mass, log_norm, gt_level = (torch.cat(t) if t[0] is not None else None for t in zip(*outs))
+    volume = torch.where(count < 0, float("nan"), count.to(torch.float32) / Q)
+    out = dict(threshold=threshold, count=count, volume=volume, mass=mass, log_norm=log_norm, offset=offset)
+    if gt is not None:
+        out.update(gt_log_prob=gt_log_prob, gt_level=gt_level[:, 0], gt_inside=gt_log_prob[:, None] >= threshold)
+    return out
+
+
 def grid_pose_fisher(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None, base=None,
                      images_per_launch: int = None) -> dict:
     """The matrix-Fisher distribution that matches each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same
