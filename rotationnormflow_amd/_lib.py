@@ -206,3 +206,20 @@ def lib():
 def check(rc: int):
     if rc != 0:
         raise RuntimeError("librnf_hip: " + lib().rnf_last_error().decode())
+
+
+def call(name: str, args, device):
+    """Run the struct entry point ``rnf_<name>`` on ``args`` (a ``_Pass``) on ``device``'s current stream.  Where the library exports
+    ``rnf_<name>_workspace_bytes`` the workspace is asked for (0: the arguments were refused, ``rnf_last_error`` says why), allocated for the
+    duration of the call -- the caching allocator's blocks are 512-byte aligned -- and entered into ``args``."""
+    import torch
+    L = lib()
+    if f"rnf_{name}_workspace_bytes" in _SIGNATURES:
+        need = getattr(L, f"rnf_{name}_workspace_bytes")(C.byref(args))
+        if need == 0:
+            check(1)
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), need
+    with torch.cuda.device(device):
+        args.stream = torch.cuda.current_stream(device).cuda_stream
+        check(getattr(L, "rnf_" + name)(C.byref(args)))

@@ -1433,31 +1433,24 @@ extern "C" int rnf_so3_grid_children(const RnfGridChildren *p) {
 }
 
 // Beam selection (csrc/grid_beam.h): passes of one-chunk-per-block sorts until one chunk per image remains.
-static const char *grid_beam_check(const RnfGridBeamSelect *p) {
-    static thread_local char msg[256];
-    if (!p || p->struct_bytes != sizeof(RnfGridBeamSelect)) {
-        snprintf(msg, sizeof(msg), "RnfGridBeamSelect.struct_bytes does not match the library's %zu", sizeof(RnfGridBeamSelect));
-        return msg;
-    }
-    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.g=%d outside 1..65535", p->g);
-    else if (p->M < 1 || p->M > gb::ROW_MAX + 1) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.M=%lld outside 1..2^31 - 1", (long long)p->M);
-    else if (p->beam < 1 || p->beam > gb::MAX_BEAM) snprintf(msg, sizeof(msg), "RnfGridBeamSelect.beam=%d outside 1..%d", p->beam, gb::MAX_BEAM);
-    else return nullptr;
-    return msg;
+static int grid_beam_check(const RnfGridBeamSelect *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridBeamSelect))
+        return fail("RnfGridBeamSelect.struct_bytes does not match the library's %zu", sizeof(RnfGridBeamSelect));
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridBeamSelect.g=%d outside 1..65535", p->g);
+    if (p->M < 1 || p->M > gb::ROW_MAX + 1) return fail("RnfGridBeamSelect.M=%lld outside 1..2^31 - 1", (long long)p->M);
+    if (p->beam < 1 || p->beam > gb::MAX_BEAM) return fail("RnfGridBeamSelect.beam=%d outside 1..%d", p->beam, gb::MAX_BEAM);
+    return 0;
 }
 
 extern "C" size_t rnf_grid_beam_select_workspace_bytes(const RnfGridBeamSelect *p) {
-    if (const char *e = grid_beam_check(p)) {
-        fail("%s", e);
-        return 0;
-    }
+    if (grid_beam_check(p)) return 0;
     const long long nb = gb::blocks_for(p->M);
     // two ping-pong buffers of the first pass's keys; 8 bytes when a single pass suffices (never 0, which means an error)
     return nb > 1 ? 2 * (size_t)p->g * (size_t)nb * (size_t)p->beam * sizeof(unsigned long long) : 8;
 }
 
 extern "C" int rnf_grid_beam_select(const RnfGridBeamSelect *p) {
-    if (const char *e = grid_beam_check(p)) return fail("%s", e);
+    if (grid_beam_check(p)) return 1;
     if (!p->logp || !p->rows_out || !p->logp_out) return fail("RnfGridBeamSelect: null logp or output pointer");
     const size_t need = rnf_grid_beam_select_workspace_bytes(p);
     if (!p->workspace || p->workspace_bytes < need)
@@ -1482,29 +1475,22 @@ extern "C" int rnf_grid_beam_select(const RnfGridBeamSelect *p) {
 }
 
 // Top-k pose modes on the grid (csrc/grid_modes.h): k arg-max passes and one mass pass, each followed by its per-image finalise.
-static const char *grid_modes_check(const RnfGridModes *p) {
-    static thread_local char msg[256];
-    if (!p || p->struct_bytes != sizeof(RnfGridModes)) {
-        snprintf(msg, sizeof(msg), "RnfGridModes.struct_bytes does not match the library's %zu", sizeof(RnfGridModes));
-        return msg;
-    }
-    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridModes.g=%d outside 1..65535", p->g);
-    else if (p->Q < 1) snprintf(msg, sizeof(msg), "RnfGridModes.Q=%lld must be >= 1", (long long)p->Q);
-    else if (p->top_k < 1 || p->top_k > gm::MAX_K) snprintf(msg, sizeof(msg), "RnfGridModes.top_k=%d outside 1..%d", p->top_k, gm::MAX_K);
-    else return nullptr;
-    return msg;
+static int grid_modes_check(const RnfGridModes *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridModes))
+        return fail("RnfGridModes.struct_bytes does not match the library's %zu", sizeof(RnfGridModes));
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridModes.g=%d outside 1..65535", p->g);
+    if (p->Q < 1) return fail("RnfGridModes.Q=%lld must be >= 1", (long long)p->Q);
+    if (p->top_k < 1 || p->top_k > gm::MAX_K) return fail("RnfGridModes.top_k=%d outside 1..%d", p->top_k, gm::MAX_K);
+    return 0;
 }
 
 extern "C" size_t rnf_grid_modes_workspace_bytes(const RnfGridModes *p) {
-    if (const char *e = grid_modes_check(p)) {
-        fail("%s", e);
-        return 0;
-    }
+    if (grid_modes_check(p)) return 0;
     return (size_t)p->g * (size_t)gm::blocks_for(p->Q) * sizeof(double) * (size_t)(p->top_k + 2);
 }
 
 extern "C" int rnf_grid_modes(const RnfGridModes *p) {
-    if (const char *e = grid_modes_check(p)) return fail("%s", e);
+    if (grid_modes_check(p)) return 1;
     if (!(p->separation_rad > 0.0 && p->separation_rad <= M_PI))
         return fail("RnfGridModes.separation_rad=%g outside (0, pi]", p->separation_rad);
     if (!p->logp || !p->grid || !p->index_out || !p->logp_out || !p->mass_out || !p->log_norm_out)
@@ -1538,32 +1524,25 @@ extern "C" int rnf_grid_modes(const RnfGridModes *p) {
 
 // Credible sets on the grid (csrc/grid_credible.h): the row maximum by grid_modes.h's arg-max pass, then 4 histogram passes of the radix
 // select, each followed by its finalise.
-static const char *grid_credible_check(const RnfGridCredible *p) {
-    static thread_local char msg[256];
-    if (!p || p->struct_bytes != sizeof(RnfGridCredible)) {
-        snprintf(msg, sizeof(msg), "RnfGridCredible.struct_bytes does not match the library's %zu", sizeof(RnfGridCredible));
-        return msg;
-    }
-    if (p->g < 1 || p->g > 65535) snprintf(msg, sizeof(msg), "RnfGridCredible.g=%d outside 1..65535", p->g);
-    else if (p->Q < 1 || p->Q > gc::MAX_Q) snprintf(msg, sizeof(msg), "RnfGridCredible.Q=%lld outside 1..2^26", (long long)p->Q);
-    else if (p->n_levels < 1 || p->n_levels > gc::MAX_LEVELS)
-        snprintf(msg, sizeof(msg), "RnfGridCredible.n_levels=%d outside 1..%d", p->n_levels, gc::MAX_LEVELS);
-    else if (p->n_queries < 0 || p->n_queries > gc::MAX_QUERIES)
-        snprintf(msg, sizeof(msg), "RnfGridCredible.n_queries=%d outside 0..%d", p->n_queries, gc::MAX_QUERIES);
-    else return nullptr;
-    return msg;
+static int grid_credible_check(const RnfGridCredible *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridCredible))
+        return fail("RnfGridCredible.struct_bytes does not match the library's %zu", sizeof(RnfGridCredible));
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridCredible.g=%d outside 1..65535", p->g);
+    if (p->Q < 1 || p->Q > gc::MAX_Q) return fail("RnfGridCredible.Q=%lld outside 1..2^26", (long long)p->Q);
+    if (p->n_levels < 1 || p->n_levels > gc::MAX_LEVELS)
+        return fail("RnfGridCredible.n_levels=%d outside 1..%d", p->n_levels, gc::MAX_LEVELS);
+    if (p->n_queries < 0 || p->n_queries > gc::MAX_QUERIES)
+        return fail("RnfGridCredible.n_queries=%d outside 0..%d", p->n_queries, gc::MAX_QUERIES);
+    return 0;
 }
 
 extern "C" size_t rnf_grid_credible_workspace_bytes(const RnfGridCredible *p) {
-    if (const char *e = grid_credible_check(p)) {
-        fail("%s", e);
-        return 0;
-    }
+    if (grid_credible_check(p)) return 0;
     return gc::carve(nullptr, p->Q, p->g, p->n_levels, p->n_queries).bytes;
 }
 
 extern "C" int rnf_grid_credible(const RnfGridCredible *p) {
-    if (const char *e = grid_credible_check(p)) return fail("%s", e);
+    if (grid_credible_check(p)) return 1;
     if (!p->levels) return fail("RnfGridCredible: null levels");
     gc::Levels levels = {};
     for (int j = 0; j < p->n_levels; ++j) {
@@ -1889,31 +1868,23 @@ __global__ __launch_bounds__(64) void rotation_moments_final_kernel(const double
 }
 }  // namespace rmom
 
-static const char *rotation_moments_check(const RnfRotationMoments *p) {
-    static thread_local char msg[256];
-    if (!p || p->struct_bytes != sizeof(RnfRotationMoments)) {
-        snprintf(msg, sizeof(msg), "RnfRotationMoments.struct_bytes does not match the library's %zu", sizeof(RnfRotationMoments));
-        return msg;
-    }
-    if (p->G < 1) snprintf(msg, sizeof(msg), "RnfRotationMoments.G=%lld must be >= 1", (long long)p->G);
-    else if (p->n < 1 || p->n > (1LL << 40)) snprintf(msg, sizeof(msg), "RnfRotationMoments.n=%lld outside 1..2^40", (long long)p->n);
-    else if ((double)p->G * (double)rmom::chunks_for(p->n) > 2147483647.0)
-        snprintf(msg, sizeof(msg), "RnfRotationMoments: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G,
-                 rmom::chunks_for(p->n));
-    else return nullptr;
-    return msg;
+static int rotation_moments_check(const RnfRotationMoments *p) {
+    if (!p || p->struct_bytes != sizeof(RnfRotationMoments))
+        return fail("RnfRotationMoments.struct_bytes does not match the library's %zu", sizeof(RnfRotationMoments));
+    if (p->G < 1) return fail("RnfRotationMoments.G=%lld must be >= 1", (long long)p->G);
+    if (p->n < 1 || p->n > (1LL << 40)) return fail("RnfRotationMoments.n=%lld outside 1..2^40", (long long)p->n);
+    if ((double)p->G * (double)rmom::chunks_for(p->n) > 2147483647.0)
+        return fail("RnfRotationMoments: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G, rmom::chunks_for(p->n));
+    return 0;
 }
 
 extern "C" size_t rnf_rotation_moments_workspace_bytes(const RnfRotationMoments *p) {
-    if (const char *e = rotation_moments_check(p)) {
-        fail("%s", e);
-        return 0;
-    }
+    if (rotation_moments_check(p)) return 0;
     return (size_t)p->G * (size_t)rmom::chunks_for(p->n) * rmom::SLOTS * sizeof(double);
 }
 
 extern "C" int rnf_rotation_moments(const RnfRotationMoments *p) {
-    if (const char *e = rotation_moments_check(p)) return fail("%s", e);
+    if (rotation_moments_check(p)) return 1;
     if (!p->rotations || !p->moments_out) return fail("RnfRotationMoments: null rotations or moments_out");
     if (p->shared_rotations && !p->log_weights) return fail("RnfRotationMoments.shared_rotations needs log_weights (every group would get the same moment)");
     const size_t need = rnf_rotation_moments_workspace_bytes(p);
@@ -2177,37 +2148,29 @@ static inline long long chunks_for(long long n) { return (n + kMixChunk - 1) / k
         default: { constexpr int KK = 8; __VA_ARGS__; } break;                                                                             \
     }
 
-static const char *fisher_mixture_check(const RnfFisherMixtureFit *p) {
-    static thread_local char msg[256];
-    if (!p || p->struct_bytes != sizeof(RnfFisherMixtureFit)) {
-        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherMixtureFit));
-        return msg;
-    }
-    if (p->G < 1 || p->G > 0x7fffffffLL) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.G=%lld outside 1..2^31-1", (long long)p->G);
-    else if (p->n < 1 || p->n > (1LL << 40)) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.n=%lld outside 1..2^40", (long long)p->n);
-    else if (p->K < 1 || p->K > kMixMaxK) snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.K=%d outside 1..%d", (int)p->K, kMixMaxK);
-    else if (p->iterations < 1 || p->iterations > kMixMaxIterations)
-        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit.iterations=%d outside 1..%d", (int)p->iterations, kMixMaxIterations);
-    else if ((double)p->G * (double)rmix::chunks_for(p->n) > 2147483647.0)
-        snprintf(msg, sizeof(msg), "RnfFisherMixtureFit: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G,
-                 rmix::chunks_for(p->n));
-    else return nullptr;
-    return msg;
+static int fisher_mixture_check(const RnfFisherMixtureFit *p) {
+    if (!p || p->struct_bytes != sizeof(RnfFisherMixtureFit))
+        return fail("RnfFisherMixtureFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherMixtureFit));
+    if (p->G < 1 || p->G > 0x7fffffffLL) return fail("RnfFisherMixtureFit.G=%lld outside 1..2^31-1", (long long)p->G);
+    if (p->n < 1 || p->n > (1LL << 40)) return fail("RnfFisherMixtureFit.n=%lld outside 1..2^40", (long long)p->n);
+    if (p->K < 1 || p->K > kMixMaxK) return fail("RnfFisherMixtureFit.K=%d outside 1..%d", (int)p->K, kMixMaxK);
+    if (p->iterations < 1 || p->iterations > kMixMaxIterations)
+        return fail("RnfFisherMixtureFit.iterations=%d outside 1..%d", (int)p->iterations, kMixMaxIterations);
+    if ((double)p->G * (double)rmix::chunks_for(p->n) > 2147483647.0)
+        return fail("RnfFisherMixtureFit: G=%lld groups of %lld chunks are more than one launch serves", (long long)p->G, rmix::chunks_for(p->n));
+    return 0;
 }
 
 // workspace, in doubles: chunk partials [G][nchunk][10 K + 3] | chunk maxima in the layout of rotation_moments_max_kernel [G][nchunk][11] |
 // c [G][K] | finished flags [G] (int32, one per 8 bytes)
 extern "C" size_t rnf_fisher_mixture_fit_workspace_bytes(const RnfFisherMixtureFit *p) {
-    if (const char *e = fisher_mixture_check(p)) {
-        fail("%s", e);
-        return 0;
-    }
+    if (fisher_mixture_check(p)) return 0;
     const size_t cells = (size_t)p->G * (size_t)rmix::chunks_for(p->n);
     return (cells * (size_t)(mix_slots(p->K) + rmom::SLOTS) + (size_t)p->G * (size_t)p->K + (size_t)p->G) * sizeof(double);
 }
 
 extern "C" int rnf_fisher_mixture_fit(const RnfFisherMixtureFit *p) {
-    if (const char *e = fisher_mixture_check(p)) return fail("%s", e);
+    if (fisher_mixture_check(p)) return 1;
     if (!p->rotations || !p->A_init || !p->A_out || !p->log_pi_out || !p->loglik_out || !p->status_out || !p->iterations_out)
         return fail("RnfFisherMixtureFit: null rotations, A_init, A_out, log_pi_out, loglik_out, status_out or iterations_out");
     if (p->shared_rotations && !p->log_weights) return fail("RnfFisherMixtureFit.shared_rotations needs log_weights (every group would be the same)");

@@ -1,0 +1,486 @@
+"""The grid analyses: evaluate a flow's log-density on the HEALPix grid over SO(3) (``utils.sd``) and reduce each image's row on the
+device -- the arg-max of ``eval.py``'s ``log_pdf`` mode (``grid_estimate_rotations``), top-k modes with their mass (``grid_pose_modes``),
+highest-density credible sets (``grid_pose_credible``), matrix-Fisher and mixture fits (``grid_pose_fisher``, ``grid_pose_mixture``) and the
+coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path from (flow, feature, base) to log-density rows
+(``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_children`` and ``grid_beam_select`` are the reductions' entry points of the
+library on rows already at hand.  ``harness`` re-exports the public functions.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, runtime
+from .flow.flow import Flow
+from .utils import fisher, sd
+
+
+# Rotations per launch of the grid search: images are grouped up to about 2^21 rotations (the regime the shared-row kernels are measured
+# in); a single image's grid larger than GRID_MAX_LAUNCH_ROWS is evaluated in chunks of that size.  Flows with side layers take one feature
+# row per rotation (runtime.expand_shared_rows), so their launches are kept to GRID_SIDE_LAUNCH_ROWS to bound the expanded features.
+GRID_LAUNCH_ROWS = 1 << 21
+GRID_MAX_LAUNCH_ROWS = 1 << 24
+GRID_SIDE_LAUNCH_ROWS = 1 << 18
+
+
+def _batch_coupled(flow: Flow) -> list:
+    """Names of ``flow``'s layer classes whose matrices come from the first rows of a launch."""
+    return sorted({type(m).__name__ for m in flow.modules() if getattr(m, "_rnf_batch_coupled", False)})
+
+
+def _refuse_batch_coupled(flow: Flow, who: str, consequence: str = ""):
+    coupled = _batch_coupled(flow)
+    if coupled:
+        raise ValueError(f"{who}: batch-coupled layers ({', '.join(coupled)}) take their matrices from a launch's first rows{consequence}; "
+                         "use grid_estimate_rotations")
+
+
+class _GridFlow:
+    """The one path from (flow, feature rows, base rows) to log-density rows: B images' feature [B,F] (or None) and base (A [1|B,3,3], c)
+    (or None, None), the flow's packed image and what bounds a launch.  Call its methods under no_grad."""
+
+    def __init__(self, flow: Flow, feature, B, A, c, dev):
+        self.flow, self.feature, self.B, self.A, self.c, self.dev = flow, feature, B, A, c, dev
+        self.packed = flow._packed(dev, feature)
+        self.coupled = bool(_batch_coupled(flow))
+
+    @property
+    def budget(self):
+        """Rotations per launch (the module's constants, read at call time)."""
+        return GRID_SIDE_LAUNCH_ROWS if self.packed.side_layers else GRID_LAUNCH_ROWS
+
+    def log_prob(self, rot, b0, b1, repeat):
+        """log p [(b1 - b0) * repeat] of ``rot`` [(b1 - b0) * repeat,3,3]: ``repeat`` consecutive rotations per image b0..b1-1, which share the
+        image's feature row and base row."""
+        feat = self.feature[b0:b1] if self.feature is not None else None
+        rows = (self.A, self.c) if self.A is None or self.A.shape[0] == 1 else (self.A[b0:b1], self.c[b0:b1])
+        return runtime.run_log_prob(self.flow, self.packed, rot, feat, *rows, feature_repeat=repeat)["logp"]
+
+    def launches(self, grid, images_per_launch, who: str):
+        """Evaluate the images' log-density on ``grid`` [Q,3,3] in launches of about GRID_LAUNCH_ROWS shared-row rotations.
+        Yields (b0, b1, lo, logp [b1 - b0, rows]) per launch: images b0..b1-1 on grid rows lo..lo+rows-1 -- whole images (lo = 0, rows = Q)
+        when several share a launch, consecutive chunks of one image otherwise."""
+        Q, B = grid.shape[0], self.B
+        if images_per_launch is None:
+            images_per_launch = 1 if self.coupled else max(1, self.budget // Q)
+        g = min(int(images_per_launch), B)
+        if g < 1 or (self.coupled and g > 1):
+            raise ValueError(f"{who}: images_per_launch={images_per_launch}" + (" (batch-coupled layers: 1)" if self.coupled else ""))
+        if g > 1 and g * Q > GRID_MAX_LAUNCH_ROWS:
+            raise ValueError(f"{who}: {g} images of {Q} rotations exceed {GRID_MAX_LAUNCH_ROWS} rotations per launch")
+        chunk = Q if g > 1 else min(Q, GRID_SIDE_LAUNCH_ROWS if self.packed.side_layers else GRID_MAX_LAUNCH_ROWS)
+        rep = grid.repeat(g, 1, 1) if g > 1 else grid          # one image per launch: the grid itself, no copy
+        for b0 in range(0, B, g):
+            b1 = min(B, b0 + g)
+            if g > 1:
+                yield b0, b1, 0, self.log_prob(rep[:(b1 - b0) * Q], b0, b1, Q).reshape(b1 - b0, Q)
+                continue
+            for lo in range(0, Q, chunk):
+                part = grid[lo:lo + chunk]
+                yield b0, b1, lo, self.log_prob(part, b0, b1, part.shape[0]).reshape(1, -1)
+
+    def images(self, grid, images_per_launch, who: str):
+        """``launches`` by whole images: yields (b0, b1, logp [b1 - b0, Q]).  An image evaluated in chunks has them gathered into one [1,Q]
+        float32 buffer, which the next such image overwrites (in stream order): reduce it before asking for the next."""
+        Q, whole = grid.shape[0], None
+        for b0, b1, lo, lp in self.launches(grid, images_per_launch, who):
+            if lp.shape[1] < Q:                                 # one image in chunks: gather them first
+                if whole is None:
+                    whole = torch.empty(1, Q, dtype=torch.float32, device=self.dev)
+                whole[:, lo:lo + lp.shape[1]] = lp
+                if lo + lp.shape[1] < Q:
+                    continue
+                lp = whole
+            yield b0, b1, lp
+
+
+def _grid_inputs(flow: Flow, feature, number_queries, recursion_level, offset, base, who: str):
+    """The common arguments of the grid searches -> (_GridFlow of the B images, level, offset [3,3])."""
+    if not flow.condition:
+        feature = None
+    if feature is not None:
+        dev, B = feature.device, feature.shape[0]
+    else:
+        dev = base.A.device if base is not None else torch.device("cuda", torch.cuda.current_device())
+        B = base.A.reshape(-1, 3, 3).shape[0] if base is not None else 1
+    if dev.type != "cuda":
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    level = int(recursion_level) if recursion_level is not None else sd.closest_grid_level(500 if number_queries is None else number_queries)
+    if offset is None:
+        offset = sd.random_rotations(1)[0]
+    offset = offset.reshape(3, 3).to(device=dev, dtype=torch.float32)
+    A = c = None
+    if base is not None:
+        A = base.A.detach().reshape(-1, 3, 3).to(device=dev, dtype=torch.float32)
+        c = base.log_const().reshape(-1).to(device=dev, dtype=torch.float32)
+        if A.shape[0] not in (1, B):
+            raise ValueError(f"{who}: the base has {A.shape[0]} rows for {B} images (1 or {B})")
+    return _GridFlow(flow, feature, B, A, c, dev), level, offset
+
+
+def _grid_launches(flow: Flow, feature, grid, B, A, c, images_per_launch, who: str):
+    """``_GridFlow.launches`` for B images given as their feature [B,F] (or None) and base rows (A, c) (or None, None)."""
+    return _GridFlow(flow, feature, B, A, c, grid.device).launches(grid, images_per_launch, who)
+
+
+def grid_estimate_rotations(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None,
+                            base=None, images_per_launch: int = None):
+    """Grid-search pose estimate of ``eval.py``'s ``log_pdf`` mode (eval.py:437-462): evaluate each image's log-density on the HEALPix grid
+    over SO(3) (``utils.sd``; level ``recursion_level``, or the one closest to ``number_queries``, default 500, in log space) multiplied on
+    the right by ``offset`` [3,3] (None: one Haar-uniform rotation drawn from torch's generator, as ``trans.random_rotation()``), and keep
+    the grid point of largest log p (``torch.argmax``: the first on a tie).
+
+    feature [B,F] (None for an unconditional flow: B = the base's rows, or 1).  ``base``: None (uniform) or a ``MatrixFisherN`` with one row
+    (shared by every image) or B rows (row b scores image b's grid; its log-constants are sliced, never recomputed on a slice).
+    ``images_per_launch``: images evaluated per launch (default: as many as fit in about 2^21 rotations; 1 for flows with batch-coupled
+    layers, whose matrices come from the first rows of a launch, as in the reference's per-image chunks).
+    Returns (est [B,3,3], max_log_prob [B], index [B] into the grid, offset [3,3])."""
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_estimate_rotations")
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        bests, indices = [], []
+        for b0, b1, lo, lp in gf.launches(grid, images_per_launch, "grid_estimate_rotations"):
+            if b1 - b0 > 1:
+                idx = torch.argmax(lp, dim=-1)
+                bests.append(lp.gather(1, idx[:, None])[:, 0])
+                indices.append(idx)
+                continue
+            lp = lp[0]                                          # the first chunk's maximum wins a tie, a NaN wins as in torch.argmax
+            idx = torch.argmax(lp)
+            val = lp[idx]
+            if lo == 0:
+                v, i = val, idx
+            else:
+                take = (val > v) | (val.isnan() & ~v.isnan())
+                v, i = torch.where(take, val, v), torch.where(take, idx + lo, i)
+            if lo + lp.shape[0] == grid.shape[0]:
+                bests.append(v.reshape(1))
+                indices.append(i.reshape(1))
+        best, index = (bests[0], indices[0]) if len(bests) == 1 else (torch.cat(bests), torch.cat(indices))
+        est = grid[index]
+    return est, best, index, offset
+
+
+def grid_modes(logp: torch.Tensor, grid: torch.Tensor, top_k: int, separation_rad: float, gt: torch.Tensor = None):
+    """``rnf_grid_modes`` on g images' log-densities ``logp`` [g,Q] (float32, on the device) over ``grid`` [Q,3,3]: the top-k modes
+    separated by ``separation_rad`` and the mass each carries (include/rnf_hip.h).  ``gt``: None or [g,K,3,3] ground truths for the spread.
+    -> (index [g,k] int64, log_prob [g,k], mass [g,k], log_norm [g], spread [g] in radians or None)"""
+    g, Q = logp.shape
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    grid = grid.reshape(Q, 9).to(torch.float32).contiguous()
+    gt = None if gt is None else gt.reshape(g, -1, 9).to(device=dev, dtype=torch.float32).contiguous()
+    index = torch.empty(g, top_k, dtype=torch.int64, device=dev)
+    log_prob = torch.empty(g, top_k, dtype=torch.float32, device=dev)
+    mass = torch.empty(g, top_k, dtype=torch.float32, device=dev)
+    log_norm = torch.empty(g, dtype=torch.float32, device=dev)
+    spread = torch.empty(g, dtype=torch.float32, device=dev) if gt is not None else None
+    args = _lib.GridModes(logp=lp.data_ptr(), grid=grid.data_ptr(), Q=Q, g=g, top_k=int(top_k), separation_rad=float(separation_rad),
+                          gt=gt.data_ptr() if gt is not None else None, n_gt=gt.shape[1] if gt is not None else 0,
+                          index_out=index.data_ptr(), logp_out=log_prob.data_ptr(), mass_out=mass.data_ptr(),
+                          log_norm_out=log_norm.data_ptr(), spread_out=spread.data_ptr() if spread is not None else None)
+    _lib.call("grid_modes", args, dev)
+    return index, log_prob, mass, log_norm, spread
+
+
+def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, separation_deg: float = 15.0, number_queries: int = None,
+                    recursion_level: int = None, offset=None, base=None, gt_rotation=None, images_per_launch: int = None) -> dict:
+    """The ``top_k`` pose modes of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches), at least
+    ``separation_deg`` apart, with the probability mass of each.  Grid cells have equal Haar volume and the flow's density is relative to the
+    normalised Haar measure, so exp(log p_i) / Q is cell i's mass; ``log_norm`` = log(sum_i exp(log p_i) / Q) tends to 0 as the grid level
+    grows.  Mode 0 is ``grid_estimate_rotations``'s estimate; mode j the first arg-max among the points at least ``separation_deg`` from
+    modes 0..j-1, its mass that of the points within ``separation_deg`` of it and of no earlier mode (``rnf_grid_modes``,
+    include/rnf_hip.h).  Modes that do not exist have index -1, log p -inf, mass 0 and NaN rotations.  ``gt_rotation`` [B,K,3,3] or
+    [B,3,3] adds IPDF's spread: the expected angle (degrees) to the closest ground truth under the grid-normalised mass.
+    An image whose grid is evaluated in chunks (more than 2^24 rows, level >= 6; 2^18 with side layers) has its chunks gathered into one
+    [Q] float32 buffer (4 bytes per grid row) before the reduction.
+    -> dict(est [B,k,3,3], log_prob [B,k], index [B,k] int64, mass [B,k], log_norm [B], spread_deg [B] (with gt_rotation), offset [3,3])"""
+    if not 1 <= int(top_k) <= 16:
+        raise ValueError(f"grid_pose_modes: top_k={top_k} outside 1..16")
+    if not 0.0 < float(separation_deg) <= 180.0:
+        raise ValueError(f"grid_pose_modes: separation_deg={separation_deg} outside (0, 180]")
+    k, sep = int(top_k), float(np.deg2rad(np.float64(separation_deg)))
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_pose_modes")
+    gt = None
+    if gt_rotation is not None:
+        gt = gt_rotation.reshape(gf.B, -1, 3, 3).to(device=gf.dev, dtype=torch.float32)
+        if gt.shape[1] > 128:
+            raise ValueError(f"grid_pose_modes: {gt.shape[1]} ground truths per image (at most 128)")
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        outs = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, "grid_pose_modes"):
+            outs.append(grid_modes(lp, grid, k, sep, gt[b0:b1] if gt is not None else None))
+        index, log_prob, mass, log_norm, spread = (torch.cat(t) if t[0] is not None else None for t in zip(*outs))
+        est = grid[index.clamp(min=0)]
+        est[index < 0] = float("nan")
+    out = dict(est=est, log_prob=log_prob, index=index, mass=mass, log_norm=log_norm, offset=offset)
+    if gt is not None:
+        out["spread_deg"] = torch.rad2deg(spread)
+    return out
+
+
+GRID_CREDIBLE_MAX_ROWS = 1 << 26                   # rnf_grid_credible's fixed point (include/rnf_hip.h): level 6 fits
+GRID_CREDIBLE_MAX_LEVELS = 8
+GRID_CREDIBLE_MAX_QUERIES = 16
+GRID_GT_ROW = 32                                    # the shortest shared row on the fast shared-row kernels (csrc/flow_plan.h)
+
+
+def _credible_levels(levels, who: str):
+    lv = [float(a) for a in (levels if isinstance(levels, (tuple, list)) else np.asarray(levels, np.float64).reshape(-1))]
+    if not 1 <= len(lv) <= GRID_CREDIBLE_MAX_LEVELS:
+        raise ValueError(f"{who}: {len(lv)} levels (1 to {GRID_CREDIBLE_MAX_LEVELS})")
+    for a in lv:
+        if not 0.0 < a < 1.0:
+            raise ValueError(f"{who}: level {a} outside (0, 1)")
+    return lv
+
+
+def grid_credible(logp: torch.Tensor, levels, queries: torch.Tensor = None):
+    """``rnf_grid_credible`` on g images' log-densities ``logp`` [g,Q] (float32, on the device): per level alpha the highest-density
+    credible set {log p >= threshold}, the smallest such set of grid cells with mass >= alpha, and per query log-density v [g,G] the mass
+    and number of the cells with log p > v (include/rnf_hip.h).
+    -> (threshold [g,J], count [g,J] int64, mass [g,J], log_norm [g], query_mass [g,G] or None, query_count [g,G] int64 or None)"""
+    lv = _credible_levels(levels, "grid_credible")
+    g, Q = logp.shape
+    if Q > GRID_CREDIBLE_MAX_ROWS:
+        raise ValueError(f"grid_credible: {Q} grid rows (at most 2^26)")
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    J, G = len(lv), 0
+    if queries is not None:
+        queries = queries.reshape(g, -1).to(device=dev, dtype=torch.float32).contiguous()
+        G = queries.shape[1]
+        if not 1 <= G <= GRID_CREDIBLE_MAX_QUERIES:
+            raise ValueError(f"grid_credible: {G} queries per image (at most {GRID_CREDIBLE_MAX_QUERIES})")
+    threshold = torch.empty(g, J, dtype=torch.float32, device=dev)
+    count = torch.empty(g, J, dtype=torch.int64, device=dev)
+    mass = torch.empty(g, J, dtype=torch.float32, device=dev)
+    log_norm = torch.empty(g, dtype=torch.float32, device=dev)
+    query_mass = torch.empty(g, G, dtype=torch.float32, device=dev) if G else None
+    query_count = torch.empty(g, G, dtype=torch.int64, device=dev) if G else None
+    host_levels = (C.c_double * J)(*lv)
+    args = _lib.GridCredible(logp=lp.data_ptr(), Q=Q, g=g, levels=C.addressof(host_levels), n_levels=J,
+                             queries=queries.data_ptr() if G else None, n_queries=G, threshold_out=threshold.data_ptr(),
+                             count_out=count.data_ptr(), mass_out=mass.data_ptr(), log_norm_out=log_norm.data_ptr(),
+                             query_mass_out=query_mass.data_ptr() if G else None, query_count_out=query_count.data_ptr() if G else None)
+    _lib.call("grid_credible", args, dev)
+    return threshold, count, mass, log_norm, query_mass, query_count
+
+
+def grid_pose_credible(flow: Flow, feature: torch.Tensor = None, levels=(0.5, 0.9, 0.95), number_queries: int = None,
+                       recursion_level: int = None, offset=None, base=None, gt_rotation=None, images_per_launch: int = None) -> dict:
+    """Highest-density credible sets of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the
+    chunk gathering of ``grid_pose_modes``): per level alpha the smallest set of grid cells {log p >= threshold} that carries mass alpha
+    under the grid-normalised density, its number of cells ``count`` and its ``volume`` = count / Q as a fraction of SO(3).  Cell masses
+    are fixed-point integers, so the sets are exact order statistics, bit-identical from run to run and for any grouping; a reported mass is
+    within Q 2^-(S+1), S = 62 - ceil(log2 Q), of the real-valued one (``rnf_grid_credible``, include/rnf_hip.h; 1.1e-6 at level 5).
+    ``gt_rotation`` [B,3,3] or [B,K,3,3] (K <= 16 symmetric ground truths) adds the calibration statistics: the flow's log-density at the
+    ground truths themselves (the densest of an image's K), evaluated like a grid row -- a ground truth that is a grid row gets that row's
+    log p bit for bit, except in flows with batch-coupled layers, whose matrices come from the first rows of a launch: there the ground
+    truths' own launch (one per image) builds them from the ground truths, not from the grid's first rows; ``gt_level`` = the mass of the
+    cells denser than it, its HPD level, uniform on [0, 1] for a calibrated model; and ``gt_inside`` [B,J] = gt_log_prob >= threshold.
+    ``gt_inside.float().mean(0)`` is the coverage curve: the fraction of images whose alpha-set holds the ground truth, alpha when
+    calibrated.  Grids above 2^26 rows (level 7) are refused.
+    -> dict(threshold [B,J], count [B,J] int64, volume [B,J], mass [B,J], log_norm [B], offset [3,3]; with gt_rotation: gt_log_prob [B],
+    gt_level [B], gt_inside [B,J] bool)"""
+    lv = _credible_levels(levels, "grid_pose_credible")
+    level = int(recursion_level) if recursion_level is not None else sd.closest_grid_level(500 if number_queries is None else number_queries)
+    if sd.grid_size(level) > GRID_CREDIBLE_MAX_ROWS:
+        raise ValueError(f"grid_pose_credible: level {level} has {sd.grid_size(level)} grid rows (at most 2^26)")
+    if gt_rotation is not None and gt_rotation.dim() == 4 and gt_rotation.shape[1] > GRID_CREDIBLE_MAX_QUERIES:
+        raise ValueError(f"grid_pose_credible: {gt_rotation.shape[1]} ground truths per image (at most {GRID_CREDIBLE_MAX_QUERIES})")
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_pose_credible")
+    B = gf.B
+    gt = None
+    if gt_rotation is not None:
+        gt = gt_rotation.reshape(B, -1, 3, 3).to(device=gf.dev, dtype=torch.float32).contiguous()
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        Q = grid.shape[0]
+        gt_log_prob = None
+        if gt is not None:
+            # The images at their ground truths: shared rows through run_log_prob, each image's K padded with its first one to GRID_GT_ROW
+            # rotations -- rows that long run on the kernels the grid's rows run on (csrc/flow_plan.h), so a ground truth that is a grid row
+            # gets that row's log p bit for bit.  Launches hold the rows the grid's launches may; batch-coupled flows take one image per
+            # launch, as their grids do (their matrices then come from the ground truths: see the docstring).
+            K = gt.shape[1]
+            step = 1 if gf.coupled else max(1, gf.budget // GRID_GT_ROW)
+            pad = torch.cat([gt, gt[:, :1].expand(-1, GRID_GT_ROW - K, -1, -1)], dim=1)
+            parts = []
+            for b0 in range(0, B, step):
+                b1 = min(B, b0 + step)
+                at = gf.log_prob(pad[b0:b1].reshape(-1, 3, 3), b0, b1, GRID_GT_ROW)
+                parts.append(at.reshape(b1 - b0, GRID_GT_ROW)[:, :K].max(dim=1).values)
+            gt_log_prob = parts[0] if len(parts) == 1 else torch.cat(parts)
+        outs = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, "grid_pose_credible"):
+            outs.append(grid_credible(lp, lv, gt_log_prob[b0:b1, None] if gt is not None else None)[:5])
+        threshold, count, mass, log_norm, gt_level = (torch.cat(t) if t[0] is not None else None for t in zip(*outs))
+    volume = torch.where(count < 0, float("nan"), count.to(torch.float32) / Q)
+    out = dict(threshold=threshold, count=count, volume=volume, mass=mass, log_norm=log_norm, offset=offset)
+    if gt is not None:
+        out.update(gt_log_prob=gt_log_prob, gt_level=gt_level[:, 0], gt_inside=gt_log_prob[:, None] >= threshold)
+    return out
+
+
+def grid_pose_fisher(flow: Flow, feature: torch.Tensor = None, number_queries: int = None, recursion_level: int = None, offset=None, base=None,
+                     images_per_launch: int = None) -> dict:
+    """The matrix-Fisher distribution that matches each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same
+    launches): the grid moment M_b = sum_i softmax(log p_b)_i R_i in fp64 (``rnf_rotation_moments`` on the shared grid) and its
+    maximum-likelihood A_b (``rnf_fisher_fit``), i.e. the Fisher with E[R] = M_b -- the moment projection of the grid posterior.
+    ``mode`` = U V^T of A's proper SVD is its most likely rotation, ``s`` its three concentrations; ``mean_rotation`` and ``entropy`` come
+    from the exact kernel on the fitted A.  ``status`` [B] int32 as ``fit_matrix_fisher`` (1: capped at the default max_concentration 1e4,
+    e.g. all mass on one grid point).  Flows with batch-coupled layers are refused as in ``grid_beam_estimate_rotations``.
+    -> dict(A [B,3,3], mean_rotation [B,3,3], mode [B,3,3], s [B,3] fp64, entropy [B], status [B], moments [B,3,3] fp64, offset [3,3])"""
+    who = "grid_pose_fisher"
+    _refuse_batch_coupled(flow, who, ", so an image's density would depend on the launch")
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        moments = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            moments.append(fisher.rotation_moments(grid, lp))
+        moments = moments[0] if len(moments) == 1 else torch.cat(moments)
+        fit = fisher.fit_matrix_fisher(moments)
+        U, V, _, _ = fisher.device_proper_svd(fit["A"])
+        mf = fisher.MatrixFisherN(fit["A"], "exact")
+        return dict(A=fit["A"], mean_rotation=mf.mean_rotation(), mode=U @ V.transpose(-1, -2), s=fit["s"], entropy=mf.entropy(),
+                    status=fit["status"], moments=moments, offset=offset)
+
+
+def grid_pose_mixture(flow: Flow, feature: torch.Tensor = None, components: int = 4, separation_deg: float = 15.0, iterations: int = 64,
+                      tol: float = 1e-9, number_queries: int = None, recursion_level: int = None, offset=None, base=None,
+                      images_per_launch: int = None, max_concentration: float = 1e4) -> dict:
+    """A ``components``-component mixture of matrix-Fishers for each image's density on the grid of ``grid_estimate_rotations`` (same
+    inputs, same launches as ``grid_pose_fisher``): EM on the shared grid with the image's log-densities as log-weights
+    (``rnf_fisher_mixture_fit``), started from the image's ``grid_modes`` (``fisher.mixture_init_from_modes``: component k on mode k,
+    weight = the mode's share of the mass; a mode that does not exist is an empty component, status 8, weight 0).  ``kl`` = log Q -
+    weight_entropy - log_likelihood is the KL divergence from the grid-normalised posterior (mass softmax(log p)_i on cell i, i.e. density
+    Q softmax(log p)_i w.r.t. Haar) to the mixture: >= 0 up to rounding, the smaller the better the summary; with ``components=1`` it is
+    the same quantity for the single Fisher of ``grid_pose_fisher``, whose A, s and status that call reproduces bit for bit.
+    ``mode`` = U V^T of each A's proper SVD.  Flows with batch-coupled layers are refused as in ``grid_pose_fisher``.
+    -> dict(A [B,K,3,3], weight [B,K] fp64, mode [B,K,3,3], s [B,K,3] fp64, log_likelihood [B] fp64, kl [B] fp64, status [B,K],
+    iterations [B], loglik [B,iterations+1] fp64 (the trace: entry t before iteration t, NaN after the last used one), offset [3,3])"""
+    who = "grid_pose_mixture"
+    if not 1 <= int(components) <= 8:
+        raise ValueError(f"{who}: components={components} outside 1..8")
+    if not 0.0 < float(separation_deg) <= 180.0:
+        raise ValueError(f"{who}: separation_deg={separation_deg} outside (0, 180]")
+    _refuse_batch_coupled(flow, who, ", so an image's density would depend on the launch")
+    K, sep = int(components), float(np.deg2rad(np.float64(separation_deg)))
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        B, Q = gf.B, grid.shape[0]
+        fits = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            index, _, mass, _, _ = grid_modes(lp, grid, K, sep)
+            A0, lp0 = fisher.mixture_init_from_modes(grid, index, mass, sep)
+            fits.append(fisher.fit_matrix_fisher_mixture(grid, lp, A0, lp0, iterations, tol, max_concentration))
+        fit = fits[0] if len(fits) == 1 else {k: torch.cat([f[k] for f in fits]) for k in fits[0]}
+        U, V, _, _ = fisher.device_proper_svd(fit["A"])
+        L = fit["loglik"].gather(1, fit["iterations"].long()[:, None])[:, 0]
+        return dict(A=fit["A"], weight=fit["log_pi"].exp(), mode=(U @ V.transpose(-1, -2)).reshape(B, K, 3, 3), s=fit["s"], log_likelihood=L,
+                    kl=float(np.log(Q)) - fit["weight_entropy"] - L, status=fit["status"], iterations=fit["iterations"], loglik=fit["loglik"],
+                    offset=offset)
+
+
+def grid_children(parents: torch.Tensor, level: int, offset=None, rotations: bool = True):
+    """``rnf_so3_grid_children``: the 12 level-(``level`` + 1) children of each level-``level`` grid row in ``parents`` [..., m] (int64, on
+    the device; a row outside the level, e.g. -1, has children -1) -> (rows [..., m * 12] int64, rotations [..., m * 12, 3, 3] or None).
+    The rotations are bit-identical to the rows of ``utils.sd.generate_healpix_grid(level + 1, offset=offset)`` (include/rnf_hip.h)."""
+    dev = parents.device
+    par = parents.to(torch.int64).contiguous()
+    shape = par.shape[:-1] + (par.shape[-1] * 12,)
+    rows = torch.empty(shape, dtype=torch.int64, device=dev)
+    rot = torch.empty(shape + (3, 3), dtype=torch.float32, device=dev) if rotations else None
+    off = offset.reshape(9).to(device=dev, dtype=torch.float32).contiguous() if offset is not None else None
+    _lib.call("so3_grid_children", _lib.GridChildren(level=int(level), parents=par.data_ptr(), n=par.numel(),
+                                                     offset=off.data_ptr() if off is not None else None, rows_out=rows.data_ptr(),
+                                                     rot_out=rot.data_ptr() if rot is not None else None), dev)
+    return rows, rot
+
+
+def grid_beam_select(logp: torch.Tensor, beam: int, rows: torch.Tensor = None):
+    """``rnf_grid_beam_select``: per image (row of ``logp`` [g,M], float32 on the device), the ``beam`` best distinct candidate rows --
+    log p descending (a NaN first), then row ascending; ``rows`` [g,M] int64 the candidates' grid rows (None: candidate i is row i; a row
+    < 0 is no candidate).  Past the distinct rows: row -1, log p -inf.  -> (rows [g,beam] int64, log_prob [g,beam])"""
+    g, M = logp.shape
+    dev = logp.device
+    lp = logp.to(torch.float32).contiguous()
+    rw = rows.reshape(g, M).to(torch.int64).contiguous() if rows is not None else None
+    rows_out = torch.empty(g, int(beam), dtype=torch.int64, device=dev)
+    logp_out = torch.empty(g, int(beam), dtype=torch.float32, device=dev)
+    args = _lib.GridBeamSelect(logp=lp.data_ptr(), rows=rw.data_ptr() if rw is not None else None, M=M, g=g, beam=int(beam),
+                               rows_out=rows_out.data_ptr(), logp_out=logp_out.data_ptr())
+    _lib.call("grid_beam_select", args, dev)
+    return rows_out, logp_out
+
+
+GRID_BEAM_MAX = 1024
+GRID_BEAM_MAX_START = 4
+
+
+def grid_beam_estimate_rotations(flow: Flow, feature: torch.Tensor = None, recursion_level: int = 5, start_level: int = 2, beam: int = 16,
+                                 offset=None, base=None, images_per_launch: int = None):
+    """Coarse-to-fine beam search for ``grid_estimate_rotations``'s estimate at level ``recursion_level``: evaluate the whole level
+    ``start_level`` grid, keep each image's ``beam`` best distinct rows (``rnf_grid_beam_select``), then at every level up to
+    ``recursion_level`` evaluate the 12 children of each kept row (``rnf_so3_grid_children``: the four NESTED sub-pixels times the tilts
+    2t - 1, 2t, 2t + 1) and select again; the last level keeps the best row.  Every evaluated row is a row of the full level-L grid (same
+    rotation bits, same log p), so ``index`` is in the full grid's row order and, when the beams cover every row, the result is
+    ``grid_estimate_rotations(recursion_level=L)``'s.  About beam * 12 * (L - start_level) rows per image instead of 72 * 8^L.
+    No host synchronisation between levels.
+
+    Inputs as ``grid_estimate_rotations`` (feature [B,F] or None, ``offset``, ``base`` with 1 or B rows); ``images_per_launch`` groups the
+    start level as there and the refinement launches up to about 2^21 rows (beam * 12 per image).  Limits (ValueError before any launch):
+    0 <= start_level <= min(recursion_level, 4), recursion_level <= 8, 1 <= beam <= 1024; flows with batch-coupled layers are refused
+    (their matrices come from a launch's first rows, so a candidate set would change the density).  start_level == recursion_level is
+    ``grid_estimate_rotations`` itself.  Returns (est [B,3,3], max_log_prob [B], index [B] into the level-L grid, offset [3,3])."""
+    who = "grid_beam_estimate_rotations"
+    L, S, beam = int(recursion_level), int(start_level), int(beam)
+    if not 0 <= L <= sd.MAX_LEVEL:
+        raise ValueError(f"{who}: recursion_level={recursion_level} outside 0..{sd.MAX_LEVEL}")
+    if not 0 <= S <= min(L, GRID_BEAM_MAX_START):
+        raise ValueError(f"{who}: start_level={start_level} outside 0..min(recursion_level, {GRID_BEAM_MAX_START})")
+    if not 1 <= beam <= GRID_BEAM_MAX:
+        raise ValueError(f"{who}: beam={beam} outside 1..{GRID_BEAM_MAX}")
+    if images_per_launch is not None and int(images_per_launch) < 1:
+        raise ValueError(f"{who}: images_per_launch={images_per_launch}")
+    _refuse_batch_coupled(flow, who)
+    if S == L:
+        return grid_estimate_rotations(flow, feature, recursion_level=L, offset=offset, base=base, images_per_launch=images_per_launch)
+    gf, _, offset = _grid_inputs(flow, feature, None, L, offset, base, who)
+    B, dev = gf.B, gf.dev
+    with torch.no_grad():
+        # the start level: the whole grid, in grid_estimate_rotations' launches; an image evaluated in chunks is gathered first
+        grid = sd.generate_healpix_grid(S, device=dev, offset=offset)
+        kept = torch.empty(B, beam, dtype=torch.int64, device=dev)
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            kept[b0:b1] = grid_beam_select(lp, beam)[0]
+        del grid
+        # the refinement levels: each image's beam * 12 children in one shared-row launch group of about 2^21 rows
+        M = beam * 12
+        g = int(images_per_launch) if images_per_launch is not None else max(1, gf.budget // M)
+        g = max(1, min(g, B, 65535))
+        est = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+        best = torch.empty(B, dtype=torch.float32, device=dev)
+        index = torch.empty(B, dtype=torch.int64, device=dev)
+        for level in range(S, L):
+            last = level + 1 == L
+            nxt = torch.empty(B, beam, dtype=torch.int64, device=dev) if not last else None
+            for b0 in range(0, B, g):
+                b1 = min(B, b0 + g)
+                rows, rot = grid_children(kept[b0:b1], level, offset)
+                lp = gf.log_prob(rot.reshape(-1, 3, 3), b0, b1, M).reshape(b1 - b0, M)
+                sel = grid_beam_select(lp, 1 if last else beam, rows)[0]
+                if not last:
+                    nxt[b0:b1] = sel
+                    continue
+                pos = torch.argmax((rows == sel).to(torch.int32), dim=-1)          # the first candidate of the chosen row
+                ar = torch.arange(b1 - b0, device=dev)
+                est[b0:b1], best[b0:b1], index[b0:b1] = rot[ar, pos], lp[ar, pos], sel[:, 0]     # log p with its own bits
+            kept = nxt
+    return est, best, index, offset

@@ -63,42 +63,40 @@ def device_fisher_exact(A, want="c"):
     return out
 
 
+def _rotation_groups(rotations, log_weights, who: str):
+    """The group arguments of ``rotation_moments`` (its docstring) -> (R fp32 [n,3,3] | [G,n,3,3], lw fp32 [G,n] or None, n, G, shared)."""
+    if not rotations.is_cuda:
+        raise RuntimeError(f"rotationnormflow_amd runs on the GPU only (no CPU fallback): {who} needs the rotations on the GPU")
+    if rotations.dim() not in (3, 4) or tuple(rotations.shape[-2:]) != (3, 3):
+        raise ValueError(f"{who}: rotations {tuple(rotations.shape)}, expected [n,3,3] or [G,n,3,3]")
+    R = rotations.detach().to(torch.float32).contiguous()
+    n = R.shape[-3]
+    lw = None
+    if log_weights is not None:
+        lw = log_weights.detach().to(device=R.device, dtype=torch.float32)
+        lw = lw.reshape(1, -1) if lw.dim() == 1 else lw
+        if lw.dim() != 2 or lw.shape[1] != n or (R.dim() == 4 and lw.shape[0] != R.shape[0]):
+            raise ValueError(f"{who}: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
+        lw = lw.contiguous()
+    shared = R.dim() == 3 and lw is not None
+    G = lw.shape[0] if shared else (R.shape[0] if R.dim() == 4 else 1)
+    return R, lw, n, G, shared
+
+
 def rotation_moments(rotations, log_weights=None):
     """Weighted moments M_g = sum_i w_gi R_gi of groups of rotations, fp64 [G,3,3] on the device (rnf_rotation_moments): the sufficient
     statistic of ``fit_matrix_fisher``.  ``rotations`` [n,3,3] (one group), [G,n,3,3], or [n,3,3] with ``log_weights`` [G,n] (one set
     of rotations shared by G weightings -- a grid and one row of log-densities per image).  w_g = softmax(log_weights[g]) (fp64; a -inf
     row contributes 0), or 1/n without log-weights.  Fixed summation order: a group's moment is bit-identical however it is batched.
     A group whose weights are all -inf, or that holds a NaN, yields NaN.  Stream-ordered, no host synchronisation."""
-    if not rotations.is_cuda:
-        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): rotation_moments needs the rotations on the GPU")
-    if rotations.dim() not in (3, 4) or tuple(rotations.shape[-2:]) != (3, 3):
-        raise ValueError(f"rotation_moments: rotations {tuple(rotations.shape)}, expected [n,3,3] or [G,n,3,3]")
-    dev = rotations.device
-    R = rotations.detach().to(torch.float32).contiguous()
-    n = R.shape[-3]
-    lw = None
-    if log_weights is not None:
-        lw = log_weights.detach().to(device=dev, dtype=torch.float32)
-        lw = lw.reshape(1, -1) if lw.dim() == 1 else lw
-        if lw.dim() != 2 or lw.shape[1] != n or (R.dim() == 4 and lw.shape[0] != R.shape[0]):
-            raise ValueError(f"rotation_moments: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
-        lw = lw.contiguous()
-    shared = R.dim() == 3 and lw is not None
-    G = lw.shape[0] if shared else (R.shape[0] if R.dim() == 4 else 1)
+    R, lw, n, G, shared = _rotation_groups(rotations, log_weights, "rotation_moments")
+    dev = R.device
     if n < 1 or G < 1:
         raise ValueError(f"rotation_moments: {G} groups of {n} rotations")
     out = torch.empty(G, 3, 3, dtype=torch.float64, device=dev)
     args = _lib.RotationMoments(rotations=R.data_ptr(), log_weights=lw.data_ptr() if lw is not None else None, n=n, G=G,
                                 shared_rotations=int(shared), moments_out=out.data_ptr())
-    L = _lib.lib()
-    need = L.rnf_rotation_moments_workspace_bytes(_lib.C.byref(args))
-    if need == 0:
-        _lib.check(1)
-    ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), need
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.rnf_rotation_moments(_lib.C.byref(args)))
+    _lib.call("rotation_moments", args, dev)
     return out
 
 
@@ -120,11 +118,10 @@ def fit_matrix_fisher(moments, max_concentration=1e4, max_iterations=0):
     H = torch.empty(B, 6, dtype=torch.float64, device=dev)
     it = torch.empty(B, dtype=torch.int32, device=dev)
     st = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        args = _lib.FisherFit(moments=M.data_ptr(), B=B, max_concentration=float(max_concentration), max_iterations=int(max_iterations),
-                              A_out=A.data_ptr(), s_out=s.data_ptr(), hessian_out=H.data_ptr(), iterations_out=it.data_ptr(),
-                              status_out=st.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(_lib.lib().rnf_fisher_fit(_lib.C.byref(args)))
+    args = _lib.FisherFit(moments=M.data_ptr(), B=B, max_concentration=float(max_concentration), max_iterations=int(max_iterations),
+                          A_out=A.data_ptr(), s_out=s.data_ptr(), hessian_out=H.data_ptr(), iterations_out=it.data_ptr(),
+                          status_out=st.data_ptr())
+    _lib.call("fisher_fit", args, dev)
     return dict(A=A, s=s, hessian=H, iterations=it, status=st)
 
 
@@ -144,22 +141,8 @@ def fit_matrix_fisher_mixture(rotations, log_weights, A_init, log_pi_init=None, 
     (A, log_pi): T iterations equal T chained calls of one.  A group's outputs are bit-identical however it is batched; K = 1 gives the
     A, s and status of ``rotation_moments`` + ``fit_matrix_fisher``.  A group with all weights -inf, a NaN, or no live component is NaN
     with status 4.  Stream-ordered, no host synchronisation, capturable."""
-    if not rotations.is_cuda:
-        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback): fit_matrix_fisher_mixture needs the rotations on the GPU")
-    if rotations.dim() not in (3, 4) or tuple(rotations.shape[-2:]) != (3, 3):
-        raise ValueError(f"fit_matrix_fisher_mixture: rotations {tuple(rotations.shape)}, expected [n,3,3] or [G,n,3,3]")
-    dev = rotations.device
-    R = rotations.detach().to(torch.float32).contiguous()
-    n = R.shape[-3]
-    lw = None
-    if log_weights is not None:
-        lw = log_weights.detach().to(device=dev, dtype=torch.float32)
-        lw = lw.reshape(1, -1) if lw.dim() == 1 else lw
-        if lw.dim() != 2 or lw.shape[1] != n or (R.dim() == 4 and lw.shape[0] != R.shape[0]):
-            raise ValueError(f"fit_matrix_fisher_mixture: log_weights {tuple(log_weights.shape)} for rotations {tuple(rotations.shape)}")
-        lw = lw.contiguous()
-    shared = R.dim() == 3 and lw is not None
-    G = lw.shape[0] if shared else (R.shape[0] if R.dim() == 4 else 1)
+    R, lw, n, G, shared = _rotation_groups(rotations, log_weights, "fit_matrix_fisher_mixture")
+    dev = R.device
     A0 = A_init.detach().to(device=dev, dtype=torch.float32)
     if A0.dim() not in (3, 4) or tuple(A0.shape[-2:]) != (3, 3) or A0.numel() % (9 * G) or (A0.dim() == 4 and A0.shape[0] != G):
         raise ValueError(f"fit_matrix_fisher_mixture: A_init {tuple(A_init.shape)} for {G} groups, expected [G,K,3,3]")
@@ -189,20 +172,12 @@ def fit_matrix_fisher_mixture(rotations, log_weights, A_init, log_pi_init=None, 
                                  weight_entropy_out=out["weight_entropy"].data_ptr(),
                                  log_resp_out=out["log_resp"].data_ptr() if log_resp else None, status_out=out["status"].data_ptr(),
                                  iterations_out=out["iterations"].data_ptr())
-    L = _lib.lib()
-    need = L.rnf_fisher_mixture_fit_workspace_bytes(_lib.C.byref(args))
-    if need == 0:
-        _lib.check(1)
-    ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    args.workspace, args.workspace_bytes = ws.data_ptr(), need
-    with torch.cuda.device(dev):
-        args.stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.rnf_fisher_mixture_fit(_lib.C.byref(args)))
+    _lib.call("fisher_mixture_fit", args, dev)
     return out
 
 
 def mixture_init_from_modes(grid, index, mass, separation_rad):
-    """The start of a mixture fit from ``harness.grid_modes``: component k sits on mode k with A_k = kappa0 R_k, kappa0 = 2 /
+    """The start of a mixture fit from ``grid_pose.grid_modes``: component k sits on mode k with A_k = kappa0 R_k, kappa0 = 2 /
     separation_rad^2 (MF(kappa R) has an angular standard deviation of 1 / sqrt(2 kappa) per axis: half the separation), log_pi_k the log
     of the mode's share of the modes' mass; a missing mode (index -1) or one without mass is an empty component (log_pi = -inf, A = 0).
     grid [Q,3,3], index [g,K] int64, mass [g,K] -> (A_init [g,K,3,3] fp32, log_pi_init [g,K] fp64)."""
@@ -267,7 +242,7 @@ class MatrixFisherMixture(torch.nn.Module):
     def fit(cls, rotations, log_weights=None, components=4, init=None, separation_deg=15.0, iterations=64, tol=1e-9, max_concentration=1e4):
         """EM fit of one mixture to ``rotations`` [n,3,3] with weights softmax(``log_weights`` [n]) (None: 1/n), by
         ``fit_matrix_fisher_mixture``.  ``init``: A_init [K,3,3], or (A_init, log_pi_init [K]); None with log-weights given starts from
-        ``harness.grid_modes`` of the log-weights on the rotations (``components`` modes at least ``separation_deg`` apart, see
+        ``grid_pose.grid_modes`` of the log-weights on the rotations (``components`` modes at least ``separation_deg`` apart, see
         ``mixture_init_from_modes``); None without log-weights is refused.  The result carries ``fit_status`` [K], ``fit_s`` [K,3],
         ``fit_iterations``, ``log_likelihood`` (fp64 scalars on the device) and ``fit`` (the whole output dict)."""
         if rotations.dim() != 3:
@@ -282,9 +257,9 @@ class MatrixFisherMixture(torch.nn.Module):
                 raise ValueError("MatrixFisherMixture.fit: without log_weights there are no modes to start from; pass init")
             if not 1 <= int(components) <= 8:
                 raise ValueError(f"MatrixFisherMixture.fit: components={components} outside 1..8")
-            from .. import harness
+            from .. import grid_pose
             sep = math.radians(float(separation_deg))
-            index, _, mass, _, _ = harness.grid_modes(lw.to(device=rotations.device, dtype=torch.float32), rotations, int(components), sep)
+            index, _, mass, _, _ = grid_pose.grid_modes(lw.to(device=rotations.device, dtype=torch.float32), rotations, int(components), sep)
             A0, lp0 = mixture_init_from_modes(rotations, index, mass, sep)
         else:
             A0, lp0 = init if isinstance(init, (tuple, list)) else (init, None)

@@ -8,7 +8,7 @@ import torch
 from scipy.special import ive
 from scipy.stats import chi2
 
-from rotationnormflow_amd import harness, synth
+from rotationnormflow_amd import grid_pose, harness, synth
 from rotationnormflow_amd.utils import fisher, sd
 from rotationnormflow_amd.utils.fisher import MatrixFisherN
 from tests import fisher_exact as fe
@@ -288,7 +288,7 @@ def test_grid_pose_fisher():
     # the moment from the grid search's own log-densities, in long double
     grid = sd.generate_healpix_grid(2, device=feat.device, offset=O)
     with torch.no_grad():
-        lp = torch.cat([x[3] for x in harness._grid_launches(fl, feat, grid, B, None, None, None, "test")])
+        lp = torch.cat([x[3] for x in grid_pose._grid_launches(fl, feat, grid, B, None, None, None, "test")])
     est, best, index, _ = harness.grid_estimate_rotations(fl, feat, recursion_level=2, offset=O)
     assert torch.equal(lp.max(-1).values, best)
     want = _moments_ref(grid.cpu().numpy(), lp.cpu().numpy())

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from rotationnormflow_amd import harness, runtime, synth
+from rotationnormflow_amd import grid_pose, harness, runtime, synth
 from rotationnormflow_amd.utils import sd
 from rotationnormflow_amd.utils.fisher import MatrixFisherN
 from tests.test_gpu_grid_pose import _fisher_rows, _flow, _offset
@@ -189,13 +189,13 @@ def test_side_layer_flow_gathers_the_chunks_of_one_image():
     feat = torch.from_numpy(synth.features(B, 16, seed=6)).cuda()
     O = _offset(4).cuda()
     Q = sd.grid_size(4)
-    assert Q > harness.GRID_SIDE_LAUNCH_ROWS
+    assert Q > grid_pose.GRID_SIDE_LAUNCH_ROWS
     out = harness.grid_pose_credible(fl, feat, recursion_level=4, offset=O)
     grid = sd.generate_healpix_grid(4, device="cuda", offset=O)
     lp = torch.empty(B, Q, device="cuda")
     chunks = 0
     with torch.no_grad():
-        for b0, b1, lo, part in harness._grid_launches(fl, feat, grid, B, None, None, None, "test"):
+        for b0, b1, lo, part in grid_pose._grid_launches(fl, feat, grid, B, None, None, None, "test"):
             lp[b0:b1, lo:lo + part.shape[1]] = part
             chunks += 1
     assert chunks == 2 * B

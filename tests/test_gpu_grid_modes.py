@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from rotationnormflow_amd import harness, runtime, synth
+from rotationnormflow_amd import grid_pose, harness, runtime, synth
 from rotationnormflow_amd.utils import sd
 from rotationnormflow_amd.utils.fisher import MatrixFisherN
 from tests.test_gpu_grid_pose import _fisher_rows, _flow, _offset
@@ -127,7 +127,7 @@ def test_level6_gathers_the_chunks_of_one_image():
     O = _offset(7)
     est, best, index, _ = harness.grid_estimate_rotations(fl, feat, recursion_level=6, offset=O)
     m = harness.grid_pose_modes(fl, feat, top_k=2, recursion_level=6, offset=O)
-    assert sd.grid_size(6) > harness.GRID_MAX_LAUNCH_ROWS
+    assert sd.grid_size(6) > grid_pose.GRID_MAX_LAUNCH_ROWS
     assert torch.equal(m["index"][:, 0], index) and torch.equal(m["log_prob"][:, 0], best) and torch.equal(m["est"][:, 0], est)
     assert int(m["index"][0, 1]) >= 0 and bool(torch.isfinite(m["log_norm"]).all()) and float(m["mass"].sum()) <= 1 + 1e-6
 

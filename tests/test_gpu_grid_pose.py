@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from oracle import flow_oracle as orc
-from rotationnormflow_amd import harness, make_config, runtime, synth
+from rotationnormflow_amd import grid_pose, harness, make_config, runtime, synth
 from rotationnormflow_amd.utils import sd
 from rotationnormflow_amd.utils.fisher import MatrixFisherN
 from tests.gpu_helpers import product_flow
@@ -123,8 +123,9 @@ def test_grouping_and_chunking_do_not_change_the_result(monkeypatch):
     runs = [harness.grid_estimate_rotations(fl, feat, recursion_level=2, offset=_offset(2), base=base, images_per_launch=g)
             for g in (1, 3, B, None)]
     with monkeypatch.context() as m:
-        m.setattr(harness, "GRID_MAX_LAUNCH_ROWS", 1000)              # one image's 4608 rotations in five ragged chunks
+        m.setattr(grid_pose, "GRID_MAX_LAUNCH_ROWS", 1000)            # one image's 4608 rotations in five ragged chunks
         runs.append(harness.grid_estimate_rotations(fl, feat, recursion_level=2, offset=_offset(2), base=base, images_per_launch=1))
+        assert _chunks(fl, feat, 2, B) == 5 * B                       # the patch reaches the launch loop
     est0, best0, index0, _ = runs[0]
     for est, best, index, _ in runs[1:]:
         assert torch.equal(index, index0) and torch.equal(best, best0) and torch.equal(est, est0)
@@ -132,6 +133,50 @@ def test_grouping_and_chunking_do_not_change_the_result(monkeypatch):
     e1, b1, i1, O = harness.grid_estimate_rotations(fl, feat, recursion_level=2, offset=_offset(2), base=one)
     idx, val = _materialised(fl, sd.generate_healpix_grid(2, device="cuda", offset=O), feat, one, B)
     assert torch.equal(i1, idx) and torch.equal(b1, val)
+
+
+def _chunks(fl, feat, level, B, images_per_launch=1):
+    """How many launches ``_grid_launches`` makes for B images on the level's grid."""
+    grid = sd.generate_healpix_grid(level, device="cuda", offset=_offset(2).cuda())
+    with torch.no_grad():
+        return sum(1 for _ in grid_pose._grid_launches(fl, feat, grid, B, None, None, images_per_launch, "test"))
+
+
+def _same_bits(a, b):
+    """torch.equal, with NaNs equal where both have one."""
+    if not a.is_floating_point():
+        return torch.equal(a, b)
+    return torch.equal(a.isnan(), b.isnan()) and torch.equal(torch.where(a.isnan(), 0, a), torch.where(b.isnan(), 0, b))
+
+
+def test_every_whole_image_analysis_gathers_ragged_chunks(monkeypatch):
+    """Each analysis that reduces whole images, on one image per launch in five ragged chunks (4608 rows, 1000 per launch) against the
+    three images in one launch: the same bits in every returned tensor."""
+    _, _, fl = _flow(seed=6)
+    B = 3
+    feat = torch.from_numpy(synth.features(B, 32, seed=3)).cuda()
+    gt = torch.from_numpy(synth.uniform_rotations(B, seed=12)).cuda()
+    O = _offset(2)
+
+    def analyses(g):
+        return dict(modes=harness.grid_pose_modes(fl, feat, top_k=4, recursion_level=2, offset=O, images_per_launch=g),
+                    credible=harness.grid_pose_credible(fl, feat, recursion_level=2, offset=O, gt_rotation=gt, images_per_launch=g),
+                    fisher=harness.grid_pose_fisher(fl, feat, recursion_level=2, offset=O, images_per_launch=g),
+                    mixture=harness.grid_pose_mixture(fl, feat, components=2, iterations=8, recursion_level=2, offset=O, images_per_launch=g),
+                    beam=dict(zip(("est", "max_log_prob", "index", "offset"),
+                                  harness.grid_beam_estimate_rotations(fl, feat, recursion_level=3, start_level=2, beam=16, offset=O,
+                                                                       images_per_launch=g))))
+
+    want = analyses(None)
+    assert _chunks(fl, feat, 2, B, None) == 1
+    with monkeypatch.context() as m:
+        m.setattr(grid_pose, "GRID_MAX_LAUNCH_ROWS", 1000)
+        got = analyses(1)
+        assert _chunks(fl, feat, 2, B) == 5 * B
+    for name, out in want.items():
+        assert set(got[name]) == set(out)
+        for key, value in out.items():
+            assert _same_bits(got[name][key], value), (name, key)
 
 
 def test_unconditional_flow_uses_one_image_per_base_row():
