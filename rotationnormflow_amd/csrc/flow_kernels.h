@@ -1646,10 +1646,7 @@ __device__ __forceinline__ void cond16_finish(const f32x16 &o, int h, Rot &R, fl
             M[4 * (2 * g + 1) + c] = h ? mine : other;
         }
     M[0] += 1.f; M[5] += 1.f; M[10] += 1.f; M[15] += 1.f;
-    float Mi[16];
-    float det = inv4(M, Mi);
-    if (INVERSE) affine16_apply(Mi, -logf(fabsf(det)), R, ldj);
-    else affine16_apply(M, logf(fabsf(det)), R, ldj);
+    cond16_apply(M, INVERSE, R, ldj);
 }
 
 // Conditional 3x3 layers (extended instantiation only): M = I + reshape(outputs 0..8, 3, 3); output i sits where output i of
@@ -2122,11 +2119,12 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                     for (int i = 0; i < 9; ++i) M9[i] = m[i];
                     cond_gs9_apply(M9, DIR != 0, R, ldj);
                 } else {
-                    float M[16], Mi[16];
+                    float M[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) M[i] = m[i];
                     if (kind == RNF_KIND_SIDE16_ROT) {            // ConditionRot (flow/rottrans.py:37-66): orthogonal, log-det 0, inverse = transpose
                         if (DIR) {
+                            float Mi[16];
 #pragma unroll
                             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -2136,9 +2134,7 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                             affine16_apply(M, 0.f, R, ldj, true);
                         }
                     } else {                                      // Condition16TransLU (flow/squeezetrans.py:134-144)
-                        const float det = inv4(M, Mi);
-                        if (DIR) affine16_apply(Mi, -logf(fabsf(det)), R, ldj);
-                        else affine16_apply(M, logf(fabsf(det)), R, ldj);
+                        cond16_apply(M, DIR != 0, R, ldj);
                     }
                 }
                 continue;

@@ -359,8 +359,9 @@ struct AffineSaved {
     float ab;                 // the chosen sqrt(max(0, 1 +- m00 +- m11 +- m22))
 };
 
-RNF_HD void affine16_forward_saved(const float (&M)[16], float logabsdet, const Rot &Rin, Rot &Rout, float &ldj, AffineSaved &sv) {
-    const float m00 = Rin.c0.x, m01 = Rin.c1.x, m02 = Rin.c2.x, m10 = Rin.c0.y, m11 = Rin.c1.y, m12 = Rin.c2.y, m20 = Rin.c0.z, m21 = Rin.c1.z, m22 = Rin.c2.z;
+// q = rot_to_quat(Rin) with the candidate it chose and that candidate's square root, which the reverse step needs
+RNF_HD void affine16_save_quat(const Rot &Rin, AffineSaved &sv) {
+    const float m00 = Rin.c0.x, m11 = Rin.c1.y, m22 = Rin.c2.z;
     const float a[4] = {sqrtf(fmaxf(1.0f + m00 + m11 + m22, 0.0f)), sqrtf(fmaxf(1.0f + m00 - m11 - m22, 0.0f)),
                         sqrtf(fmaxf(1.0f - m00 + m11 - m22, 0.0f)), sqrtf(fmaxf(1.0f - m00 - m11 + m22, 0.0f))};
     int best = 0;
@@ -368,16 +369,18 @@ RNF_HD void affine16_forward_saved(const float (&M)[16], float logabsdet, const 
     sv.best = best;
     sv.ab = a[best];
     rot_to_quat(Rin, sv.q);
+}
+
+RNF_HD void affine16_forward_saved(const float (&M)[16], float logabsdet, const Rot &Rin, Rot &Rout, float &ldj, AffineSaved &sv) {
+    affine16_save_quat(Rin, sv);
     for (int i = 0; i < 4; ++i) sv.t[i] = M[4 * i] * sv.q[0] + M[4 * i + 1] * sv.q[1] + M[4 * i + 2] * sv.q[2] + M[4 * i + 3] * sv.q[3];
     sv.l2 = sv.t[0] * sv.t[0] + sv.t[1] * sv.t[1] + sv.t[2] * sv.t[2] + sv.t[3] * sv.t[3];
     quat_to_rot(sv.t, sv.l2, Rout);
     ldj = logabsdet - 2.0f * logf(sv.l2);
 }
 
-// gM (16, accumulated into by the caller over the batch) gets g_t (x) q; the log|det M| term (sum_b g_ldj) M^-T is added by the
-// caller once per batch.  Returns dL/dRin.
-RNF_HD void affine16_backward(const float (&M)[16], const AffineSaved &sv, const Rot &gRout, float g_ldj, bool orthogonal, float (&gM)[16],
-                              Rot &gRin) {
+// dL/dt of R' = rot(t), ldj = ... - 2 log|t|^2
+RNF_HD void affine16_backward_t(const AffineSaved &sv, const Rot &gRout, float g_ldj, bool orthogonal, float (&gt)[4]) {
     const float w = sv.t[0], x = sv.t[1], y = sv.t[2], z = sv.t[3];
     const float s2 = 2.0f / sv.l2;
     // R' entries E_ij = delta_ij - s2 * P_ij(t) (diag) or s2 * P_ij (off-diag); collect g wrt s2 and wrt the quadratic forms
@@ -387,7 +390,6 @@ RNF_HD void affine16_backward(const float (&M)[16], const AffineSaved &sv, const
                 Q20 = x * z - y * w, Q21 = y * z + x * w, Q22 = -(x * x + y * y);
     const float g_s2 = g00 * Q00 + g01 * Q01 + g02 * Q02 + g10 * Q10 + g11 * Q11 + g12 * Q12 + g20 * Q20 + g21 * Q21 + g22 * Q22;
     // dQ/dt
-    float gt[4];
     gt[0] = s2 * (-g01 * z + g02 * y + g10 * z - g12 * x - g20 * y + g21 * x);
     gt[1] = s2 * (g01 * y + g02 * z + g10 * y - 2.0f * g11 * x - g12 * w + g20 * z + g21 * w - 2.0f * g22 * x);
     gt[2] = s2 * (-2.0f * g00 * y + g01 * x + g02 * w + g10 * x + g12 * z - g20 * w + g21 * z - 2.0f * g22 * y);
@@ -395,13 +397,9 @@ RNF_HD void affine16_backward(const float (&M)[16], const AffineSaved &sv, const
     // s2 = 2 / l2, ldj = ... - 2 log l2,  l2 = |t|^2
     const float g_l2 = -g_s2 * s2 / sv.l2 - (orthogonal ? 0.f : 2.0f * g_ldj / sv.l2);
     for (int i = 0; i < 4; ++i) gt[i] += 2.0f * sv.t[i] * g_l2;
-    // t = M q
-    float gq[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            gM[4 * i + j] += gt[i] * sv.q[j];
-            gq[j] += M[4 * i + j] * gt[i];
-        }
+}
+// dL/dRin from dL/dq, q = rot_to_quat(Rin)
+RNF_HD void affine16_backward_q(const AffineSaved &sv, const float (&gq)[4], Rot &gRin) {
     // q = cand / (2 max(ab, 0.1)), cand depends on `best` (so3_math.h rot_to_quat); ab = sqrt(1 +- m00 +- m11 +- m22)
     const float den = 2.0f * fmaxf(sv.ab, 0.1f);
     const float inv = 1.0f / den;
@@ -427,6 +425,53 @@ RNF_HD void affine16_backward(const float (&M)[16], const AffineSaved &sv, const
     gRin.c0 = v3f{r00, r10, r20};
     gRin.c1 = v3f{r01, r11, r21};
     gRin.c2 = v3f{r02, r12, r22};
+}
+
+// gM (16, accumulated into by the caller over the batch) gets g_t (x) q; the log|det M| term (sum_b g_ldj) M^-T is added by the
+// caller once per batch.  Returns dL/dRin.
+RNF_HD void affine16_backward(const float (&M)[16], const AffineSaved &sv, const Rot &gRout, float g_ldj, bool orthogonal, float (&gM)[16],
+                              Rot &gRin) {
+    float gt[4];
+    affine16_backward_t(sv, gRout, g_ldj, orthogonal, gt);
+    // t = M q
+    float gq[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            gM[4 * i + j] += gt[i] * sv.q[j];
+            gq[j] += M[4 * i + j] * gt[i];
+        }
+    affine16_backward_q(sv, gq, gRin);
+}
+
+// Condition16Trans / Condition16TransLU backward for a per-sample M, both passes, on Ms = 2^-e M as so3_math.h cond16_apply computes the
+// layer: dL/dMs is formed from Ms and Ms^-1 (entries and pivots in range whatever the scale of M) and dL/dM = 2^-e dL/dMs (exact), so
+// dL/dM(2^k M) = 2^-k dL/dM(M) bit for bit and dL/dRin does not change.
+//   forward pass:  t = Ms q,      dL/dMs = g_t q^T + g_ldj Ms^-T,   dL/dq = Ms^T g_t
+//   inverse pass:  t = Ms^-1 q (carried through the Gauss-Jordan elimination as a right-hand side),  dL/dq = Ms^-T g_t,  dL/dMs = -Ms^-T (g_t q^T) Ms^-T - g_ldj Ms^-T = -(dL/dq) t^T - g_ldj Ms^-T
+// (inverse_matrix_grad<4> of the rank-one g_t q^T, written out).  Non-finite where cond16_apply is.
+RNF_HD void cond16_backward(const float (&M)[16], bool inverse, const Rot &Rin, const Rot &gRout, float g_ldj, float (&gM)[16], Rot &gRin) {
+    float ms[16], mi[16], lad;
+    AffineSaved sv;
+    affine16_save_quat(Rin, sv);
+    for (int i = 0; i < 4; ++i) sv.t[i] = sv.q[i];
+    const int e = inv4_scaled(M, ms, mi, sv.t, lad);
+    if (!inverse)
+        for (int i = 0; i < 4; ++i) sv.t[i] = ms[4 * i] * sv.q[0] + ms[4 * i + 1] * sv.q[1] + ms[4 * i + 2] * sv.q[2] + ms[4 * i + 3] * sv.q[3];
+    sv.l2 = sv.t[0] * sv.t[0] + sv.t[1] * sv.t[1] + sv.t[2] * sv.t[2] + sv.t[3] * sv.t[3];
+    const bool ok = sv.l2 >= kAff16Lo && sv.l2 <= kAff16Hi && fabsf(lad) <= 3.402823466e38f;
+    float gt[4], gq[4] = {0.f, 0.f, 0.f, 0.f};
+    affine16_backward_t(sv, gRout, g_ldj, false, gt);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) gq[j] += (inverse ? mi[4 * i + j] : ms[4 * i + j]) * gt[i];      // the applied matrix, entry by entry
+    const float gl = inverse ? -g_ldj : g_ldj;
+    const float bad = ok ? 0.f : __builtin_nanf("");
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const float g = (inverse ? -gq[i] * sv.t[j] : gt[i] * sv.q[j]) + gl * mi[4 * j + i];
+            gM[4 * i + j] = ldexpf(g, -e) + bad;
+        }
+    affine16_backward_q(sv, gq, gRin);
+    gRin.c0 = nan_unless(ok, gRin.c0); gRin.c1 = nan_unless(ok, gRin.c1); gRin.c2 = nan_unless(ok, gRin.c2);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -531,15 +531,28 @@ RNF_HD void quat_to_rot(const float (&q)[4], float l2, Rot &R) {
 // q' = M q(R); R' = R(q'/|q'|); ldj = log|det M| - 4 log|q'| = log|det M| - 2 log|q'|^2
 // `orthogonal`: M is a 4-D rotation (UnconditionRot, flow/rottrans.py:8-23): |q'| = 1 and det M = +-1, the reference
 // returns a log-det of exactly 0, so nothing is added.
+RNF_HD v3f nan_unless(bool ok, v3f v) {                  // scalar selects: a select between two structs goes through memory
+    const float q = __builtin_nanf("");
+    return v3f{ok ? v.x : q, ok ? v.y : q, ok ? v.z : q};
+}
+// R' and ldj are NaN where |q'|^2 is not a normal number in [2^-80, 2^80] (M q = 0, a NaN or infinite entry, an overflow): 2 / |q'|^2 would
+// be 0, infinite or short of bits there, and R' the identity or no rotation at all; and where log|det M| is not finite (a zero or
+// infinite pivot).  So both are finite or both NaN.  Comparisons, not fminf: a NaN must fail them.
+constexpr float kAff16Lo = 8.271806125530277e-25f, kAff16Hi = 1.2089258196146292e24f;      // 2^-80, 2^80
+RNF_HD void affine16_finish_quat(const float (&t)[4], float logabsdet, Rot &R, float &ldj, bool orthogonal) {
+    const float l2 = fmaf(t[3], t[3], fmaf(t[2], t[2], fmaf(t[1], t[1], t[0] * t[0])));
+    const bool ok = l2 >= kAff16Lo && l2 <= kAff16Hi && fabsf(logabsdet) <= 3.402823466e38f;
+    quat_to_rot(t, l2, R);
+    R.c0 = nan_unless(ok, R.c0); R.c1 = nan_unless(ok, R.c1); R.c2 = nan_unless(ok, R.c2);
+    if (!orthogonal) ldj += ok ? logabsdet - 2.0f * logf(l2) : __builtin_nanf("");
+}
 RNF_HD void affine16_apply(const float (&M)[16], float logabsdet, Rot &R, float &ldj, bool orthogonal = false) {
     float q[4], t[4];
     rot_to_quat(R, q);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         t[i] = fmaf(M[4 * i + 3], q[3], fmaf(M[4 * i + 2], q[2], fmaf(M[4 * i + 1], q[1], M[4 * i] * q[0])));
-    float l2 = fmaf(t[3], t[3], fmaf(t[2], t[2], fmaf(t[1], t[1], t[0] * t[0])));
-    quat_to_rot(t, l2, R);
-    if (!orthogonal) ldj += logabsdet - 2.0f * logf(l2);
+    affine16_finish_quat(t, logabsdet, R, ldj, orthogonal);
 }
 
 // calculate_16 for a CONSTANT matrix without the quaternion detour.  For a unit quaternion every product q_i q_j is an affine
@@ -695,11 +708,6 @@ RNF_HD bool orth3_ok(v3f p0, v3f p1, v3f p2) {
     const float t = kPolar3Orth;
     return fabsf(dot3(p0, p0) - 1.0f) <= t && fabsf(dot3(p1, p1) - 1.0f) <= t && fabsf(dot3(p2, p2) - 1.0f) <= t &&
            fabsf(dot3(p0, p1)) <= t && fabsf(dot3(p0, p2)) <= t && fabsf(dot3(p1, p2)) <= t;
-}
-
-RNF_HD v3f nan_unless(bool ok, v3f v) {                  // scalar selects: a select between two structs goes through memory
-    const float q = __builtin_nanf("");
-    return v3f{ok ? v.x : q, ok ? v.y : q, ok ? v.z : q};
 }
 
 // Gram-Schmidt rotation [q0 q1 q0 x q1] of two columns x0, x1.  b1 = x1 - (q0.x1) q0 is left with a component of about 2^-23 |x1| along q0,
@@ -888,32 +896,167 @@ RNF_HD void inv6(float (&a)[36], float (&b)[36]) {
     }
 }
 
-// 4x4 inverse and determinant by cofactors (Condition16Trans.inverse: torch.linalg.inv, flow/squeezetrans.py:51-55;
-// my_det_4_4: squeezetrans.py:17-22).  Returns det(M); Minv = adj(M)/det.
-RNF_HD float inv4(const float (&m)[16], float (&o)[16]) {
-    float s0 = m[0] * m[5] - m[4] * m[1],  s1 = m[0] * m[6] - m[4] * m[2],  s2 = m[0] * m[7] - m[4] * m[3];
-    float s3 = m[1] * m[6] - m[5] * m[2],  s4 = m[1] * m[7] - m[5] * m[3],  s5 = m[2] * m[7] - m[6] * m[3];
-    float c5 = m[10] * m[15] - m[14] * m[11], c4 = m[9] * m[15] - m[13] * m[11], c3 = m[9] * m[14] - m[13] * m[10];
-    float c2 = m[8] * m[15] - m[12] * m[11],  c1 = m[8] * m[14] - m[12] * m[10], c0 = m[8] * m[13] - m[12] * m[9];
-    float det = s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
-    float id = 1.0f / det;
-    o[0]  = ( m[5] * c5 - m[6] * c4 + m[7] * c3) * id;
-    o[1]  = (-m[1] * c5 + m[2] * c4 - m[3] * c3) * id;
-    o[2]  = ( m[13] * s5 - m[14] * s4 + m[15] * s3) * id;
-    o[3]  = (-m[9] * s5 + m[10] * s4 - m[11] * s3) * id;
-    o[4]  = (-m[4] * c5 + m[6] * c2 - m[7] * c1) * id;
-    o[5]  = ( m[0] * c5 - m[2] * c2 + m[3] * c1) * id;
-    o[6]  = (-m[12] * s5 + m[14] * s2 - m[15] * s1) * id;
-    o[7]  = ( m[8] * s5 - m[10] * s2 + m[11] * s1) * id;
-    o[8]  = ( m[4] * c4 - m[5] * c2 + m[7] * c0) * id;
-    o[9]  = (-m[0] * c4 + m[1] * c2 - m[3] * c0) * id;
-    o[10] = ( m[12] * s4 - m[13] * s2 + m[15] * s0) * id;
-    o[11] = (-m[8] * s4 + m[9] * s2 - m[11] * s0) * id;
-    o[12] = (-m[4] * c3 + m[5] * c1 - m[6] * c0) * id;
-    o[13] = ( m[0] * c3 - m[1] * c1 + m[2] * c0) * id;
-    o[14] = (-m[12] * s3 + m[13] * s1 - m[14] * s0) * id;
-    o[15] = ( m[8] * s3 - m[9] * s1 + m[10] * s0) * id;
+// ---- the per-sample 4x4 layer (Condition16Trans, Condition16TransLU) and the 4x4 inverse -------------------------------------------
+// 2^pow2_exponent16(M) brings the largest entry of M into [1, 2) (polar3_exponent for sixteen entries).
+RNF_HD int pow2_exponent16(const float (&m)[16]) {
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(m[i]));
+    return (amax > 0.f && amax <= 3.402823466e38f) ? ilogbf(amax) : 0;
+}
+// Gauss-Jordan with partial pivoting on [a | b | x], everything in registers as in inv6 (compare-and-swap of whole rows, no dynamic
+// indexing): on return b = a^-1 b0 (WITH_B), x = a^-1 x0 (WITH_X), a = I.  Returns det(a), the signed product of the pivots.  The parts a
+// caller does not ask for are not carried.  The reciprocal of a pivot is hw_rcp (v_rcp_f32 on the device, 1 ulp; 1 / x on the host).  A zero pivot gives infinite or NaN
+// results, never a finite one.
+template <bool WITH_B, bool WITH_X>
+RNF_HD float gauss_jordan4(float (&a)[16], float (&b)[16], float (&x)[4]) {
+    float det = 1.0f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 4; ++r) {                 // bubble the largest |a[r][c]| up to row c
+            const bool sw = fabsf(a[4 * r + c]) > fabsf(a[4 * c + c]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float ac = a[4 * c + k], ar = a[4 * r + k];
+                a[4 * c + k] = sw ? ar : ac; a[4 * r + k] = sw ? ac : ar;
+                if constexpr (WITH_B) {
+                    const float bc = b[4 * c + k], br = b[4 * r + k];
+                    b[4 * c + k] = sw ? br : bc; b[4 * r + k] = sw ? bc : br;
+                }
+            }
+            if constexpr (WITH_X) {
+                const float xc = x[c], xr = x[r];
+                x[c] = sw ? xr : xc; x[r] = sw ? xc : xr;
+            }
+            det = sw ? -det : det;
+        }
+        det *= a[4 * c + c];
+        const float ip = hw_rcp(a[4 * c + c]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a[4 * c + k] *= ip;
+            if constexpr (WITH_B) b[4 * c + k] *= ip;
+        }
+        if constexpr (WITH_X) x[c] *= ip;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (r == c) continue;
+            const float f = a[4 * r + c];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a[4 * r + k] = fmaf(-f, a[4 * c + k], a[4 * r + k]);
+                if constexpr (WITH_B) b[4 * r + k] = fmaf(-f, b[4 * c + k], b[4 * r + k]);
+            }
+            if constexpr (WITH_X) x[r] = fmaf(-f, x[c], x[r]);
+        }
+    }
     return det;
+}
+// log|det a| and the solve a x = x0 without the inverse, by Householder reflections: no pivoting and so no selects and no row swaps.
+// a = Q R column by column, x <- Q^T x carried along and back-substituted (WITH_X).  Backward stable for every matrix: the computed x solves (a + E) x = x0 with |E| a small multiple of
+// 2^-23 |a|.  Returns the product of the diagonal of R, which is det(a) up to its sign.  A zero column gives 1 / 0 and NaN from there on.
+template <bool WITH_X>
+RNF_HD float qr4_solve(float (&a)[16], float (&x)[4]) {
+    float det = 1.0f, id0 = 0.f, id1 = 0.f, id2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float s2 = 0.f;
+#pragma unroll
+        for (int r = c; r < 4; ++r) s2 = fmaf(a[4 * r + c], a[4 * r + c], s2);
+        const float acc = a[4 * c + c];
+        const float alpha = -copysignf(hw_sqrt(s2), acc);                  // r_cc; v = (a_cc - alpha, a_rc ...), no cancellation
+        const float vc = acc - alpha;
+        const float beta = hw_rcp(fmaf(-acc, alpha, s2));                  // 2 / v.v = 1 / (s2 - a_cc alpha)
+        det *= alpha;
+        (c == 0 ? id0 : c == 1 ? id1 : id2) = hw_rcp(alpha);
+#pragma unroll
+        for (int k = c + 1; k < 4; ++k) {
+            float w = vc * a[4 * c + k];
+#pragma unroll
+            for (int r = c + 1; r < 4; ++r) w = fmaf(a[4 * r + c], a[4 * r + k], w);
+            w *= beta;
+            a[4 * c + k] = fmaf(-w, vc, a[4 * c + k]);
+#pragma unroll
+            for (int r = c + 1; r < 4; ++r) a[4 * r + k] = fmaf(-w, a[4 * r + c], a[4 * r + k]);
+        }
+        if constexpr (WITH_X) {
+            float w = vc * x[c];
+#pragma unroll
+            for (int r = c + 1; r < 4; ++r) w = fmaf(a[4 * r + c], x[r], w);
+            w *= beta;
+            x[c] = fmaf(-w, vc, x[c]);
+#pragma unroll
+            for (int r = c + 1; r < 4; ++r) x[r] = fmaf(-w, a[4 * r + c], x[r]);
+        }
+    }
+    det *= a[15];
+    if constexpr (WITH_X) {
+        x[3] = x[3] * hw_rcp(a[15]);
+        x[2] = fmaf(-a[11], x[3], x[2]) * id2;
+        x[1] = fmaf(-a[7], x[3], fmaf(-a[6], x[2], x[1])) * id1;
+        x[0] = fmaf(-a[3], x[3], fmaf(-a[2], x[2], fmaf(-a[1], x[1], x[0]))) * id0;
+    }
+    return det;
+}
+// Ms = 2^-e M with e = pow2_exponent16(M) (exact), Mi = Ms^-1, x <- Ms^-1 x; returns e and log|det Ms| in logabsdet.  With the largest
+// entry in [1, 2) the pivots and their product stay in range for every finite M of cond up to ~1e9, and every result is bit-equal for M
+// and 2^k M.  The cofactor form this replaces had a determinant of degree 4 in the entries: overflow near |M| ~ 1e9.5, zero near
+// 1e-9.5, and an error absolute in |M|^4.
+RNF_HD int inv4_scaled(const float (&m)[16], float (&ms)[16], float (&mi)[16], float (&x)[4], float &logabsdet) {
+    const int e = pow2_exponent16(m);
+    float a[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { ms[i] = ldexpf(m[i], -e); a[i] = ms[i]; mi[i] = (i % 5 == 0) ? 1.0f : 0.0f; }
+    logabsdet = logf(fabsf(gauss_jordan4<true, true>(a, mi, x)));
+    return e;
+}
+// 4x4 inverse and determinant (Condition16Trans.inverse: torch.linalg.inv, flow/squeezetrans.py:51-55; my_det_4_4: squeezetrans.py:17-22)
+// at the scale of M itself, for the callers that need M^-1 as a matrix.  Returns det(M) (infinite or zero where it leaves the fp32 range;
+// the inverse does not go through it).
+RNF_HD float inv4(const float (&m)[16], float (&o)[16]) {
+    float a[16], x[4];
+    const int e = pow2_exponent16(m);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { a[i] = ldexpf(m[i], -e); o[i] = (i % 5 == 0) ? 1.0f : 0.0f; }
+    const float det = gauss_jordan4<true, false>(a, o, x);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[i] = ldexpf(o[i], -e);
+    return ldexpf(det, 4 * e);
+}
+// calculate_16 with a per-sample M (Condition16Trans, Condition16TransLU; flow/squeezetrans.py:41-55,134-144), forward (q' = M q) and
+// inverse pass (q' = M^-1 q), on Ms = 2^-e M: R' and ldj = +-log|det M| - 4 log|q'| are of degree 0 in M, so nothing is multiplied back
+// and cond16_apply(2^k M) is bit-equal to cond16_apply(M).  The inverse pass solves Ms q' = q by qr4_solve (backward stable:
+// an error of 2^-23 cond(M), where a product with a computed inverse carries cond(M) twice); the forward pass forms Ms q first and then
+// factors in place for the diagonal of R, so one copy of the matrix is live.  NaN as affine16_finish_quat says; a rank deficient M divides by
+// a zero diagonal entry of R and ends there as well.  Domain and figures against LAPACK fp32: DESIGN.md section 3.7c, tests/test_aff16_host.py.
+RNF_HD void cond16_apply(float (&a)[16], bool inverse, Rot &R, float &ldj) {          // a is scaled and eliminated in place
+    float q[4], t[4];
+    rot_to_quat(R, q);
+    const int e = pow2_exponent16(a);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a[i] = ldexpf(a[i], -e);
+    float det;
+    if (inverse) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = q[i];
+        det = qr4_solve<true>(a, t);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            t[i] = fmaf(a[4 * i + 3], q[3], fmaf(a[4 * i + 2], q[2], fmaf(a[4 * i + 1], q[1], a[4 * i] * q[0])));
+        det = qr4_solve<false>(a, q);
+    }
+    const float lad = logf(fabsf(det));
+    affine16_finish_quat(t, inverse ? -lad : lad, R, ldj, false);
+}
+// log|det M| of a constant 4x4 (Uncondition16Trans in the training forward): the same prescale and elimination, the exponent added back
+RNF_HD float logabsdet4(const float (&m)[16]) {
+    float a[16], x[4];
+    const int e = pow2_exponent16(m);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a[i] = ldexpf(m[i], -e);
+    return logf(fabsf(qr4_solve<false>(a, x))) + 2.772588722239781f * (float)e;          // 4 e log 2
 }
 
 }  // namespace rnf

@@ -698,31 +698,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void flow_train_backward16_kernel(co
                 lds_barrier();
             } else {
                 // Condition16Trans (flow/squeezetrans.py:41-50): M = I + reshape(net(f), 4, 4), ldj = log|det M| - 2 log|M q|^2
-                float M[16], Mi[16], gM[16];
+                float M[16], gM[16];
 #pragma unroll
-                for (int i = 0; i < 16; ++i) { M[i] = Cm.at(i, c) + ((i % 5) == 0 ? 1.f : 0.f); gM[i] = 0.f; }
-                inv4(M, Mi);
-                Rot Rout;
-                AffineSaved sv;
-                float l;
-                if (args.dir) {                         // inverse pass: the layer applies M^-1 (squeezetrans.py:51-55), log|det M^-1| = -log|det M|
-                    float gMi[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) gMi[i] = 0.f;
-                    affine16_forward_saved(Mi, 0.f, Rin, Rout, l, sv);
-                    affine16_backward(Mi, sv, gR, g_ldj, false, gMi, gRin);
-                    inverse_matrix_grad<4>(Mi, gMi, gM);
-                } else {
-                    affine16_forward_saved(M, 0.f, Rin, Rout, l, sv);
-                    affine16_backward(M, sv, gR, g_ldj, false, gM, gRin);
-                }
-                const float gl = args.dir ? -g_ldj : g_ldj;
+                for (int i = 0; i < 16; ++i) M[i] = Cm.at(i, c) + ((i % 5) == 0 ? 1.f : 0.f);
+                cond16_backward(M, args.dir != 0, Rin, gR, g_ldj, gM, gRin);
                 lds_barrier();                          // every thread has read C
                 if (writer) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) Cm.at(4 * i + jj, c) = gM[4 * i + jj] + gl * Mi[4 * jj + i];
+                    for (int i = 0; i < 16; ++i) Cm.at(i, c) = gM[i];
                 }
                 lds_barrier();
             }
@@ -926,12 +909,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void flow_train_forward16_kernel(con
                 o[0] = R.c0.x; o[1] = R.c1.x; o[2] = R.c2.x; o[3] = R.c0.y; o[4] = R.c1.y; o[5] = R.c2.y; o[6] = R.c0.z; o[7] = R.c1.z; o[8] = R.c2.z;
             }
             if (!mlp) {                                   // Uncondition16Trans (squeezetrans.py:57-66) / UnconditionRot (rottrans.py:8-23)
-                float M[16], Mi[16];
+                float M[16];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) M[i] = P[i];
                 const bool orth = (d.x >> 8) & 1;
-                const float det = orth ? 1.f : inv4(M, Mi);
-                affine16_apply(M, logf(fabsf(det)), R, ldj, orth);
+                affine16_apply(M, orth ? 0.f : logabsdet4(M), R, ldj, orth);
                 continue;
             }
             const int p1 = (perm_row + 1) % 3;
@@ -1037,11 +1019,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void flow_train_forward16_kernel(con
                 set_col(R, sv.p2, sv.tzu * sv.inv_tzu);
                 ldj += logf(sm[2] / sm[0]);
             } else {                                      // Condition16Trans (squeezetrans.py:41-50): M = I + reshape(net(f), 4, 4)
-                float M[16], Mi[16];
+                float M[16];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) M[i] = Cm.at(i, c) + ((i % 5) == 0 ? 1.f : 0.f);
-                const float det = inv4(M, Mi);
-                affine16_apply(M, logf(fabsf(det)), R, ldj, false);
+                cond16_apply(M, false, R, ldj);
             }
             lds_barrier();                                // C and the reduction scratch are free again
         }

@@ -271,7 +271,7 @@ RNF_RARE_FN void rare_side(int kind, int dir, const float *m, const Rot *Rin, co
 #pragma unroll
                     for (int i = 0; i < 9; ++i) gM[i] = g9[i];
                 } else {
-                    float M[16], Mi[16];
+                    float M[16];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) M[i] = m[i];
                     const bool orth = kind == RNF_KIND_SIDE16_ROT;      // ConditionRot (rottrans.py:37-66): ldj = 0, inverse pass M^T
@@ -296,23 +296,7 @@ RNF_RARE_FN void rare_side(int kind, int dir, const float *m, const Rot *Rin, co
                             affine16_backward(M, sv, gRV, g_ldj, true, gM, gRin);
                         }
                     } else {                                // Condition16TransLU (squeezetrans.py:134-144): as Condition16Trans, M given
-                        inv4(M, Mi);
-                        if (dir) {
-                            float gMi[16];
-#pragma unroll
-                            for (int i = 0; i < 16; ++i) gMi[i] = 0.f;
-                            affine16_forward_saved(Mi, 0.f, RinV, Rout, l, sv);
-                            affine16_backward(Mi, sv, gRV, g_ldj, false, gMi, gRin);
-                            inverse_matrix_grad<4>(Mi, gMi, gM);
-                        } else {
-                            affine16_forward_saved(M, 0.f, RinV, Rout, l, sv);
-                            affine16_backward(M, sv, gRV, g_ldj, false, gM, gRin);
-                        }
-                        const float gl = dir ? -g_ldj : g_ldj;      // d log|det M| / dM = M^-T
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) gM[4 * i + jj] += gl * Mi[4 * jj + i];
+                        cond16_backward(M, dir != 0, RinV, gRV, g_ldj, gM, gRin);
                     }
                 }
     }
@@ -737,31 +721,14 @@ __global__ __launch_bounds__(TR_WAVES * 64) void flow_train_backward_kernel(cons
                 lds_barrier();
             } else {
                 // Condition16Trans (flow/squeezetrans.py:41-50): M = I + reshape(net(f), 4, 4), ldj = log|det M| - 2 log|M q|^2
-                float M[16], Mi[16], gM[16];
+                float M[16], gM[16];
 #pragma unroll
-                for (int i = 0; i < 16; ++i) { M[i] = Cm.at(i, lane) + ((i % 5) == 0 ? 1.f : 0.f); gM[i] = 0.f; }
-                inv4(M, Mi);
-                Rot Rout;
-                AffineSaved sv;
-                float l;
-                if (args.dir) {                         // inverse pass: the layer applies M^-1 (squeezetrans.py:51-55), log|det M^-1| = -log|det M|
-                    float gMi[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) gMi[i] = 0.f;
-                    affine16_forward_saved(Mi, 0.f, Rin, Rout, l, sv);
-                    affine16_backward(Mi, sv, gR, g_ldj, false, gMi, gRin);
-                    inverse_matrix_grad<4>(Mi, gMi, gM);
-                } else {
-                    affine16_forward_saved(M, 0.f, Rin, Rout, l, sv);
-                    affine16_backward(M, sv, gR, g_ldj, false, gM, gRin);
-                }
-                const float gl = args.dir ? -g_ldj : g_ldj;
+                for (int i = 0; i < 16; ++i) M[i] = Cm.at(i, lane) + ((i % 5) == 0 ? 1.f : 0.f);
+                cond16_backward(M, args.dir != 0, Rin, gR, g_ldj, gM, gRin);
                 lds_barrier();                          // every wave has read C
                 if (wave == 0) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) Cm.at(4 * i + jj, lane) = gM[4 * i + jj] + gl * Mi[4 * jj + i];
+                    for (int i = 0; i < 16; ++i) Cm.at(i, lane) = gM[i];
                 }
                 lds_barrier();
             }

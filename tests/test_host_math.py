@@ -1,6 +1,6 @@
 """CPU: csrc/so3_math.h compiled for the host (tests/csrc/host_math.cpp) against float64 numpy / the oracle.
 Checks the algebra the kernels use per sample: branch-free softplus, the [0,2pi) arctangent, small-range sincos, the
-cofactor 4x4 inverse, calculate_16, and the 2-D in-plane Moebius layer against the oracle's 3-D formulation."""
+4x4 inverse, calculate_16, and the 2-D in-plane Moebius layer against the oracle's 3-D formulation."""
 import ctypes as C
 import os
 import subprocess
