@@ -499,6 +499,79 @@ int rnf_grid_credible(const RnfGridCredible *credible);
  * n_queries are out of range. */
 size_t rnf_grid_credible_workspace_bytes(const RnfGridCredible *credible);
 
+/* The grid cell of rotations: the inverse of the row function of rnf_so3_healpix_grid (csrc/grid_locate.h).  With R' = R O^T (O the
+ * offset, the identity when NULL) written as Rx(phi) Rz(theta) Rx(tau):
+ *   z = R'00 clipped to [-1, 1], sin(theta) = hypot(R'10, R'20), phi = atan2(R'20, R'10), tau = atan2(R'02, -R'01);
+ *   p = ang2pix in the RING ordering at nside = 2^level (Gorski et al. 2005), in the polar caps (|z| > 2/3) with sin(theta) and not
+ *       sqrt(1 - z^2): tmp = nside sin(theta) / sqrt((1 + |z|) / 3);
+ *   t = rint(tau / (2 pi / (6 nside))) mod 6 nside, so that a cell is centred on its grid tilt;  row = t * npix + p.
+ * At a pole, R'10 = R'20 = 0 exactly: phi = 0 and tau = atan2(R'21, R'11) for z > 0, atan2(R'21, R'22) for z < 0.
+ * fp64 inside from the fp32 entries, one thread per rotation.  A rotation with a non-finite entry has row -1.  Every row of the level's
+ * grid (with the same offset) is located in its own cell.
+ * What a cell is: the rotations that this function maps to the row.  The 72 * 8^level cells partition SO(3) into parts of equal Haar
+ * volume, which is what makes a histogram over them comparable with exp(lp_i) / Q.  What it is not: the Voronoi cell of the grid
+ * rotation; at level 1 about 73 % of Haar-uniform rotations lie in the cell whose grid rotation is also their geodesically nearest one.
+ * rows_out and counts are both optional, at least one is required.  With counts, counts[b][row] is incremented by an integer atomic
+ * for every rotation of image b whose row is not -1: integer sums do not depend on their order, so the counts are bit-identical from run
+ * to run.  counts is accumulated into and never cleared: clear it before the first call, then stream a sample set through any number
+ * of calls (a cell's count must stay below 2^31).  n = 0 is a no-op.  Stream-ordered, no host synchronisation, capturable. */
+typedef struct RnfGridLocate {
+    size_t struct_bytes;        /* sizeof(RnfGridLocate); any other value is refused (header and library differ) */
+    int32_t level;              /* 0..8; with counts 0..6: Q = 72 * 8^level <= 2^26 */
+    const float *rotations;     /* dev float[g][n][9] row-major */
+    int64_t n;                  /* rotations per image, 0..2^36 */
+    int32_t g;                  /* images, 1..65535 */
+    const float *offset;        /* dev float[9] row-major, or NULL (identity): the offset the grid was generated with */
+    int64_t *rows_out;          /* dev int64[g][n], or NULL */
+    int32_t *counts;            /* dev int32[g][Q], or NULL */
+    void *stream;
+} RnfGridLocate;
+int rnf_so3_grid_locate(const RnfGridLocate *locate);
+
+/* How well g histograms over the grid's cells (rnf_so3_grid_locate) fit g densities on the grid (csrc/grid_locate.h).  Per image, with
+ * c_i >= 0 the count of cell i (a negative count is read as 0), n = sum c_i, M the maximum of its log p (the first arg-max, a NaN
+ * winning), w_i = expf(lp_i - M) (the fp32 exponential of rnf_grid_modes), Z = sum w_i and p_i = w_i / Z -- the density at the cell's
+ * grid rotation, normalised over the grid: a midpoint value, not the cell's exact mass --
+ *   stats[b][RNF_GRID_FIT_LOG_NORM]             M + log Z - log Q, rnf_grid_modes' log_norm to 1e-6;
+ *   stats[b][RNF_GRID_FIT_LOG_LIKELIHOOD]       (1/n) sum c_i lp_i: the mean log p at the grid rotations of the samples' cells;
+ *   stats[b][RNF_GRID_FIT_GRID_LOG_LIKELIHOOD]  log_likelihood - log_norm: the mean of log(p_i Q), IPDF's grid-normalised metric;
+ *   stats[b][RNF_GRID_FIT_G]                    2 sum_{c_i > 0} c_i (log(c_i / n) - log p_i): the likelihood-ratio statistic, 2 n KL;
+ *   stats[b][RNF_GRID_FIT_CHI2]                 sum (c_i - n p_i)^2 / (n p_i): Pearson's statistic;
+ *   stats[b][RNF_GRID_FIT_N]                    n;   stats[b][RNF_GRID_FIT_OCCUPIED]  the number of cells with c_i > 0 (both exact).
+ * After M, one pass: Z, S1 = sum c_i log c_i, S2 = sum c_i (lp_i - M), S3 = sum c_i^2 / w_i over the occupied cells, all in fp64, n and
+ * the occupied cells as integers; g_stat = 2 (S1 - S2 + n log Z - n log n), chi2 = Z S3 / n - n.
+ * Edge cases: a -inf cell with c_i = 0 contributes nothing.  An occupied cell with w_i = 0 -- lp_i = -inf, or expf underflowed, about
+ * 104 below M -- makes log_likelihood -inf and g_stat = chi2 = +inf (grid_log_likelihood -inf, NaN when the row has no finite value).
+ * A NaN in the image's log p, or a maximum of +inf: the five statistics are NaN, n and occupied are still counted.  n = 0: log_norm as
+ * otherwise, the other four NaN.  A row without a finite value has log_norm -inf.
+ * Deterministic: blocks per image depend on Q alone, fixed per-thread order, fixed shuffle trees, the finalise sums the block partials
+ * in index order, no floating-point atomics -- bit-identical from run to run and whatever g.  Stream-ordered, no host synchronisation,
+ * capturable in a HIP graph. */
+#define RNF_GRID_FIT_LOG_NORM 0
+#define RNF_GRID_FIT_LOG_LIKELIHOOD 1
+#define RNF_GRID_FIT_GRID_LOG_LIKELIHOOD 2
+#define RNF_GRID_FIT_G 3
+#define RNF_GRID_FIT_CHI2 4
+#define RNF_GRID_FIT_N 5
+#define RNF_GRID_FIT_OCCUPIED 6
+#define RNF_GRID_FIT_STATS 7
+typedef struct RnfGridFit {
+    size_t struct_bytes;        /* sizeof(RnfGridFit); any other value is refused (header and library differ) */
+    const float *logp;          /* dev float[g][Q]: image b's log p on grid row i */
+    const int32_t *counts;      /* dev int32[g][Q]: image b's samples in cell i */
+    int64_t Q;                  /* 1..2^26 */
+    int32_t g;                  /* images, 1..65535 */
+    double *stats_out;          /* dev double[g][RNF_GRID_FIT_STATS] */
+    /* dev scratch, 8-byte aligned, of at least rnf_grid_fit_workspace_bytes(this struct) bytes =
+     * g * (16 min(ceil(Q / 2048), 2048) + 48 min(ceil(Q / 8192), 512) + 12) rounded up to 16: the maximum's and the pass's block partials */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfGridFit;
+int rnf_grid_fit(const RnfGridFit *fit);
+/* The workspace rnf_grid_fit requires for the same struct (the pointers are not read); 0 when struct_bytes, g or Q are out of range. */
+size_t rnf_grid_fit_workspace_bytes(const RnfGridFit *fit);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

@@ -60,6 +60,21 @@ class GridCredible(_Pass):
                 ("query_count_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class GridLocate(_Pass):
+    """RnfGridLocate (include/rnf_hip.h): the grid cell of rotations, and their histogram over the cells."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("rotations", C.c_void_p), ("n", C.c_int64), ("g", C.c_int32),
+                ("offset", C.c_void_p), ("rows_out", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class GridFit(_Pass):
+    """RnfGridFit (include/rnf_hip.h): how well histograms over the grid's cells fit densities on the grid."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("logp", C.c_void_p), ("counts", C.c_void_p), ("Q", C.c_int64), ("g", C.c_int32),
+                ("stats_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+GRID_FIT_STATS = ("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
+
+
 class GridChildren(_Pass):
     """RnfGridChildren (include/rnf_hip.h): the 12 children of SO(3) grid rows one level down, and their rotations."""
     _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("parents", C.c_void_p), ("n", C.c_int64), ("offset", C.c_void_p),
@@ -148,6 +163,9 @@ _SIGNATURES = {
     "rnf_grid_credible": (C.c_int, [C.POINTER(GridCredible)]),
     "rnf_grid_credible_workspace_bytes": (C.c_size_t, [C.POINTER(GridCredible)]),
     "rnf_so3_grid_children": (C.c_int, [C.POINTER(GridChildren)]),
+    "rnf_so3_grid_locate": (C.c_int, [C.POINTER(GridLocate)]),
+    "rnf_grid_fit": (C.c_int, [C.POINTER(GridFit)]),
+    "rnf_grid_fit_workspace_bytes": (C.c_size_t, [C.POINTER(GridFit)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -30,6 +30,7 @@
 #include "so3_grid.h"
 #include "grid_beam.h"
 #include "grid_credible.h"
+#include "grid_locate.h"
 
 using namespace rnf;
 
@@ -1593,6 +1594,67 @@ extern "C" int rnf_grid_credible(const RnfGridCredible *p) {
                            (long long *)p->count_out, p->mass_out, p->log_norm_out, p->query_mass_out, (long long *)p->query_count_out);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// The cell of a rotation and the histogram over the cells (csrc/grid_locate.h): one thread per rotation.
+extern "C" int rnf_so3_grid_locate(const RnfGridLocate *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridLocate))
+        return fail("RnfGridLocate.struct_bytes does not match the library's %zu", sizeof(RnfGridLocate));
+    if (p->level < 0 || p->level > so3g::MAX_LEVEL) return fail("RnfGridLocate.level=%d outside 0..%d", p->level, so3g::MAX_LEVEL);
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridLocate.g=%d outside 1..65535", p->g);
+    if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridLocate.n=%lld outside 0..2^36", (long long)p->n);
+    if (!p->rows_out && !p->counts) return fail("RnfGridLocate: null rows_out and counts (at least one output)");
+    if (p->counts && (72LL << (3 * p->level)) > gl::MAX_Q)
+        return fail("RnfGridLocate.counts: Q=%lld rows of level %d exceed 2^26", 72LL << (3 * p->level), p->level);
+    if (p->n == 0) return 0;
+    if (!p->rotations) return fail("RnfGridLocate: null rotations");
+    const long long total = (long long)p->g * p->n;
+    long long blocks = (total + gl::THREADS - 1) / gl::THREADS;
+    if (blocks > (1LL << 20)) blocks = 1LL << 20;
+    hipLaunchKernelGGL(gl::so3_grid_locate_kernel, dim3((unsigned)blocks), dim3(gl::THREADS), 0, reinterpret_cast<hipStream_t>(p->stream),
+                       (int)p->level, (long long)p->n, total, p->rotations, p->offset, (long long *)p->rows_out, (int *)p->counts);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The fit of a histogram against a grid density (csrc/grid_locate.h): the row maximum by grid_modes.h's arg-max pass, one pass, its finalise.
+static int grid_fit_check(const RnfGridFit *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridFit)) return fail("RnfGridFit.struct_bytes does not match the library's %zu", sizeof(RnfGridFit));
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridFit.g=%d outside 1..65535", p->g);
+    if (p->Q < 1 || p->Q > gl::MAX_Q) return fail("RnfGridFit.Q=%lld outside 1..2^26", (long long)p->Q);
+    return 0;
+}
+
+extern "C" size_t rnf_grid_fit_workspace_bytes(const RnfGridFit *p) {
+    if (grid_fit_check(p)) return 0;
+    return gl::carve(nullptr, p->Q, p->g).bytes;
+}
+
+extern "C" int rnf_grid_fit(const RnfGridFit *p) {
+    if (grid_fit_check(p)) return 1;
+    if (!p->logp || !p->counts || !p->stats_out) return fail("RnfGridFit: null logp, counts or stats_out");
+    const size_t need = rnf_grid_fit_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfGridFit.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_fit_workspace_bytes)", p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridFit.workspace must be 8-byte aligned");
+    static_assert(gl::N_STATS == RNF_GRID_FIT_STATS, "csrc/grid_locate.h and include/rnf_hip.h disagree on the statistics");
+    const gl::Workspace w = gl::carve(p->workspace, p->Q, p->g);
+    const long long Q = p->Q;
+    const int nbm = (int)gm::blocks_for(Q), nb = (int)gl::blocks_for(Q);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
+                       (const long long *)w.max_index, (const float *)w.max_value, w.max_part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
+                       w.max_index, w.max_value);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gl::grid_fit_kernel, dim3(nb, p->g), dim3(gl::THREADS), 0, s, p->logp, (const int *)p->counts, Q,
+                       (const float *)w.max_value, w.part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gl::grid_fit_final_kernel, dim3(p->g), dim3(gl::THREADS), 0, s, (const gl::FitPart *)w.part, nb, Q,
+                       (const float *)w.max_value, p->stats_out);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -1,9 +1,9 @@
 """The grid analyses: evaluate a flow's log-density on the HEALPix grid over SO(3) (``utils.sd``) and reduce each image's row on the
 device -- the arg-max of ``eval.py``'s ``log_pdf`` mode (``grid_estimate_rotations``), top-k modes with their mass (``grid_pose_modes``),
-highest-density credible sets (``grid_pose_credible``), matrix-Fisher and mixture fits (``grid_pose_fisher``, ``grid_pose_mixture``) and the
-coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path from (flow, feature, base) to log-density rows
-(``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_children`` and ``grid_beam_select`` are the reductions' entry points of the
-library on rows already at hand.  ``harness`` re-exports the public functions.
+highest-density credible sets (``grid_pose_credible``), samples against the density (``grid_pose_fit``), matrix-Fisher and mixture fits
+(``grid_pose_fisher``, ``grid_pose_mixture``) and the coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path
+from (flow, feature, base) to log-density rows (``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_fit``, ``grid_children`` and
+``grid_beam_select`` are the reductions' entry points of the library on rows already at hand.  ``harness`` re-exports the public functions.
 """
 from __future__ import annotations
 
@@ -323,6 +323,112 @@ def grid_pose_credible(flow: Flow, feature: torch.Tensor = None, levels=(0.5, 0.
     out = dict(threshold=threshold, count=count, volume=volume, mass=mass, log_norm=log_norm, offset=offset)
     if gt is not None:
         out.update(gt_log_prob=gt_log_prob, gt_level=gt_level[:, 0], gt_inside=gt_log_prob[:, None] >= threshold)
+    return out
+
+
+GRID_FIT_MAX_ROWS = 1 << 26                        # rnf_grid_fit's and the histogram's limit (include/rnf_hip.h): level 6 fits
+
+
+def grid_fit(logp: torch.Tensor, counts: torch.Tensor) -> dict:
+    """``rnf_grid_fit`` on g images: how well the histogram ``counts`` [g,Q] (int32, ``sd.grid_histogram``) of n samples fits the density
+    ``logp`` [g,Q] (float32) on the same grid, both on the device (include/rnf_hip.h).  With p_i = softmax(logp)_i, the density at cell
+    i's grid rotation normalised over the grid -- a midpoint value of the density, not the cell's exact mass:
+    ``log_norm`` = log(sum_i exp(lp_i) / Q); ``log_likelihood`` = the mean log p at the grid rotations of the samples' cells;
+    ``grid_log_likelihood`` = log_likelihood - log_norm, the mean of log(p_i Q) (IPDF's metric); ``g_stat`` = 2 sum c_i log(c_i / (n p_i))
+    and ``chi2`` = sum (c_i - n p_i)^2 / (n p_i); ``n``, ``occupied`` (cells with a sample; both int64, exact); ``kl`` = g_stat / (2 n),
+    the KL divergence from the empirical histogram to the grid density in nats (its sampling floor is (Q - 1) / (2 n)); ``dof`` = Q - 1 and
+    ``z`` = (g_stat - dof) / sqrt(2 dof).  ``z`` reads as a standard normal under "the samples come from p" only when the chi-square
+    limit holds, i.e. with n / Q of a few or more samples per cell, and only as far as the midpoint values stand for the cells' masses.
+    Deterministic: bit-identical from run to run and whatever g.
+    -> dict(log_norm, log_likelihood, grid_log_likelihood, g_stat, chi2, kl, z: float64 [g]; n, occupied: int64 [g]; dof: int)"""
+    if logp.dim() != 2 or counts.dim() != 2 or logp.shape != counts.shape:
+        raise ValueError(f"grid_fit: logp {tuple(logp.shape)} and counts {tuple(counts.shape)} (want [g,Q] both)")
+    g, Q = logp.shape
+    if not 1 <= Q <= GRID_FIT_MAX_ROWS:
+        raise ValueError(f"grid_fit: {Q} grid rows (1 to 2^26)")
+    if not 1 <= g <= 65535:
+        raise ValueError(f"grid_fit: {g} images (1 to 65535)")
+    if counts.dtype != torch.int32:
+        raise ValueError(f"grid_fit: counts of dtype {counts.dtype} (want int32, as grid_histogram returns)")
+    if not logp.is_cuda or not counts.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    dev = logp.device
+    lp = logp.detach().to(torch.float32).contiguous()
+    cn = counts.to(dev).contiguous()
+    stats = torch.empty(g, len(_lib.GRID_FIT_STATS), dtype=torch.float64, device=dev)
+    _lib.call("grid_fit", _lib.GridFit(logp=lp.data_ptr(), counts=cn.data_ptr(), Q=Q, g=g, stats_out=stats.data_ptr()), dev)
+    out = {name: stats[:, i] for i, name in enumerate(_lib.GRID_FIT_STATS)}
+    n = out["n"]
+    out["kl"] = out["g_stat"] / (2.0 * n)
+    out["dof"] = Q - 1
+    out["z"] = (out["g_stat"] - (Q - 1)) / float(np.sqrt(2.0 * (Q - 1))) if Q > 1 else torch.full_like(n, float("nan"))
+    out["n"], out["occupied"] = n.to(torch.int64), out["occupied"].to(torch.int64)
+    return out
+
+
+def grid_pose_fit(flow: Flow, feature: torch.Tensor = None, samples: torch.Tensor = None, n_samples: int = 1 << 18, recursion_level: int = 2,
+                  offset=None, base=None, images_per_launch: int = None) -> dict:
+    """Samples against the flow's density, on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk gathering of
+    ``grid_pose_modes``): each image's ``samples`` are binned into the grid's cells (``sd.grid_histogram`` at the offset the density is
+    evaluated at) and the histogram is held against the image's log-density row (``grid_fit``, whose statistics are returned).
+    ``samples`` [B,n,3,3], or [n,3,3] for one image or an unconditional flow without a B-row base: ground truths (one, or all symmetric
+    ones of an image: ``grid_log_likelihood`` is then IPDF's log-likelihood of the ground truth's cell), rotations of a dataset (``kl``:
+    data against model), samples of another model.  ``samples`` None: ``n_samples`` per image are drawn from the flow itself --
+    ``base.sample`` (``sd.random_rotations`` without a base) through ``flow.inverse`` with the image's feature row, in launches of at
+    most the module's launch budget, accumulated into one histogram -- so ``kl`` and ``z`` say whether the sampler and the density agree
+    (``kl`` against its floor (Q - 1) / (2 n)).  Flows with batch-coupled layers take one image per launch, as in ``grid_pose_credible``.
+    Limits (ValueError before any launch): recursion_level 0..6 (Q <= 2^26), n_samples >= 1.
+    -> ``grid_fit``'s dict (every entry [B]; ``log_norm`` is the grid's) plus counts [B,Q] int32 and offset [3,3]"""
+    who = "grid_pose_fit"
+    level = int(recursion_level)
+    if not 0 <= level <= sd.MAX_LEVEL or sd.grid_size(level) > GRID_FIT_MAX_ROWS:
+        raise ValueError(f"{who}: recursion_level={recursion_level} outside 0..6 (at most 2^26 grid rows)")
+    if samples is None and int(n_samples) < 1:
+        raise ValueError(f"{who}: n_samples={n_samples} (at least 1)")
+    if samples is not None and (samples.dim() not in (3, 4) or tuple(samples.shape[-2:]) != (3, 3)):
+        raise ValueError(f"{who}: samples of shape {tuple(samples.shape)} (want [B,n,3,3] or [n,3,3])")
+    if images_per_launch is not None and int(images_per_launch) < 1:
+        raise ValueError(f"{who}: images_per_launch={images_per_launch}")
+    gf, level, offset = _grid_inputs(flow, feature, None, level, offset, base, who)
+    B, dev = gf.B, gf.dev
+    if B > 65535:
+        raise ValueError(f"{who}: {B} images (at most 65535)")
+    if samples is not None:
+        if samples.dim() == 3:
+            samples = samples[None]
+        if samples.shape[0] != B:
+            raise ValueError(f"{who}: samples for {samples.shape[0]} images, {B} images")
+        samples = samples.to(device=dev, dtype=torch.float32)
+    Q = sd.grid_size(level)
+    with torch.no_grad():
+        if samples is not None:
+            counts = sd.grid_histogram(samples, level, offset)
+        else:
+            counts = torch.zeros(B, Q, dtype=torch.int32, device=dev)
+            total = int(n_samples)
+            step = 1 if gf.coupled else min(B, gf.budget)               # images per sampling launch
+            for b0 in range(0, B, step):
+                b1 = min(B, b0 + step)
+                k = b1 - b0
+                mf = None
+                if gf.A is not None:                                    # the images' base rows; a single row serves them all
+                    mf = fisher.MatrixFisherN(gf.A if gf.A.shape[0] == 1 else gf.A[b0:b1])
+                per = max(1, gf.budget // k)
+                for s0 in range(0, total, per):
+                    m = min(per, total - s0)
+                    if mf is None:
+                        z = sd.random_rotations(k * m, device=dev)
+                    else:
+                        z = mf.sample(k * m if gf.A.shape[0] == 1 else m).reshape(k * m, 3, 3)
+                    feat = gf.feature[b0:b1] if gf.feature is not None else None
+                    x = flow.inverse(z, feat, feature_repeat=m if feat is not None else None)[0]
+                    sd.grid_histogram(x.reshape(k, m, 3, 3), level, offset, out=counts[b0:b1])
+        grid = sd.generate_healpix_grid(level, device=dev, offset=offset)
+        fits = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            fits.append(grid_fit(lp, counts[b0:b1]))
+    out = fits[0] if len(fits) == 1 else {k: (torch.cat([f[k] for f in fits]) if k != "dof" else Q - 1) for k in fits[0]}
+    out.update(counts=counts, offset=offset)
     return out
 
 

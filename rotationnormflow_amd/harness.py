@@ -29,7 +29,7 @@ from . import runtime
 from .flow.flow import Flow
 # the grid analyses live in grid_pose.py; their public functions stay reachable as harness.<name>
 from .grid_pose import (grid_beam_estimate_rotations, grid_beam_select, grid_children, grid_credible, grid_estimate_rotations,  # noqa: F401
-                        grid_modes, grid_pose_credible, grid_pose_fisher, grid_pose_mixture, grid_pose_modes)
+                        grid_fit, grid_modes, grid_pose_credible, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes)
 
 
 def load_reference_checkpoint(path, map_location="cpu") -> dict:

@@ -4,6 +4,9 @@ equivolumetric HEALPix grid over SO(3) of the IPDF line (Yershova et al. 2010), 
 The grid is generated on the GPU by ``rnf_so3_healpix_grid`` (no healpy, scipy or numpy build on the host), optionally already multiplied on
 the right by an offset rotation (eval.py:440-442 ``grid @ random_rot``).  As in the reference, the functions return CPU tensors unless a
 ``device`` is given; the GPU does the work either way.
+
+``grid_index`` and ``grid_histogram`` go the other way, from rotations on the device to the grid cells that hold them
+(``rnf_so3_grid_locate``).
 """
 import numpy as np
 import torch
@@ -86,3 +89,59 @@ def generate_queries(number_queries, mode="random", device=None) -> torch.Tensor
     if mode == "grid":
         return get_closest_available_grid(number_queries, device=device)
     raise ValueError(f"generate_queries: mode must be 'random' or 'grid', got {mode!r}")
+
+
+GRID_HISTOGRAM_MAX_ROWS = 1 << 26                  # rnf_so3_grid_locate's limit on a histogram (include/rnf_hip.h): level 6 fits
+
+
+def _locate_inputs(rotations, recursion_level, offset, who: str, histogram: bool = False):
+    """Argument checks of the locate functions, all before a launch -> (level, rotations float32 contiguous, offset [9] or None)."""
+    level = int(recursion_level)
+    if not 0 <= level <= MAX_LEVEL:
+        raise ValueError(f"{who}: recursion level {level} outside 0..{MAX_LEVEL}")
+    if rotations.dim() < 2 or tuple(rotations.shape[-2:]) != (3, 3) or (histogram and rotations.dim() not in (3, 4)):
+        raise ValueError(f"{who}: rotations of shape {tuple(rotations.shape)} (want {'[n,3,3] or [g,n,3,3]' if histogram else '[..., 3, 3]'})")
+    if histogram and grid_size(level) > GRID_HISTOGRAM_MAX_ROWS:
+        raise ValueError(f"{who}: level {level} has {grid_size(level)} grid rows (at most 2^26)")
+    if offset is not None and offset.numel() != 9:
+        raise ValueError(f"{who}: offset of shape {tuple(offset.shape)} (want [3, 3])")
+    if not rotations.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    rot = rotations.detach().to(torch.float32).contiguous()
+    off = offset.detach().reshape(9).to(device=rot.device, dtype=torch.float32).contiguous() if offset is not None else None
+    return level, rot, off
+
+
+def grid_index(rotations: torch.Tensor, recursion_level: int, offset=None) -> torch.Tensor:
+    """The row of ``generate_healpix_grid(recursion_level, offset=offset)`` whose cell holds each of ``rotations`` [..., 3, 3] (on the
+    device): the inverse of the grid's row function (``rnf_so3_grid_locate``, include/rnf_hip.h).  Every grid row is in its own cell; the
+    cells have equal Haar volume and are not the Voronoi cells of the grid rotations.  A rotation with a non-finite entry has row -1.
+    -> int64 [...]"""
+    level, rot, off = _locate_inputs(rotations, recursion_level, offset, "grid_index")
+    rows = torch.empty(rot.shape[:-2], dtype=torch.int64, device=rot.device)
+    if rows.numel() == 0:                                  # nothing to locate (an empty tensor has no address to pass)
+        return rows
+    _lib.call("so3_grid_locate", _lib.GridLocate(level=level, rotations=rot.data_ptr(), n=rows.numel(), g=1,
+                                                  offset=off.data_ptr() if off is not None else None, rows_out=rows.data_ptr()), rot.device)
+    return rows
+
+
+def grid_histogram(rotations: torch.Tensor, recursion_level: int, offset=None, out: torch.Tensor = None) -> torch.Tensor:
+    """How many of each image's ``rotations`` ([n,3,3]: one image, or [g,n,3,3]; on the device) lie in each cell of the level's grid
+    (``grid_index``'s cells; rows -1 are not counted) -> int32 [g, 72 * 8^level].  With ``out`` (int32 [g,Q], contiguous, on the
+    device) the counts are added to it and it is returned, so a large sample set can be streamed through several calls.  Integer atomics:
+    bit-identical from run to run.  Levels 0..6 (Q <= 2^26), g <= 65535."""
+    level, rot, off = _locate_inputs(rotations, recursion_level, offset, "grid_histogram", histogram=True)
+    Q = grid_size(level)
+    g, n = (1, rot.shape[0]) if rot.dim() == 3 else rot.shape[:2]
+    if not 1 <= g <= 65535:
+        raise ValueError(f"grid_histogram: {g} images (1 to 65535)")
+    if out is None:
+        out = torch.zeros(g, Q, dtype=torch.int32, device=rot.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (g, Q) or not out.is_contiguous() or out.device != rot.device:
+        raise ValueError(f"grid_histogram: out must be a contiguous int32 [{g},{Q}] tensor on {rot.device}")
+    if n == 0:
+        return out
+    _lib.call("so3_grid_locate", _lib.GridLocate(level=level, rotations=rot.data_ptr(), n=n, g=g,
+                                                  offset=off.data_ptr() if off is not None else None, counts=out.data_ptr()), rot.device)
+    return out
