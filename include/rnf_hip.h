@@ -572,6 +572,47 @@ int rnf_grid_fit(const RnfGridFit *fit);
 /* The workspace rnf_grid_fit requires for the same struct (the pointers are not read); 0 when struct_bytes, g or Q are out of range. */
 size_t rnf_grid_fit_workspace_bytes(const RnfGridFit *fit);
 
+/* Pairwise sums of isotropic matrix-Fisher kernels between two sets of rotations (csrc/so3_kernel_sum.h): the kernel density estimate
+ * on SO(3) and the prediction step of a Bayes filter on the SO(3) grid.  With w_g = softmax(log_weights[g]) over the n centres (w = 1/n
+ * without log-weights),
+ *   out[g][a][i] = log sum_j w_gj k_a(C_j, Q_i),   k_kappa(C, Q) = exp(-(kappa/2) |Q - C|_F^2 - l(kappa)),
+ *   l(kappa) = c(kappa I) - 3 kappa = log(i0e(2 kappa) - i1e(2 kappa)) in fp64, l(0) = 0:
+ * k_kappa(C, .) is the density of MF(kappa C) w.r.t. the Haar probability measure.  The exponent is formed from the nine differences of
+ * the fp32 entries, never from tr(C^T Q) - 3, which loses all digits for sharp kernels.  Each (g, a, i) is a log-sum-exp about its
+ * largest term: finite whenever a finite weight exists (a query 90 degrees from its nearest centre at kappa = 1e4 returns about -1e4).
+ * leave_one_out != 0: the queries are the centres (queries NULL or == centres, m == n) and
+ *   out[g][a][i] = log sum_{j != i} w_gj k_a(C_j, C_i) - log1p(-w_gi);   only index i is left out, a duplicate of C_i elsewhere counts.
+ * Edge cases: a centre with log-weight -inf is left out whatever its entries; any other centre with a non-finite entry, or a NaN
+ * log-weight, makes every output of that group NaN; a query with a non-finite entry is NaN; a group with no mass left (all weights
+ * -inf, leave-one-out with n = 1, w_gi = 1) is NaN.  m = 0 is a no-op.
+ * Deterministic: the centres are split into chunks of 4096 (a function of n alone), one (max, sum) partial is written per (query,
+ * bandwidth, group, chunk) -- fp32 sums over at most 64 centres, fp64 above -- and a finalise combines the chunk partials in chunk
+ * order in fp64, subtracts the normalisers and rounds once to fp32; no floating-point atomics.  A query's result is bit-identical from
+ * run to run and whatever m, G, the query's position and the group's position are: queries and groups may be tiled over calls.
+ * Four launches.  Stream-ordered, no host synchronisation, capturable in a HIP graph as a linear chain. */
+typedef struct RnfSo3KernelSum {
+    size_t struct_bytes;        /* sizeof(RnfSo3KernelSum); any other value is refused (header and library differ) */
+    const float *centres;       /* dev float[n][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9] row-major, 16-byte aligned, or NULL: the centres (then m must be n) */
+    const float *log_weights;   /* dev float[G][n], or NULL (uniform weights) */
+    int64_t n;                  /* centres, 1..2^24 */
+    int64_t m;                  /* queries, 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    const double *kappas;       /* HOST double[J], each finite in 0..1e6 */
+    int32_t J;                  /* bandwidths, 1..8 */
+    int32_t leave_one_out;      /* 0, or != 0 as above */
+    float *out;                 /* dev float[G][J][m] */
+    /* dev scratch, 8-byte aligned, of at least rnf_so3_kernel_sum_workspace_bytes(this struct) bytes =
+     * 12 G J ceil(n / 4096) m + 16 G ceil(n / 4096) + 8 G rounded up to 16 */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3KernelSum;
+int rnf_so3_kernel_sum(const RnfSo3KernelSum *sum);
+/* The workspace rnf_so3_kernel_sum requires for the same struct (the pointers are not read); 0 when struct_bytes, J, G, n or m are out of
+ * range or the size does not fit. */
+size_t rnf_so3_kernel_sum_workspace_bytes(const RnfSo3KernelSum *sum);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

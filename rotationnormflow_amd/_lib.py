@@ -72,6 +72,13 @@ class GridFit(_Pass):
                 ("stats_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class So3KernelSum(_Pass):
+    """RnfSo3KernelSum (include/rnf_hip.h): pairwise sums of matrix-Fisher kernels between two sets of rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("queries", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64),
+                ("m", C.c_int64), ("G", C.c_int32), ("kappas", C.c_void_p), ("J", C.c_int32), ("leave_one_out", C.c_int32), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 GRID_FIT_STATS = ("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
@@ -166,6 +173,8 @@ _SIGNATURES = {
     "rnf_so3_grid_locate": (C.c_int, [C.POINTER(GridLocate)]),
     "rnf_grid_fit": (C.c_int, [C.POINTER(GridFit)]),
     "rnf_grid_fit_workspace_bytes": (C.c_size_t, [C.POINTER(GridFit)]),
+    "rnf_so3_kernel_sum": (C.c_int, [C.POINTER(So3KernelSum)]),
+    "rnf_so3_kernel_sum_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelSum)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -31,6 +31,7 @@
 #include "grid_beam.h"
 #include "grid_credible.h"
 #include "grid_locate.h"
+#include "so3_kernel_sum.h"
 
 using namespace rnf;
 
@@ -1654,6 +1655,83 @@ extern "C" int rnf_grid_fit(const RnfGridFit *p) {
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(gl::grid_fit_final_kernel, dim3(p->g), dim3(gl::THREADS), 0, s, (const gl::FitPart *)w.part, nb, Q,
                        (const float *)w.max_value, p->stats_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Pairwise matrix-Fisher kernel sums (csrc/so3_kernel_sum.h): the weights pass and its finalise, the pairwise pass, its finalise.
+static int so3_kernel_sum_check(const RnfSo3KernelSum *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3KernelSum))
+        return fail("RnfSo3KernelSum.struct_bytes does not match the library's %zu", sizeof(RnfSo3KernelSum));
+    if (p->J < 1 || p->J > ks::MAX_J) return fail("RnfSo3KernelSum.J=%d outside 1..%d", p->J, ks::MAX_J);
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3KernelSum.G=%d outside 1..65535", p->G);
+    if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3KernelSum.n=%lld outside 1..2^24", (long long)p->n);
+    if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3KernelSum.m=%lld outside 0..2^31-1", (long long)p->m);
+    if (ks::carve(nullptr, p->n, p->m, p->G, p->J).bytes == 0)
+        return fail("RnfSo3KernelSum: the workspace of G=%d, J=%d, n=%lld, m=%lld does not fit; tile the queries", p->G, p->J, (long long)p->n,
+                    (long long)p->m);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_kernel_sum_workspace_bytes(const RnfSo3KernelSum *p) {
+    if (so3_kernel_sum_check(p)) return 0;
+    return ks::carve(nullptr, p->n, p->m, p->G, p->J).bytes;
+}
+
+template <int J, int GB, bool LOO>
+static void so3_kernel_sum_launch(const RnfSo3KernelSum *p, const float *Q, const ks::Scales &sc, const ks::Workspace &w, hipStream_t s) {
+    const dim3 grid((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), (unsigned)ks::chunks_for(p->n), (unsigned)((p->G + GB - 1) / GB));
+    hipLaunchKernelGGL((ks::so3_kernel_sum_kernel<J, GB, LOO>), grid, dim3(ks::THREADS), 0, s, p->centres, Q, p->log_weights, (int)p->n, (int)p->m,
+                       (int)p->G, sc, w.pmax, w.psum);
+}
+
+extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
+    if (so3_kernel_sum_check(p)) return 1;
+    if (!p->kappas) return fail("RnfSo3KernelSum: null kappas");
+    for (int a = 0; a < p->J; ++a)
+        if (!(p->kappas[a] >= 0.0 && p->kappas[a] <= ks::MAX_KAPPA))
+            return fail("RnfSo3KernelSum.kappas[%d]=%g outside 0..1e6", a, p->kappas[a]);
+    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
+        return fail("RnfSo3KernelSum: centres and queries must be 16-byte aligned");
+    const bool loo = p->leave_one_out != 0;
+    if (loo && (p->m != p->n || (p->queries && p->queries != p->centres)))
+        return fail("RnfSo3KernelSum.leave_one_out: the queries must be the centres (queries NULL or == centres, m == n)");
+    if (!p->queries && p->m != p->n) return fail("RnfSo3KernelSum: null queries stand for the centres, but m=%lld and n=%lld", (long long)p->m, (long long)p->n);
+    if (p->m == 0) return 0;
+    if (!p->centres || !p->out) return fail("RnfSo3KernelSum: null centres or out");
+    const size_t need = ks::carve(nullptr, p->n, p->m, p->G, p->J).bytes;
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3KernelSum.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_kernel_sum_workspace_bytes)", p->workspace_bytes,
+                    need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3KernelSum.workspace must be 8-byte aligned");
+    const ks::Workspace w = ks::carve(p->workspace, p->n, p->m, p->G, p->J);
+    ks::Scales sc;
+    ks::Normalisers nm;
+    ks::scales_of(p->kappas, p->J, sc, nm);
+    const float *Q = p->queries ? p->queries : p->centres;
+    const int nchunk = (int)ks::chunks_for(p->n);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
+    HIP_TRY(hipGetLastError());
+#define RNF_KS_CASE(J)                                                                 \
+    case J:                                                                            \
+        if (loo) so3_kernel_sum_launch<J, 1, true>(p, Q, sc, w, s);                    \
+        else so3_kernel_sum_launch<J, 1, false>(p, Q, sc, w, s);                       \
+        break;
+    if (p->J == 1 && !loo && p->G > 1) {           // several groups share one d2
+        so3_kernel_sum_launch<1, ks::GROUPS_PER_THREAD, false>(p, Q, sc, w, s);
+    } else {
+        switch (p->J) {
+            RNF_KS_CASE(1) RNF_KS_CASE(2) RNF_KS_CASE(3) RNF_KS_CASE(4) RNF_KS_CASE(5) RNF_KS_CASE(6) RNF_KS_CASE(7) RNF_KS_CASE(8)
+        }
+    }
+#undef RNF_KS_CASE
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_sum_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->J, p->G), dim3(ks::THREADS), 0, s,
+                       (const float *)w.pmax, (const double *)w.psum, (const double *)w.log_z, p->log_weights, (int)p->n, (int)p->m, nchunk, nm,
+                       (int)loo, p->out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -366,6 +366,33 @@ def grid_fit(logp: torch.Tensor, counts: torch.Tensor) -> dict:
     return out
 
 
+def grid_diffuse(logp: torch.Tensor, grid: torch.Tensor, kappa: float) -> torch.Tensor:
+    """The prediction step of a Bayes filter on the SO(3) grid: each image's grid posterior diffused by an isotropic matrix-Fisher motion
+    kernel of concentration ``kappa`` (0..1e6).  ``logp`` [B,Q] log-densities on the rows of ``grid`` [Q,3,3] (any normalisation), both
+    on the device.  With p_b = softmax(logp_b), k the kernel of ``utils.kde.so3_kernel_log_density`` and Z_j = (1/Q) sum_i k(R_j, R_i),
+        out[b][i] = log sum_j p_bj k(R_j, R_i) / Z_j:
+    dividing by Z_j makes the operator a Markov kernel ON THE GRID, so that sum_i exp(out[b][i]) / Q = 1 whatever kappa -- a kernel
+    sharper than a cell would otherwise leak or gain mass (1.69 at level 2 with kappa = 64).  Two calls of the pairwise kernel sum:
+    log Z, then the sum with the log-weights log p_b - log Z_j (whose softmax normaliser is added back).  kappa -> infinity returns
+    log_softmax(logp) + log Q; the cost is Q^2 pairs per image, meant for levels <= 3.
+    -> float32 [B,Q], a log-density w.r.t. Haar on the grid rows, ready for grid_modes, grid_credible and the others."""
+    from .utils.kde import so3_kernel_log_density
+    if not isinstance(logp, torch.Tensor) or logp.dim() != 2:
+        raise ValueError(f"grid_diffuse: logp {tuple(getattr(logp, 'shape', ()))} (want [B,Q])")
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape) != (logp.shape[1], 3, 3):
+        raise ValueError(f"grid_diffuse: grid {tuple(getattr(grid, 'shape', ()))} for logp {tuple(logp.shape)} (want [Q,3,3])")
+    if not 1 <= logp.shape[0] <= 65535:
+        raise ValueError(f"grid_diffuse: logp holds {logp.shape[0]} images (1 to 65535)")
+    if not logp.is_cuda or not grid.is_cuda:
+        raise ValueError("grid_diffuse: logp and grid must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    kappa = float(kappa)
+    lz = so3_kernel_log_density(grid, grid, kappa)                                         # [Q]: log Z_j (k is symmetric)
+    # log(p_bj / Z_j), formed in fp64 and rounded once: these are the numbers the second call sees
+    lw = (torch.log_softmax(logp.detach().to(torch.float64), dim=1) - lz.to(torch.float64)).to(torch.float32)
+    out = so3_kernel_log_density(grid, grid, kappa, log_weights=lw)                        # weights softmax(lw): normalised to 1 ..
+    return (out.to(torch.float64) + torch.logsumexp(lw.to(torch.float64), dim=1, keepdim=True)).to(torch.float32)   # .. so their normaliser comes back
+
+
 def grid_pose_fit(flow: Flow, feature: torch.Tensor = None, samples: torch.Tensor = None, n_samples: int = 1 << 18, recursion_level: int = 2,
                   offset=None, base=None, images_per_launch: int = None) -> dict:
     """Samples against the flow's density, on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk gathering of

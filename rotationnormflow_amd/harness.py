@@ -28,8 +28,8 @@ from .configs import load_yaml_config, make_config
 from . import runtime
 from .flow.flow import Flow
 # the grid analyses live in grid_pose.py; their public functions stay reachable as harness.<name>
-from .grid_pose import (grid_beam_estimate_rotations, grid_beam_select, grid_children, grid_credible, grid_estimate_rotations,  # noqa: F401
-                        grid_fit, grid_modes, grid_pose_credible, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes)
+from .grid_pose import (grid_beam_estimate_rotations, grid_beam_select, grid_children, grid_credible, grid_diffuse,  # noqa: F401
+                        grid_estimate_rotations, grid_fit, grid_modes, grid_pose_credible, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes)
 
 
 def load_reference_checkpoint(path, map_location="cpu") -> dict:
@@ -121,6 +121,26 @@ def mean_log_likelihood(flow: Flow, rotations: torch.Tensor, base=None, batch_si
         for lo in range(0, rotations.shape[0], batch_size):
             total += flow.log_prob(rotations[lo:lo + batch_size].to(device), base=base)["sum"]
     return float(total[0] / total[1])
+
+
+def kde_baseline(train_rotations: torch.Tensor, test_rotations: torch.Tensor, kappas=None) -> dict:
+    """The non-parametric baseline to print next to ``mean_log_likelihood(flow, test)``: a kernel density estimate of the training set
+    (``utils.kde.SO3KernelDensity``, isotropic matrix-Fisher kernel, the bandwidth of ``kappas`` -- default 2^(k/2), k = 4..28 -- with the
+    best leave-one-out likelihood) scored on the test set.  Both sets [n,3,3] on the device.  Does the flow beat a KDE of its own
+    training set?
+    -> dict(kappa, loo_log_likelihood: the winner's mean leave-one-out log-likelihood on the training set, test_log_likelihood: the mean
+    log-density of the test rotations, n_train, n_test)"""
+    from .utils.kde import SO3KernelDensity
+    if not isinstance(test_rotations, torch.Tensor) or test_rotations.dim() != 3 or tuple(test_rotations.shape[-2:]) != (3, 3):
+        raise ValueError(f"kde_baseline: test_rotations {tuple(getattr(test_rotations, 'shape', ()))}, expected [n,3,3]")
+    if test_rotations.shape[0] < 1:
+        raise ValueError("kde_baseline: test_rotations is empty")
+    if not test_rotations.is_cuda:
+        raise ValueError("kde_baseline: test_rotations is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    kde = SO3KernelDensity.fit(train_rotations, kappas=kappas)
+    test = kde.log_prob(test_rotations).to(torch.float64).mean()
+    return dict(kappa=float(kde.kappa), loo_log_likelihood=float(kde.loo_log_likelihood.max()), test_log_likelihood=float(test),
+                n_train=int(kde.rotations.shape[0]), n_test=int(test_rotations.shape[0]))
 
 
 def expand_optimizer_state(flow: Flow, state: dict) -> dict:
