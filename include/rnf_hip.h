@@ -613,6 +613,52 @@ int rnf_so3_kernel_sum(const RnfSo3KernelSum *sum);
  * range or the size does not fit. */
 size_t rnf_so3_kernel_sum_workspace_bytes(const RnfSo3KernelSum *sum);
 
+/* Responsibility-weighted first moments of the same kernel sum (csrc/so3_kernel_moments.h): the score of the kernel density estimate,
+ * its mean-shift step and its derivative with respect to the bandwidth.  One concentration kappa, no leave-one-out.  With
+ * r_ij = w_gj k(C_j, Q_i) / sum_l w_gl k(C_l, Q_i), per group g and query i:
+ *   log_density = log sum_j w_gj k(C_j, Q_i)        bit-identical to rnf_so3_kernel_sum's output for the same inputs with J = 1
+ *   mean        = M_i = sum_j r_ij C_j              so that d log p / dQ_i = kappa (M_i - Q_i)
+ *   msd         = D_i = sum_j r_ij |Q_i - C_j|_F^2  so that d log p / dkappa = -D_i / 2 - l'(kappa)
+ *   rotation    = polar(M_i), the rotation that maximises tr(M_i^T R): the mean-shift step.  NaN where det M_i <= 0 (a convex
+ *                 combination of rotations need not have a mean direction) or where M_i is too ill-conditioned to project
+ *   step        = |rotation - Q_i|_F, NaN where rotation is
+ * Any output pointer may be NULL, except that step requires rotation.  group_queries != 0: every group has its own m queries
+ * (queries float[G][m][9]); otherwise the G groups share queries float[m][9].
+ * The edge cases are those of rnf_so3_kernel_sum, for every output of the (group, query): a centre with log-weight -inf is left out
+ * whatever its entries; another non-finite centre or a NaN log-weight makes its group NaN; a non-finite query is NaN; a group with no
+ * mass is NaN; m = 0 is a no-op; kappa = 0 gives mean = sum_j w_gj C_j for every query.
+ * Deterministic in the same way: chunks of 4096 centres, one partial (fp32 max, 11 fp64 sums: e, e d^2, e C[0..8]; fp32 over at most 64
+ * centres) per (group, chunk, query), combined in chunk order in fp64, divided by the first sum and rounded once; no floating-point
+ * atomics.  A query's outputs are bit-identical from run to run and whatever m, G, the query's position and the group's position
+ * are, and whether its queries are shared or given per group.  Five launches.  Stream-ordered, no host synchronisation, capturable in a
+ * HIP graph as a linear chain. */
+typedef struct RnfSo3KernelMoments {
+    size_t struct_bytes;        /* sizeof(RnfSo3KernelMoments); any other value is refused (header and library differ) */
+    const float *centres;       /* dev float[n][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9], or float[G][m][9] with group_queries; 16-byte aligned */
+    const float *log_weights;   /* dev float[G][n], or NULL (uniform weights) */
+    int64_t n;                  /* centres, 1..2^24 */
+    int64_t m;                  /* queries (per group), 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    int32_t group_queries;      /* 0: the groups share the queries; != 0: one set per group */
+    double kappa;               /* finite, 0..1e6 */
+    float *log_density;         /* dev float[G][m], or NULL */
+    float *mean;                /* dev float[G][m][9], or NULL */
+    float *msd;                 /* dev float[G][m], or NULL */
+    float *rotation;            /* dev float[G][m][9], or NULL */
+    float *step;                /* dev float[G][m], or NULL; requires rotation */
+    double *dlog_normaliser;    /* HOST double, or NULL: receives l'(kappa) (fp64, l'(0) = -3), also when m = 0 */
+    /* dev scratch, 8-byte aligned, of at least rnf_so3_kernel_moments_workspace_bytes(this struct) bytes =
+     * 92 G ceil(n / 4096) m + 16 G ceil(n / 4096) + 8 G + 4 ceil(n / 4096) rounded up to 16 */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3KernelMoments;
+int rnf_so3_kernel_moments(const RnfSo3KernelMoments *moments);
+/* The workspace rnf_so3_kernel_moments requires for the same struct (the pointers are not read); 0 when struct_bytes, G, n or m are out
+ * of range or the size does not fit. */
+size_t rnf_so3_kernel_moments_workspace_bytes(const RnfSo3KernelMoments *moments);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

@@ -79,6 +79,14 @@ class So3KernelSum(_Pass):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class So3KernelMoments(_Pass):
+    """RnfSo3KernelMoments (include/rnf_hip.h): responsibility-weighted first moments of the same kernel sum."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("queries", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64),
+                ("m", C.c_int64), ("G", C.c_int32), ("group_queries", C.c_int32), ("kappa", C.c_double), ("log_density", C.c_void_p),
+                ("mean", C.c_void_p), ("msd", C.c_void_p), ("rotation", C.c_void_p), ("step", C.c_void_p), ("dlog_normaliser", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 GRID_FIT_STATS = ("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
@@ -175,6 +183,8 @@ _SIGNATURES = {
     "rnf_grid_fit_workspace_bytes": (C.c_size_t, [C.POINTER(GridFit)]),
     "rnf_so3_kernel_sum": (C.c_int, [C.POINTER(So3KernelSum)]),
     "rnf_so3_kernel_sum_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelSum)]),
+    "rnf_so3_kernel_moments": (C.c_int, [C.POINTER(So3KernelMoments)]),
+    "rnf_so3_kernel_moments_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelMoments)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -32,6 +32,7 @@
 #include "grid_credible.h"
 #include "grid_locate.h"
 #include "so3_kernel_sum.h"
+#include "so3_kernel_moments.h"
 
 using namespace rnf;
 
@@ -1732,6 +1733,65 @@ extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
     hipLaunchKernelGGL(ks::so3_kernel_sum_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->J, p->G), dim3(ks::THREADS), 0, s,
                        (const float *)w.pmax, (const double *)w.psum, (const double *)w.log_z, p->log_weights, (int)p->n, (int)p->m, nchunk, nm,
                        (int)loo, p->out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Moments of the same kernel sum (csrc/so3_kernel_moments.h): the weights pass and its finalise, the chunk flags, the pairwise pass, its
+// finalise.
+static int so3_kernel_moments_check(const RnfSo3KernelMoments *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3KernelMoments))
+        return fail("RnfSo3KernelMoments.struct_bytes does not match the library's %zu", sizeof(RnfSo3KernelMoments));
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3KernelMoments.G=%d outside 1..65535", p->G);
+    if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3KernelMoments.n=%lld outside 1..2^24", (long long)p->n);
+    if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3KernelMoments.m=%lld outside 0..2^31-1", (long long)p->m);
+    if (km::carve(nullptr, p->n, p->m, p->G).bytes == 0)
+        return fail("RnfSo3KernelMoments: the workspace of G=%d, n=%lld, m=%lld does not fit; tile the queries", p->G, (long long)p->n,
+                    (long long)p->m);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_kernel_moments_workspace_bytes(const RnfSo3KernelMoments *p) {
+    if (so3_kernel_moments_check(p)) return 0;
+    return km::carve(nullptr, p->n, p->m, p->G).bytes;
+}
+
+extern "C" int rnf_so3_kernel_moments(const RnfSo3KernelMoments *p) {
+    if (so3_kernel_moments_check(p)) return 1;
+    if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("RnfSo3KernelMoments.kappa=%g outside 0..1e6", p->kappa);
+    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
+        return fail("RnfSo3KernelMoments: centres and queries must be 16-byte aligned");
+    if (p->step && !p->rotation) return fail("RnfSo3KernelMoments.step requires rotation");
+    if (p->dlog_normaliser) *p->dlog_normaliser = km::dlog_normaliser(p->kappa);
+    if (p->m == 0) return 0;
+    if (!p->centres || !p->queries) return fail("RnfSo3KernelMoments: null centres or queries");
+    const size_t need = km::carve(nullptr, p->n, p->m, p->G).bytes;
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3KernelMoments.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_kernel_moments_workspace_bytes)",
+                    p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3KernelMoments.workspace must be 8-byte aligned");
+    const km::Workspace w = km::carve(p->workspace, p->n, p->m, p->G);
+    ks::Scales sc;
+    ks::Normalisers nm;
+    ks::scales_of(&p->kappa, 1, sc, nm);
+    const int nchunk = (int)ks::chunks_for(p->n);
+    const unsigned blocks = (unsigned)((p->m + ks::THREADS - 1) / ks::THREADS);
+    const long long q_group = p->group_queries ? 9 * (long long)p->m : 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(km::so3_kernel_moments_flags_kernel, dim3(nchunk), dim3(ks::THREADS), 0, s, p->centres, (int)p->n, w.flags);
+    HIP_TRY(hipGetLastError());
+    const int block = km::block_for(p->m, nchunk, p->G);
+    hipLaunchKernelGGL(km::so3_kernel_moments_kernel, dim3((unsigned)((p->m + block - 1) / block), nchunk, p->G), dim3(block), 0, s, p->centres,
+                       p->queries, p->log_weights,
+                       (int)p->n, (int)p->m, q_group, sc, (const int *)w.flags, w.pmax, w.psum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(km::so3_kernel_moments_final_kernel, dim3(blocks, p->G), dim3(ks::THREADS), 0, s, (const float *)w.pmax,
+                       (const double *)w.psum, (const double *)w.log_z, p->queries, q_group, (int)p->m, nchunk, nm.l[0], p->log_density, p->mean,
+                       p->msd, p->rotation, p->step);
     HIP_TRY(hipGetLastError());
     return 0;
 }

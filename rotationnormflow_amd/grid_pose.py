@@ -222,7 +222,66 @@ def grid_pose_modes(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, se
     return out
 
 
-GRID_CREDIBLE_MAX_ROWS = 1 << 26                   # rnf_grid_credible's fixed point (include/rnf_hip.h): level 6 fits
+def grid_modes_refine(logp: torch.Tensor, grid: torch.Tensor, est: torch.Tensor, kappa: float = None, tol: float = 1e-5, max_steps: int = 200,
+                      check_every: int = 8):
+    """Mean shift of grid modes off the grid: image b's modes ``est`` [g,k,3,3] (grid rows, e.g. ``grid[index]`` of ``grid_modes``) climb
+    the kernel-smoothed grid posterior sum_i softmax(logp_b)_i k_kappa(R_i, .) (``utils.kde.so3_kernel_moments`` with the grid as
+    centres, ``logp`` [g,Q] as log-weights and one set of queries per image).  ``kappa`` defaults to 0.5 / s^2 with s = (8 pi^2 / Q)^(1/3)
+    rad, the grid spacing.  A NaN mode stays NaN.  -> (refined [g,k,3,3], converged [g,k] bool)"""
+    from .utils.kde import _kappas, _mean_shift
+    who = "grid_modes_refine"
+    if not (isinstance(logp, torch.Tensor) and logp.dim() == 2 and isinstance(grid, torch.Tensor) and tuple(grid.shape) == (logp.shape[1], 3, 3)):
+        raise ValueError(f"{who}: logp {tuple(getattr(logp, 'shape', ()))} and grid {tuple(getattr(grid, 'shape', ()))}, expected [g,Q] and [Q,3,3]")
+    if not (isinstance(est, torch.Tensor) and est.dim() == 4 and est.shape[0] == logp.shape[0] and tuple(est.shape[2:]) == (3, 3)):
+        raise ValueError(f"{who}: est {tuple(getattr(est, 'shape', ()))}, expected [{logp.shape[0]},k,3,3]")
+    if not (logp.is_cuda and grid.is_cuda and est.is_cuda):
+        raise ValueError(f"{who}: logp, grid and est must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    Q = grid.shape[0]
+    k = 0.5 / (8.0 * np.pi ** 2 / Q) ** (2.0 / 3.0) if kappa is None else float(kappa)
+    (k,), _ = _kappas(min(k, 1e6) if kappa is None else k, who)
+    refined, converged, _ = _mean_shift(grid, est, k, logp, True, float(tol), max_steps, check_every)
+    return refined, converged
+
+
+def grid_pose_modes_refined(flow: Flow, feature: torch.Tensor = None, top_k: int = 4, separation_deg: float = 15.0, kappa: float = None,
+                            number_queries: int = None, recursion_level: int = None, offset=None, base=None, gt_rotation=None,
+                            images_per_launch: int = None, tol: float = 1e-5, max_steps: int = 200, check_every: int = 8) -> dict:
+    """``grid_pose_modes`` (same inputs, same launches), then each mode is taken off the grid by mean shift on the kernel-smoothed grid
+    posterior (``grid_modes_refine``; ``kappa`` defaults to 0.5 / s^2, s the grid spacing in radians).
+    -> the dict of ``grid_pose_modes`` plus ``refined`` [B,k,3,3] and ``converged`` [B,k]; modes that do not exist stay NaN.
+    What it is and is not: ``refined`` is the mode of the SMOOTHED posterior, and it helps only where the density is wider than the grid
+    spacing.  An fp64 run at level 3 on a 0.6 MF(20 R0) + 0.4 MF(20 R0 Rz(180)) posterior gave a mean error of 3.78 degrees for the
+    arg-max and 0.02 to 0.05 degrees for kappa = 10..40; the same run with concentration 200 gave no gain at any kappa, and level 1
+    gave none."""
+    if not 1 <= int(top_k) <= 16:
+        raise ValueError(f"grid_pose_modes_refined: top_k={top_k} outside 1..16")
+    if not 0.0 < float(separation_deg) <= 180.0:
+        raise ValueError(f"grid_pose_modes_refined: separation_deg={separation_deg} outside (0, 180]")
+    k, sep = int(top_k), float(np.deg2rad(np.float64(separation_deg)))
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, "grid_pose_modes_refined")
+    gt = None
+    if gt_rotation is not None:
+        gt = gt_rotation.reshape(gf.B, -1, 3, 3).to(device=gf.dev, dtype=torch.float32)
+        if gt.shape[1] > 128:
+            raise ValueError(f"grid_pose_modes_refined: {gt.shape[1]} ground truths per image (at most 128)")
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        outs, refs = [], []
+        for b0, b1, lp in gf.images(grid, images_per_launch, "grid_pose_modes_refined"):
+            res = grid_modes(lp, grid, k, sep, gt[b0:b1] if gt is not None else None)
+            start = grid[res[0].clamp(min=0)]
+            start[res[0] < 0] = float("nan")
+            outs.append(res)
+            refs.append((start,) + grid_modes_refine(lp, grid, start, kappa, tol, max_steps, check_every))
+        index, log_prob, mass, log_norm, spread = (torch.cat(t) if t[0] is not None else None for t in zip(*outs))
+        est, refined, converged = (torch.cat(t) for t in zip(*refs))
+    out = dict(est=est, log_prob=log_prob, index=index, mass=mass, log_norm=log_norm, offset=offset, refined=refined, converged=converged)
+    if gt is not None:
+        out["spread_deg"] = torch.rad2deg(spread)
+    return out
+
+
+GRID_CREDIBLE_MAX_ROWS = 1 << 26                  # rnf_grid_credible's fixed point (include/rnf_hip.h): level 6 fits
 GRID_CREDIBLE_MAX_LEVELS = 8
 GRID_CREDIBLE_MAX_QUERIES = 16
 GRID_GT_ROW = 32                                    # the shortest shared row on the fast shared-row kernels (csrc/flow_plan.h)

@@ -29,7 +29,8 @@ from . import runtime
 from .flow.flow import Flow
 # the grid analyses live in grid_pose.py; their public functions stay reachable as harness.<name>
 from .grid_pose import (grid_beam_estimate_rotations, grid_beam_select, grid_children, grid_credible, grid_diffuse,  # noqa: F401
-                        grid_estimate_rotations, grid_fit, grid_modes, grid_pose_credible, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes)
+                        grid_estimate_rotations, grid_fit, grid_modes, grid_modes_refine, grid_pose_credible, grid_pose_fisher, grid_pose_fit, grid_pose_mixture,
+                        grid_pose_modes, grid_pose_modes_refined)
 
 
 def load_reference_checkpoint(path, map_location="cpu") -> dict:
@@ -141,6 +142,15 @@ def kde_baseline(train_rotations: torch.Tensor, test_rotations: torch.Tensor, ka
     test = kde.log_prob(test_rotations).to(torch.float64).mean()
     return dict(kappa=float(kde.kappa), loo_log_likelihood=float(kde.loo_log_likelihood.max()), test_log_likelihood=float(test),
                 n_train=int(kde.rotations.shape[0]), n_test=int(test_rotations.shape[0]))
+
+
+def kde_modes(rotations: torch.Tensor, kappa: float, top_k: int = 4, separation_deg: float = 15.0, log_weights: torch.Tensor = None) -> dict:
+    """The ``top_k`` modes of a set of rotations [n,3,3] (samples of a pose distribution, weights softmax(``log_weights``) or equal): the
+    kernel estimate with concentration ``kappa`` (no fit), then ``SO3KernelDensity.modes`` -- mean shift from up to 1024 of the samples
+    and a merge at ``separation_deg``.  The robust form of the reference's ``log_inv`` evaluation, which takes the best of the drawn
+    samples as the pose.  -> dict(est [k,3,3], log_prob [k], mass [k], converged_fraction)"""
+    from .utils.kde import SO3KernelDensity
+    return SO3KernelDensity(rotations, kappa, log_weights).modes(top_k=top_k, separation_deg=separation_deg)
 
 
 def expand_optimizer_state(flow: Flow, state: dict) -> dict:

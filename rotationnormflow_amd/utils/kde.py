@@ -2,8 +2,12 @@
 csrc/so3_kernel_sum.h).  Densities are w.r.t. the Haar probability measure, like every density in the package.
 
 ``so3_kernel_log_density`` is the primitive: log sum_j w_j k_kappa(C_j, Q_i) for sets of centres and queries, several bandwidths and
-several rows of log-weights at once, with leave-one-out.  ``SO3KernelDensity`` is the estimate with its bandwidth chosen by the
-leave-one-out likelihood.  ``grid_pose.grid_diffuse`` builds the prediction step of a Bayes filter on the SO(3) grid on the primitive."""
+several rows of log-weights at once, with leave-one-out.  ``so3_kernel_moments`` (``rnf_so3_kernel_moments``, csrc/so3_kernel_moments.h)
+adds the responsibility-weighted first moments of the same sum: the score, the mean-shift step and the derivative with respect to the
+bandwidth.  ``SO3KernelDensity`` is the estimate with its bandwidth chosen by the leave-one-out likelihood; its ``log_prob`` is
+differentiable with respect to the rotations, and it has ``score``, ``mean_shift``, ``modes`` and ``sample``.  ``grid_pose.grid_diffuse``
+builds the prediction step of a Bayes filter on the SO(3) grid on the primitive, ``grid_pose.grid_modes_refine`` takes grid modes off the
+grid by mean shift."""
 from __future__ import annotations
 
 import ctypes as C
@@ -125,13 +129,131 @@ def so3_kernel_log_density(centres, queries=None, kappa=None, log_weights=None, 
     return out if grouped else out[0]
 
 
+MOMENT_BYTES = 92                                   # workspace bytes per (group, chunk, query) of rnf_so3_kernel_moments: 11 fp64 sums, one fp32 max
+
+
+def so3_kernel_moments(centres, queries, kappa, log_weights=None, project: bool = False, group_queries: bool = False,
+                       workspace_cap: int = None) -> dict:
+    """The responsibility-weighted first moments of the kernel sum on the device (``rnf_so3_kernel_moments``): with
+    r_ij = w_j k(C_j, Q_i) / sum_l w_l k(C_l, Q_i) for ONE ``kappa`` in 0..1e6,
+    ``log_density`` [m] (the bits of ``so3_kernel_log_density``), ``mean`` [m,3,3] = M_i = sum_j r_ij C_j, ``msd`` [m] = D_i =
+    sum_j r_ij |Q_i - C_j|_F^2, ``dlogp_dkappa`` [m] float64 = -D_i / 2 - l'(kappa), and with ``project`` ``rotation`` [m,3,3] =
+    polar(M_i) -- the mean-shift step; NaN where det M_i <= 0, where there is no mean direction -- and ``step`` [m] = |rotation - Q_i|_F.
+    d log p(Q_i) / dQ_i = kappa (M_i - Q_i).  ``centres`` [n,3,3]; ``queries`` [m,3,3], shared by the groups, or with ``group_queries``
+    [G,m,3,3], one set per group; ``log_weights`` None, [n] or [G,n] as ``so3_kernel_log_density``: a 2-D ``log_weights`` (or
+    ``group_queries``) gives every output a leading G.  Edge cases as ``so3_kernel_log_density``, for every output of the (group, query).
+    A query's outputs are bit-identical however the call is tiled, so the tiling of queries and groups that keeps the workspace (92
+    ceil(n/4096) bytes per group and query) under ``workspace_cap`` (64 MiB) is invisible.  Stream-ordered, no host synchronisation, no
+    gradient (``SO3KernelDensity.log_prob`` carries one)."""
+    who = "so3_kernel_moments"
+    ks, scalar = _kappas(kappa, who)
+    if not scalar:
+        raise ValueError(f"{who}: kappa is one concentration, not a sequence")
+    k = ks[0]
+    Cn = _rotations(centres, "centres", who)
+    n, dev = Cn.shape[0], Cn.device
+    if not 1 <= n <= MAX_CENTRES:
+        raise ValueError(f"{who}: centres holds {n} rotations (1 to 2^24)")
+    group_queries = bool(group_queries)
+    if group_queries:
+        if not isinstance(queries, torch.Tensor) or queries.dim() != 4 or tuple(queries.shape[-2:]) != (3, 3):
+            raise ValueError(f"{who}: queries {tuple(getattr(queries, 'shape', ()))}, expected [G,m,3,3] with group_queries")
+        if not queries.is_cuda:
+            raise ValueError(f"{who}: queries is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        Qr = queries.detach().to(torch.float32).contiguous()
+    else:
+        Qr = _rotations(queries, "queries", who)
+    if Qr.device != dev:
+        raise ValueError(f"{who}: queries on {Qr.device}, centres on {dev}")
+    m = Qr.shape[-3]
+    if m >= 1 << 31:
+        raise ValueError(f"{who}: queries holds {m} rotations (below 2^31)")
+    lw, grouped = None, group_queries
+    if log_weights is not None:
+        if not isinstance(log_weights, torch.Tensor) or log_weights.dim() not in (1, 2) or log_weights.shape[-1] != n:
+            raise ValueError(f"{who}: log_weights {tuple(getattr(log_weights, 'shape', ()))} for {n} centres, expected [n] or [G,n]")
+        if not log_weights.is_cuda:
+            raise ValueError(f"{who}: log_weights is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        grouped = grouped or log_weights.dim() == 2
+        lw = log_weights.detach().to(device=dev, dtype=torch.float32).reshape(-1, n).contiguous()
+    G = Qr.shape[0] if group_queries else (lw.shape[0] if lw is not None else 1)
+    if lw is not None and lw.shape[0] != G:
+        raise ValueError(f"{who}: log_weights holds {lw.shape[0]} groups, queries {G}")
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError(f"{who}: {G} groups (1 to 65535)")
+    cap = WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    names = ("log_density", "mean", "msd") + (("rotation", "step") if project else ())
+    out = {name: torch.empty((G, m, 3, 3) if name in ("mean", "rotation") else (G, m), dtype=torch.float32, device=dev) for name in names}
+    dl = C.c_double(0.0)
+    if m == 0:
+        _lib.call("so3_kernel_moments", _lib.So3KernelMoments(n=n, m=0, G=G, kappa=k, dlog_normaliser=C.addressof(dl)), dev)
+    else:
+        per_query = MOMENT_BYTES * ((n + CHUNK - 1) // CHUNK)             # bytes per query and group
+        g_tile = max(1, min(G, cap // (per_query * min(m, 256))))
+        m_tile = max(1, min(m, cap // (per_query * g_tile)))
+        m_tile = m_tile if m_tile < 4 or m_tile == m else m_tile // 4 * 4          # rows of 36 bytes: every fourth is 16-byte aligned
+        for g0 in range(0, G, g_tile):
+            g1 = min(G, g0 + g_tile)
+            for i0 in range(0, m, m_tile):
+                i1 = min(m, i0 + m_tile)
+                tile = _aligned(Qr[g0:g1, i0:i1].contiguous() if group_queries else Qr[i0:i1])
+                part = {name: v[g0:g1, i0:i1] for name, v in out.items()}
+                dst = {name: v if v.is_contiguous() else torch.empty(v.shape, dtype=torch.float32, device=dev) for name, v in part.items()}
+                args = _lib.So3KernelMoments(centres=Cn.data_ptr(), queries=tile.data_ptr(),
+                                             log_weights=lw[g0:g1].data_ptr() if lw is not None else None, n=n, m=i1 - i0, G=g1 - g0,
+                                             group_queries=int(group_queries), kappa=k, dlog_normaliser=C.addressof(dl),
+                                             **{name: v.data_ptr() for name, v in dst.items()})
+                _lib.call("so3_kernel_moments", args, dev)
+                for name, v in part.items():
+                    if dst[name] is not v:
+                        v.copy_(dst[name])
+    out["dlogp_dkappa"] = -0.5 * out["msd"].to(torch.float64) - dl.value
+    return out if grouped else {name: v[0] for name, v in out.items()}
+
+
+class _KernelLogProb(torch.autograd.Function):
+    """log p(R) of an ``SO3KernelDensity`` with its gradient kappa (M - R) with respect to R, both from ONE moments call"""
+
+    @staticmethod
+    def forward(ctx, R, est):
+        kappa = float(est.kappa)
+        flat = R.detach().reshape(-1, 3, 3)
+        out = so3_kernel_moments(est.rotations, flat, kappa, est.log_weights)
+        ctx.save_for_backward(kappa * (out["mean"].to(torch.float64) - flat.to(device=out["mean"].device, dtype=torch.float64)))
+        return out["log_density"].reshape(R.shape[:-2])
+
+    @staticmethod
+    def backward(ctx, grad):
+        (dR,) = ctx.saved_tensors
+        g = grad.reshape(-1, 1, 1).to(torch.float64) * dR
+        return g.reshape(grad.shape + (3, 3)).to(torch.float32), None
+
+
+def _mean_shift(centres, starts, kappa, log_weights, group_queries, tol, max_steps, check_every, workspace_cap=None):
+    """Mean shift of ``starts`` ([s,3,3], or [G,s,3,3] with ``group_queries``) on the kernel estimate -> (rotations, converged,
+    steps_taken) of the starts' shape.  One host read-back per ``check_every`` steps."""
+    cur = starts.detach().to(torch.float32).clone()
+    frozen = torch.zeros(cur.shape[:-2], dtype=torch.bool, device=cur.device)
+    taken = torch.zeros(cur.shape[:-2], dtype=torch.int32, device=cur.device)
+    for it in range(int(max_steps)):
+        out = so3_kernel_moments(centres, cur, kappa, log_weights, project=True, group_queries=group_queries, workspace_cap=workspace_cap)
+        step = out["step"].reshape(frozen.shape)
+        frozen = frozen | (step < tol)                                   # frozen now or before: written back unchanged from here on
+        cur = torch.where(frozen[..., None, None], cur, out["rotation"].reshape(cur.shape))
+        taken = taken + (~frozen).to(torch.int32)
+        if (it + 1) % int(check_every) == 0 and bool((frozen | torch.isnan(step)).all()):
+            break
+    return cur, frozen, taken
+
+
 class SO3KernelDensity(torch.nn.Module):
     """A kernel density estimate on SO(3): p(R) = sum_j w_j MF(kappa R_j)(R) with buffers ``rotations`` [n,3,3], ``log_weights`` [n]
     (log w up to a constant; zeros for uniform weights) and ``kappa`` (a 0-d float64 tensor).  ``fit`` chooses kappa from the data.
     The three buffers are the whole state: ``log_prob`` always weights by ``log_weights`` (zeros give the bits of the unweighted sum), so
     a ``load_state_dict`` changes nothing but the numbers.  ``kappa`` is created on the CPU because the library takes its bandwidths
     from the host; after ``.to(device)`` it follows the module and every ``log_prob`` reads it back (one host synchronisation).
-    There is no gradient (``log_prob`` is not differentiable) and no ``sample()``."""
+    ``log_prob`` is differentiable with respect to its rotations (not to the buffers); ``score``, ``mean_shift``, ``modes`` and ``sample``
+    rest on the same moments pass (``so3_kernel_moments``)."""
 
     def __init__(self, rotations, kappa, log_weights=None):
         super().__init__()
@@ -175,12 +297,118 @@ class SO3KernelDensity(torch.nn.Module):
         self.loo_log_likelihood = score
         return self
 
-    def log_prob(self, R):
-        """log p(R) w.r.t. the Haar probability measure for R [...,3,3] on the device -> float32 [...]; no gradient."""
+    def _queries(self, R, who: str):
         if not isinstance(R, torch.Tensor) or R.dim() < 2 or tuple(R.shape[-2:]) != (3, 3):
-            raise ValueError(f"SO3KernelDensity.log_prob: R {tuple(getattr(R, 'shape', ()))}, expected [...,3,3]")
-        lead = R.shape[:-2]
+            raise ValueError(f"SO3KernelDensity.{who}: R {tuple(getattr(R, 'shape', ()))}, expected [...,3,3]")
         if not self.rotations.is_cuda:
-            raise ValueError("SO3KernelDensity.log_prob: rotations is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+            raise ValueError(f"SO3KernelDensity.{who}: rotations is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        return R.shape[:-2]
+
+    def log_prob(self, R):
+        """log p(R) w.r.t. the Haar probability measure for R [...,3,3] on the device -> float32 [...].  Where ``R`` requires a gradient
+        the result carries d log p / dR = kappa (M - R), the Euclidean gradient with respect to the nine entries (M: the
+        responsibility-weighted mean of the estimate's rotations, ``so3_kernel_moments``), from the same pass as the value; the value has
+        the same bits either way.  No gradient with respect to the buffers."""
+        lead = self._queries(R, "log_prob")
+        if R.requires_grad and torch.is_grad_enabled():
+            if not R.is_cuda:
+                raise ValueError("SO3KernelDensity.log_prob: R is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+            return _KernelLogProb.apply(R, self)
         out = so3_kernel_log_density(self.rotations, R.reshape(-1, 3, 3), float(self.kappa), self.log_weights)
         return out.reshape(lead)
+
+    def score(self, R, frame: str = "body"):
+        """The gradient of log p at R [...,3,3].  ``frame="ambient"``: kappa (M - R) [...,3,3], the Euclidean gradient of ``log_prob``.
+        ``frame="body"``: kappa vee(R^T M - M^T R) [...,3], the derivative along R exp(hat(v)) at v = 0 (vee(A) = (A21, A02, A10)); R^T R
+        drops out of it.  float32, detached."""
+        if frame not in ("body", "ambient"):
+            raise ValueError(f"SO3KernelDensity.score: frame={frame!r}, expected 'body' or 'ambient'")
+        lead = self._queries(R, "score")
+        flat = R.detach().reshape(-1, 3, 3)
+        kappa = float(self.kappa)
+        M = so3_kernel_moments(self.rotations, flat, kappa, self.log_weights)["mean"].to(torch.float64)
+        Rd = flat.to(device=M.device, dtype=torch.float64)
+        D = kappa * (M - Rd)
+        if frame == "ambient":
+            return D.to(torch.float32).reshape(lead + (3, 3))
+        A = Rd.transpose(1, 2) @ D
+        A = A - A.transpose(1, 2)
+        return torch.stack([A[:, 2, 1], A[:, 0, 2], A[:, 1, 0]], dim=1).to(torch.float32).reshape(lead + (3,))
+
+    def mean_shift(self, starts, kappa: float = None, tol: float = 1e-5, max_steps: int = 200, check_every: int = 8):
+        """Mean shift of ``starts`` [s,3,3] to modes of the estimate: R <- polar(M(R)), the rotation closest to the responsibility-weighted
+        mean, a host loop of ``so3_kernel_moments`` calls with one host read-back per ``check_every`` steps.  ``kappa``: the kernel of the
+        search (default: the estimate's; see ``modes``).  A start whose step |polar(M) - R|_F falls below ``tol`` is frozen -- written back
+        unchanged from then on -- so its endpoint does not depend on how long the others take, and is bit-identical whatever other starts
+        share the call.  A start that meets det M <= 0 ends as NaN.
+        -> (rotations [s,3,3], log_density [s] at the endpoints under ``kappa``, converged [s] bool, steps_taken [s] int32)"""
+        who = "SO3KernelDensity.mean_shift"
+        S = _rotations(starts, "starts", who)
+        if not self.rotations.is_cuda:
+            raise ValueError(f"{who}: rotations is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        if not (tol > 0 and int(max_steps) >= 1 and int(check_every) >= 1):
+            raise ValueError(f"{who}: tol={tol}, max_steps={max_steps}, check_every={check_every}")
+        k = float(self.kappa) if kappa is None else _kappas(float(kappa), who)[0][0]
+        rot, converged, taken = _mean_shift(self.rotations, S, k, self.log_weights, False, float(tol), max_steps, check_every)
+        return rot, so3_kernel_log_density(self.rotations, rot, k, self.log_weights), converged, taken
+
+    def modes(self, top_k: int = 4, separation_deg: float = 15.0, starts=None, kappa: float = None, tol: float = 1e-5, max_steps: int = 200,
+              check_every: int = 8) -> dict:
+        """The ``top_k`` modes of the estimate at no fixed resolution: mean shift (``mean_shift``) from ``starts``, then the endpoints are
+        merged as ``grid_pose.grid_modes`` merges grid rows -- mode 0 the endpoint of the largest log-density, mode j the largest among
+        those at least ``separation_deg`` from the earlier modes.  ``starts``: None (up to 1024 of the estimate's own rotations at a fixed
+        stride), an int (that many) or a tensor [s,3,3].  Each mode's ``mass`` is the weight share of the starts whose endpoint lies
+        within ``separation_deg`` of it and of no earlier mode (the estimate's weights for its own rotations, equal weights for given
+        starts; endpoints that are not finite count for no mode).
+        ``kappa`` is the kernel of the search, by default the estimate's.  Mode seeking wants a smoother kernel than density estimation:
+        on 4096 draws of 1/2 MF(20 I) + 1/2 MF(20 Rz(180)) the likelihood-optimal bandwidth that ``fit`` picks (kappa = 128) yields 4 to
+        10 spurious modes, kappa = 32 exactly two.
+        -> dict(est [k,3,3], log_prob [k], mass [k], converged_fraction); modes that do not exist are NaN with mass 0."""
+        from ..grid_pose import grid_modes
+        who = "SO3KernelDensity.modes"
+        if not 1 <= int(top_k) <= 16:
+            raise ValueError(f"{who}: top_k={top_k} outside 1..16")
+        if not 0.0 < float(separation_deg) <= 180.0:
+            raise ValueError(f"{who}: separation_deg={separation_deg} outside (0, 180]")
+        n = self.rotations.shape[0]
+        if starts is None or isinstance(starts, int):
+            want = 1024 if starts is None else int(starts)
+            if want < 1:
+                raise ValueError(f"{who}: starts={starts}")
+            stride = max(1, -(-n // want))
+            pick = torch.arange(0, n, stride, device=self.rotations.device)
+            S = self.rotations[pick]
+            w = torch.softmax(self.log_weights[pick].to(torch.float64), dim=0)
+        else:
+            S = _rotations(starts, "starts", who)
+            w = torch.full((S.shape[0],), 1.0 / max(1, S.shape[0]), dtype=torch.float64, device=S.device)
+        sep = math.radians(float(separation_deg))
+        rot, lp, converged, _ = self.mean_shift(S, kappa, tol, max_steps, check_every)
+        ok = torch.isfinite(rot).all(dim=2).all(dim=1) & torch.isfinite(lp)
+        clean = torch.where(ok[:, None, None], rot, torch.eye(3, device=rot.device).expand_as(rot)).contiguous()
+        index, log_prob, _, _, _ = grid_modes(torch.where(ok, lp, torch.full_like(lp, -math.inf))[None], clean, int(top_k), sep)
+        index, log_prob = index[0], log_prob[0]
+        est = clean[index.clamp(min=0)].clone()
+        est[index < 0] = float("nan")
+        # within sep: tr(E_k^T R_s) > 1 + 2 cos(sep), the rule of rnf_grid_modes; a start counts for the first mode it is within sep of
+        tr = torch.einsum("kij,sij->ks", torch.nan_to_num(est).to(torch.float64), clean.to(torch.float64))
+        near = (tr > 1.0 + 2.0 * math.cos(sep)) & (index >= 0)[:, None] & ok[None, :]
+        first = near & (torch.cumsum(near.to(torch.int32), dim=0) == 1)
+        mass = (first.to(torch.float64) * w[None, :]).sum(dim=1).to(torch.float32)
+        log_prob = torch.where(index >= 0, log_prob, torch.full_like(log_prob, float("nan")))
+        return dict(est=est, log_prob=log_prob, mass=mass, converged_fraction=float(converged.to(torch.float64).mean()))
+
+    def sample(self, n: int):
+        """``n`` rotations [n,3,3] from the estimate: a centre j drawn with probability softmax(log_weights)_j (``torch.multinomial``),
+        times a draw of MF(kappa I) from the device sampler (``MatrixFisherN``), whose Philox key comes from torch's default generator:
+        ``torch.manual_seed`` reproduces the samples."""
+        from .fisher import MatrixFisherN
+        if not self.rotations.is_cuda:
+            raise ValueError("SO3KernelDensity.sample: rotations is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"SO3KernelDensity.sample: n={n}")
+        dev = self.rotations.device
+        pick = torch.multinomial(torch.softmax(self.log_weights.to(torch.float64), dim=0).to(torch.float32), n, replacement=True)
+        noise = MatrixFisherN(float(self.kappa) * torch.eye(3, dtype=torch.float32, device=dev)[None])._sample(n)[0]
+        return self.rotations[pick] @ noise
