@@ -659,6 +659,52 @@ int rnf_so3_kernel_moments(const RnfSo3KernelMoments *moments);
  * of range or the size does not fit. */
 size_t rnf_so3_kernel_moments_workspace_bytes(const RnfSo3KernelMoments *moments);
 
+/* The distribution function of the geodesic angle from query rotations to a weighted set of rotations (csrc/so3_angle_cdf.h): the
+ * mass of a ball about an estimate, hence its error radii, and its expected error.  Centres, queries, log-weights and groups as
+ * rnf_so3_kernel_moments.  With d2_ij = |Q_i - C_j|_F^2 = 8 sin^2(theta_ij / 2) from the nine fp32 differences (capped at FLT_MAX) and
+ * theta_ij = 2 asin(min(1, sqrt(d2_ij / 8))), per group g and query i:
+ *   mass[g][t][i]       = sum_j w_gj [d2_ij <= tau_t]     fp32, in [0, 1]
+ *   mean_angle[g][i]    = sum_j w_gj theta_ij             radians
+ *   mean_sq_angle[g][i] = sum_j w_gj theta_ij^2
+ * The T thresholds, 0 <= T <= 8, come in exactly one of two forms: thresholds, HOST angles in radians in [0, pi] shared by all queries,
+ * each converted to tau = (float)(8 sin^2(theta / 2)) in fp64 and rounded once (an angle >= pi is FLT_MAX: everything counts); or
+ * query_tau, squared chordal distances on the device, one set per (group, query).  Both NULL with T = 0 is allowed when a moment output
+ * is requested.  The comparison is made on d2, never on an angle.  Any output pointer may be NULL.
+ * Edge cases: a centre with log-weight -inf is left out whatever its entries; another non-finite centre or a NaN log-weight makes its
+ * group NaN; a non-finite query is NaN; a group with no mass is NaN; m = 0 is a no-op; a NaN query_tau entry gives a NaN mass for that
+ * slot only; tau < 0 gives 0.
+ * Deterministic: chunks of 4096 centres, normalised fp32 weights from a prepass, one fp64 partial per (group, chunk, query, slot) --
+ * fp32 over at most 64 centres -- added in chunk order in fp64 and rounded once; no floating-point atomics.  A (group, query)'s outputs
+ * are bit-identical from run to run and whatever m, G, the query's position and the group's position are, whether its queries are
+ * shared or given per group, and however the thresholds are split over calls.  Five launches.  Stream-ordered, no host
+ * synchronisation, capturable in a HIP graph as a linear chain. */
+typedef struct RnfSo3AngleCdf {
+    size_t struct_bytes;        /* sizeof(RnfSo3AngleCdf); any other value is refused (header and library differ) */
+    const float *centres;       /* dev float[n][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9], or float[G][m][9] with group_queries; 16-byte aligned */
+    const float *log_weights;   /* dev float[G][n], or NULL (uniform weights) */
+    int64_t n;                  /* centres, 1..2^24 */
+    int64_t m;                  /* queries (per group), 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    int32_t group_queries;      /* 0: the groups share the queries; != 0: one set per group */
+    int32_t T;                  /* thresholds, 0..8; 0 only with a moment output */
+    const double *thresholds;   /* HOST double[T] angles in radians, each finite in [0, pi], or NULL */
+    const float *query_tau;     /* dev float[G][T][m] squared chordal distances, or NULL; exactly one of the two when T > 0 */
+    float *mass;                /* dev float[G][T][m], or NULL */
+    float *mean_angle;          /* dev float[G][m], or NULL */
+    float *mean_sq_angle;       /* dev float[G][m], or NULL */
+    /* dev scratch, 8-byte aligned, of at least rnf_so3_angle_cdf_workspace_bytes(this struct) bytes =
+     * 8 G S ceil(n / 4096) m + 16 G ceil(n / 4096) + 8 G + 4 G n rounded up to 16, with S = (T if mass is not NULL) + (2 if mean_angle or
+     * mean_sq_angle is not NULL) */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3AngleCdf;
+int rnf_so3_angle_cdf(const RnfSo3AngleCdf *cdf);
+/* The workspace rnf_so3_angle_cdf requires for the same struct (of the pointers only mass, mean_angle and mean_sq_angle are looked at,
+ * for being NULL; none is read through); 0 when struct_bytes, T, G, n or m are out of range or the size does not fit. */
+size_t rnf_so3_angle_cdf_workspace_bytes(const RnfSo3AngleCdf *cdf);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

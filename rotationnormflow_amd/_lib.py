@@ -87,6 +87,14 @@ class So3KernelMoments(_Pass):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class So3AngleCdf(_Pass):
+    """RnfSo3AngleCdf (include/rnf_hip.h): the distribution function of the geodesic angle from queries to weighted rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("queries", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64),
+                ("m", C.c_int64), ("G", C.c_int32), ("group_queries", C.c_int32), ("T", C.c_int32), ("thresholds", C.c_void_p),
+                ("query_tau", C.c_void_p), ("mass", C.c_void_p), ("mean_angle", C.c_void_p), ("mean_sq_angle", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 GRID_FIT_STATS = ("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
@@ -185,6 +193,8 @@ _SIGNATURES = {
     "rnf_so3_kernel_sum_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelSum)]),
     "rnf_so3_kernel_moments": (C.c_int, [C.POINTER(So3KernelMoments)]),
     "rnf_so3_kernel_moments_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelMoments)]),
+    "rnf_so3_angle_cdf": (C.c_int, [C.POINTER(So3AngleCdf)]),
+    "rnf_so3_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3AngleCdf)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

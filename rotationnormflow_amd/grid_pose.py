@@ -1,7 +1,8 @@
 """The grid analyses: evaluate a flow's log-density on the HEALPix grid over SO(3) (``utils.sd``) and reduce each image's row on the
 device -- the arg-max of ``eval.py``'s ``log_pdf`` mode (``grid_estimate_rotations``), top-k modes with their mass (``grid_pose_modes``),
 highest-density credible sets (``grid_pose_credible``), samples against the density (``grid_pose_fit``), matrix-Fisher and mixture fits
-(``grid_pose_fisher``, ``grid_pose_mixture``) and the coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path
+(``grid_pose_fisher``, ``grid_pose_mixture``), the error distribution of point estimates and the Acc@theta-optimal estimate
+(``grid_pose_error``, ``grid_pose_ball_estimate``) and the coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path
 from (flow, feature, base) to log-density rows (``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_fit``, ``grid_children`` and
 ``grid_beam_select`` are the reductions' entry points of the library on rows already at hand.  ``harness`` re-exports the public functions.
 """
@@ -278,6 +279,169 @@ def grid_pose_modes_refined(flow: Flow, feature: torch.Tensor = None, top_k: int
     out = dict(est=est, log_prob=log_prob, index=index, mass=mass, log_norm=log_norm, offset=offset, refined=refined, converged=converged)
     if gt is not None:
         out["spread_deg"] = torch.rad2deg(spread)
+    return out
+
+
+def _error_args(logp, grid, who: str):
+    if not (isinstance(logp, torch.Tensor) and logp.dim() == 2 and isinstance(grid, torch.Tensor) and tuple(grid.shape) == (logp.shape[1], 3, 3)):
+        raise ValueError(f"{who}: logp {tuple(getattr(logp, 'shape', ()))} and grid {tuple(getattr(grid, 'shape', ()))}, expected [g,Q] and [Q,3,3]")
+    if not 1 <= logp.shape[0] <= 65535:
+        raise ValueError(f"{who}: logp holds {logp.shape[0]} images (1 to 65535)")
+
+
+def _chord2(a, b):
+    """|a - b|_F^2 of rotations [...,3,3] in fp64 (8 sin^2 of half the angle between them)"""
+    d = a.to(torch.float64) - b.to(torch.float64)
+    return (d * d).sum(dim=(-2, -1))
+
+
+def grid_error(logp: torch.Tensor, grid: torch.Tensor, est: torch.Tensor, thresholds_deg=(15.0, 30.0), levels=(0.5, 0.9), gt: torch.Tensor = None,
+               tol_deg: float = 0.05) -> dict:
+    """The posterior distribution of the error of point estimates, in the units of Acc@theta and the median error: with image b's grid
+    posterior softmax(``logp``[b]) over ``grid`` [Q,3,3] and its estimates ``est`` [g,k,3,3] (any rotations: grid rows, refined modes,
+    another method's output), the distribution function of the geodesic angle from each estimate to the posterior
+    (``utils.angles.so3_angle_cdf`` with the grid as centres, ``logp`` [g,Q] as log-weights and one set of queries per image) gives
+    ``acc`` [g,k,T], the mass within each of ``thresholds_deg`` (up to 8, in [0, 180]) -- the predicted Acc@theta of that estimate;
+    ``expected_deg`` and ``rms_deg`` [g,k], the mean and root-mean-square angle; and ``radius_deg`` [g,k,L], for each of ``levels`` in
+    (0, 1) the radius at which the ball about the estimate reaches that mass (``so3_angle_quantile``, to ``tol_deg``): level 0.5 is the
+    predicted median error.  A NaN estimate, such as a missing mode of ``grid_pose_modes``, gives NaN.
+    ``gt`` [g,3,3], one ground truth per image, adds ``error_deg`` [g,k], the realised angle, and ``pit`` [g,k] = F(error): the mass of
+    the ball about the estimate that just reaches the truth (one call with the squared chordal distance |est - gt|_F^2 as the query's
+    threshold).  It is uniform on [0, 1] for a calibrated model: the radial counterpart of ``grid_pose_credible``'s HPD level.  A set of
+    several symmetric truths per image is refused: the error about one estimate under a symmetric posterior needs a convention for
+    the closest mode.  All float32 on the device; no host synchronisation."""
+    from .utils.angles import so3_angle_cdf, so3_angle_quantile
+    who = "grid_error"
+    _error_args(logp, grid, who)
+    if not (isinstance(est, torch.Tensor) and est.dim() == 4 and est.shape[0] == logp.shape[0] and tuple(est.shape[2:]) == (3, 3)):
+        raise ValueError(f"{who}: est {tuple(getattr(est, 'shape', ()))}, expected [{logp.shape[0]},k,3,3]")
+    th = [float(t) for t in (thresholds_deg if isinstance(thresholds_deg, (tuple, list)) else [thresholds_deg])]
+    if len(th) > 8 or not all(0.0 <= t <= 180.0 for t in th):
+        raise ValueError(f"{who}: thresholds_deg={tuple(th)}: up to 8 angles in 0..180 degrees")
+    lv = [float(a) for a in (levels if isinstance(levels, (tuple, list)) else [levels])]
+    if not all(0.0 < a < 1.0 for a in lv):
+        raise ValueError(f"{who}: level outside (0, 1) in levels={tuple(lv)}")
+    if not 0.0 < float(tol_deg) <= 180.0:
+        raise ValueError(f"{who}: tol_deg={tol_deg} outside (0, 180]")
+    if gt is not None:
+        if isinstance(gt, torch.Tensor) and gt.dim() == 4 and gt.shape[1] > 1:
+            raise ValueError(f"{who}: gt holds {gt.shape[1]} symmetric ground truths per image; the error about one estimate is defined for one")
+        if not (isinstance(gt, torch.Tensor) and gt.numel() == logp.shape[0] * 9):
+            raise ValueError(f"{who}: gt {tuple(getattr(gt, 'shape', ()))}, expected [{logp.shape[0]},3,3]")
+    if not (logp.is_cuda and grid.is_cuda and est.is_cuda and (gt is None or gt.is_cuda)):
+        raise ValueError(f"{who}: logp, grid, est and gt must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    g, k = est.shape[:2]
+    rad = [float(np.pi) if t >= 180.0 else float(np.deg2rad(np.float64(t))) for t in th]
+    cdf = so3_angle_cdf(grid, est, rad if rad else None, None, logp, group_queries=True)
+    out = dict(acc=cdf["mass"].permute(0, 2, 1).contiguous(), expected_deg=torch.rad2deg(cdf["mean_angle"]), rms_deg=torch.rad2deg(cdf["rms_angle"]))
+    if lv:
+        q = so3_angle_quantile(grid, est, lv, logp, group_queries=True, tol=float(np.deg2rad(np.float64(tol_deg))))
+        out["radius_deg"] = torch.rad2deg(q["radius"]).permute(0, 2, 1).to(torch.float32).contiguous()
+    else:
+        out["radius_deg"] = torch.empty(g, k, 0, dtype=torch.float32, device=logp.device)
+    if gt is not None:
+        d2 = _chord2(est, gt.reshape(g, 1, 3, 3).to(est.device))                           # [g,k] fp64; NaN where the estimate is
+        out["error_deg"] = torch.rad2deg(2.0 * torch.asin(torch.sqrt(d2 / 8.0).clamp(max=1.0))).to(torch.float32)
+        tau = d2.to(torch.float32)[:, None, :]                                              # rounded once: the threshold of the one call
+        out["pit"] = so3_angle_cdf(grid, est, None, tau, logp, group_queries=True, moments=False)["mass"][:, 0]
+    return out
+
+
+def grid_pose_error(flow: Flow, feature: torch.Tensor = None, est: torch.Tensor = None, thresholds_deg=(15.0, 30.0), levels=(0.5, 0.9),
+                    number_queries: int = None, recursion_level: int = None, offset=None, base=None, gt_rotation=None,
+                    images_per_launch: int = None) -> dict:
+    """``grid_error`` of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk gathering of
+    ``grid_pose_modes``).  ``est`` [B,k,3,3] or [B,3,3]: the estimates to judge; None: each image's grid arg-max, the rotation
+    ``grid_estimate_rotations`` returns (k = 1).  ``gt_rotation`` [B,3,3]: one ground truth per image, for ``error_deg`` and ``pit``.
+    -> the dict of ``grid_error`` (every entry with a leading B) plus ``est`` [B,k,3,3], ``index`` [B] int64 (the grid arg-max, as
+    ``grid_estimate_rotations``), ``log_norm`` [B] = log(sum_i exp(log p_i) / Q) and ``offset`` [3,3]."""
+    who = "grid_pose_error"
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    B = gf.B
+    if est is not None:
+        if not (isinstance(est, torch.Tensor) and est.dim() in (3, 4) and est.shape[0] == B and tuple(est.shape[-2:]) == (3, 3)):
+            raise ValueError(f"{who}: est {tuple(getattr(est, 'shape', ()))}, expected [{B},k,3,3] or [{B},3,3]")
+        est = est.reshape(B, -1, 3, 3).to(device=gf.dev, dtype=torch.float32)
+    gt = None
+    if gt_rotation is not None:
+        if gt_rotation.dim() == 4 and gt_rotation.shape[1] > 1:
+            raise ValueError(f"{who}: gt_rotation holds {gt_rotation.shape[1]} symmetric ground truths per image; the error about one "
+                             "estimate is defined for one")
+        gt = gt_rotation.reshape(B, 3, 3).to(device=gf.dev, dtype=torch.float32)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        Q = grid.shape[0]
+        outs = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            index = torch.argmax(lp, dim=1)
+            e = est[b0:b1] if est is not None else grid[index][:, None]
+            res = grid_error(lp, grid, e, thresholds_deg, levels, gt[b0:b1] if gt is not None else None)
+            res.update(est=e, index=index, log_norm=(torch.logsumexp(lp.to(torch.float64), dim=1) - float(np.log(Q))).to(torch.float32))
+            outs.append(res)
+    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
+    out["offset"] = offset
+    return out
+
+
+def grid_ball_estimate(logp: torch.Tensor, grid: torch.Tensor, radius_deg: float = 15.0, candidates: int = 4096) -> dict:
+    """The point estimate to report when scored by Acc@theta and not by density: among each image's ``candidates`` densest grid rows
+    (``torch.topk``; None: every grid row), the one whose ball of ``radius_deg`` carries the most mass under softmax(``logp``[b])
+    (``utils.angles.so3_angle_cdf`` with the candidates as per-image queries).  A tie goes to the denser row, then to the lower index --
+    the first in the candidates' order.  The maximiser over the candidates need not be the maximiser over SO(3): the ball's centre is
+    restricted to grid rows, and with ``candidates`` below Q to the densest of them; a broad mode whose rows are all less dense than
+    ``candidates`` rows elsewhere is not seen.  Cost: Q x candidates pairs per image.
+    -> dict(est [g,3,3], index [g] int64 (-1 and NaN where the image's masses are NaN), mass [g], argmax_index [g] int64 and
+    argmax_mass [g]: the densest row and its own ball mass, for comparison)"""
+    from .utils.angles import so3_angle_cdf
+    who = "grid_ball_estimate"
+    _error_args(logp, grid, who)
+    if not 0.0 < float(radius_deg) <= 180.0:
+        raise ValueError(f"{who}: radius_deg={radius_deg} outside (0, 180]")
+    g, Q = logp.shape
+    if candidates is not None and not 1 <= int(candidates):
+        raise ValueError(f"{who}: candidates={candidates} (at least 1, or None for every grid row)")
+    if not (logp.is_cuda and grid.is_cuda):
+        raise ValueError(f"{who}: logp and grid must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    rad = float(np.pi) if float(radius_deg) >= 180.0 else float(np.deg2rad(np.float64(radius_deg)))
+    lp = logp.detach().to(torch.float32)
+    top = torch.argmax(lp, dim=1)                                                            # [g]
+    if candidates is None:
+        rows = torch.arange(Q, device=lp.device)[None].expand(g, Q)
+        mass = so3_angle_cdf(grid, grid, [rad], None, lp, moments=False)["mass"][:, 0]       # [g,Q]: shared queries
+        top_mass = mass.gather(1, top[:, None])[:, 0]
+    else:
+        rows = torch.topk(lp, min(int(candidates), Q), dim=1).indices                        # [g,c]
+        queries = torch.cat([grid[top][:, None], grid[rows]], dim=1)                         # the arg-max first: its mass with its own bits
+        mass = so3_angle_cdf(grid, queries, [rad], None, lp, group_queries=True, moments=False)["mass"][:, 0]
+        top_mass, mass = mass[:, 0], mass[:, 1:]
+    dens = lp.gather(1, rows)
+    best = torch.where(torch.isnan(mass), torch.full_like(mass, -1.0), mass).max(dim=1, keepdim=True).values
+    tied = mass == best
+    dens_best = torch.where(tied, dens, torch.full_like(dens, -float("inf"))).max(dim=1, keepdim=True).values
+    index = torch.where(tied & (dens == dens_best), rows, torch.full_like(rows, Q)).min(dim=1).values
+    none = index == Q
+    index = torch.where(none, torch.full_like(index, -1), index)
+    est = grid[index.clamp(min=0)].clone()
+    est[none] = float("nan")
+    return dict(est=est, index=index, mass=torch.where(none, torch.full_like(best[:, 0], float("nan")), best[:, 0]), argmax_index=top,
+                argmax_mass=top_mass)
+
+
+def grid_pose_ball_estimate(flow: Flow, feature: torch.Tensor = None, radius_deg: float = 15.0, candidates: int = 4096,
+                            number_queries: int = None, recursion_level: int = None, offset=None, base=None,
+                            images_per_launch: int = None) -> dict:
+    """``grid_ball_estimate`` of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk
+    gathering of ``grid_pose_modes``): the Acc@``radius_deg``-optimal grid row among each image's ``candidates`` densest.
+    -> the dict of ``grid_ball_estimate`` (every entry with a leading B) plus ``offset`` [3,3]"""
+    who = "grid_pose_ball_estimate"
+    if not 0.0 < float(radius_deg) <= 180.0:
+        raise ValueError(f"{who}: radius_deg={radius_deg} outside (0, 180]")
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        outs = [grid_ball_estimate(lp, grid, radius_deg, candidates) for _, _, lp in gf.images(grid, images_per_launch, who)]
+    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
+    out["offset"] = offset
     return out
 
 
