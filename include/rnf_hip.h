@@ -705,6 +705,45 @@ int rnf_so3_angle_cdf(const RnfSo3AngleCdf *cdf);
  * for being NULL; none is read through); 0 when struct_bytes, T, G, n or m are out of range or the size does not fit. */
 size_t rnf_so3_angle_cdf_workspace_bytes(const RnfSo3AngleCdf *cdf);
 
+/* The distribution function of the geodesic angle from a weighted set of rotations to the NEAREST member of a set of query rotations
+ * (csrc/so3_set_angle_cdf.h): the error about an estimate of a symmetric object (the set is the estimate's orbit E S_s under the
+ * object's symmetry group) and the best-of-k error of k modes.  Centres, log-weights, groups, thresholds, outputs, arithmetic and
+ * edge cases as rnf_so3_angle_cdf, with queries that are m sets of K members and
+ *   d2_ij = min over the live members s of |Q_is - C_j|_F^2,     theta_ij = 2 asin(min(1, sqrt(d2_ij / 8)))
+ * in place of the single distance.  A member is live when its nine entries are finite; every other member is padding and is skipped
+ * (its distance is FLT_MAX), which is how sets of unequal size are passed.  A set with no live member is NaN in all of its outputs.
+ * min is exact: a set's outputs depend neither on the order of its members nor on padding among them, and with K = 1 every output has
+ * the bits of rnf_so3_angle_cdf for the same arguments.  Otherwise deterministic as rnf_so3_angle_cdf: a (group, set)'s outputs are
+ * bit-identical from run to run and whatever m, G, the set's position and the group's position are, whether the sets are shared or
+ * given per group, and however the thresholds are split over calls.  Five launches.  Stream-ordered, no host synchronisation,
+ * capturable in a HIP graph as a linear chain. */
+typedef struct RnfSo3SetAngleCdf {
+    size_t struct_bytes;        /* sizeof(RnfSo3SetAngleCdf); any other value is refused (header and library differ) */
+    const float *centres;       /* dev float[n][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][K][9], or float[G][m][K][9] with group_queries; 16-byte aligned */
+    const float *log_weights;   /* dev float[G][n], or NULL (uniform weights) */
+    int64_t n;                  /* centres, 1..2^24 */
+    int64_t m;                  /* sets (per group), 0..2^31 - 1 */
+    int32_t K;                  /* members per set, padding included, 1..4096 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    int32_t group_queries;      /* 0: the groups share the sets; != 0: m sets per group */
+    int32_t T;                  /* thresholds, 0..8; 0 only with a moment output */
+    const double *thresholds;   /* HOST double[T] angles in radians, each finite in [0, pi], or NULL */
+    const float *query_tau;     /* dev float[G][T][m] squared chordal distances, or NULL; exactly one of the two when T > 0 */
+    float *mass;                /* dev float[G][T][m], or NULL */
+    float *mean_angle;          /* dev float[G][m], or NULL */
+    float *mean_sq_angle;       /* dev float[G][m], or NULL */
+    /* dev scratch, 8-byte aligned, of at least rnf_so3_set_angle_cdf_workspace_bytes(this struct) bytes: rnf_so3_angle_cdf's for m
+     * queries; it does not grow with K */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3SetAngleCdf;
+int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *cdf);
+/* The workspace rnf_so3_set_angle_cdf requires for the same struct (of the pointers only mass, mean_angle and mean_sq_angle are looked
+ * at, for being NULL; none is read through); 0 when struct_bytes, T, K, G, n or m are out of range or the size does not fit. */
+size_t rnf_so3_set_angle_cdf_workspace_bytes(const RnfSo3SetAngleCdf *cdf);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

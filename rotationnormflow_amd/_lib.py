@@ -95,7 +95,15 @@ class So3AngleCdf(_Pass):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
-GRID_FIT_STATS = ("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
+class So3SetAngleCdf(_Pass):
+    """RnfSo3SetAngleCdf (include/rnf_hip.h): the distribution function of the angle to the nearest member of sets of rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("queries", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64),
+                ("m", C.c_int64), ("K", C.c_int32), ("G", C.c_int32), ("group_queries", C.c_int32), ("T", C.c_int32),
+                ("thresholds", C.c_void_p), ("query_tau", C.c_void_p), ("mass", C.c_void_p), ("mean_angle", C.c_void_p),
+                ("mean_sq_angle", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+GRID_FIT_STATS =("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
 class GridChildren(_Pass):
@@ -195,6 +203,8 @@ _SIGNATURES = {
     "rnf_so3_kernel_moments_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelMoments)]),
     "rnf_so3_angle_cdf": (C.c_int, [C.POINTER(So3AngleCdf)]),
     "rnf_so3_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3AngleCdf)]),
+    "rnf_so3_set_angle_cdf": (C.c_int, [C.POINTER(So3SetAngleCdf)]),
+    "rnf_so3_set_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3SetAngleCdf)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

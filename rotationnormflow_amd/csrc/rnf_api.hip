@@ -34,6 +34,7 @@
 #include "so3_kernel_sum.h"
 #include "so3_kernel_moments.h"
 #include "so3_angle_cdf.h"
+#include "so3_set_angle_cdf.h"
 
 using namespace rnf;
 
@@ -1887,6 +1888,113 @@ extern "C" int rnf_so3_angle_cdf(const RnfSo3AngleCdf *p) {
     hipLaunchKernelGGL(ac::so3_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
                        (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m : 0LL, (int)p->m, nchunk, T, (int)mom, taus,
                        T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The distribution function of the angle to the nearest member of a set (csrc/so3_set_angle_cdf.h): rnf_so3_angle_cdf's five launches
+// with the set kernels in place of the pairwise pass and its finalise.
+static int so3_set_angle_cdf_slots(const RnfSo3SetAngleCdf *p) { return (p->mass ? p->T : 0) + (p->mean_angle || p->mean_sq_angle ? 2 : 0); }
+
+static int so3_set_angle_cdf_check(const RnfSo3SetAngleCdf *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3SetAngleCdf))
+        return fail("RnfSo3SetAngleCdf.struct_bytes does not match the library's %zu", sizeof(RnfSo3SetAngleCdf));
+    if (p->T < 0 || p->T > sac::MAX_T) return fail("RnfSo3SetAngleCdf.T=%d outside 0..%d", p->T, sac::MAX_T);
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3SetAngleCdf.G=%d outside 1..65535", p->G);
+    if (p->K < 1 || p->K > sac::MAX_K) return fail("RnfSo3SetAngleCdf.K=%d outside 1..%d", p->K, sac::MAX_K);
+    if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3SetAngleCdf.n=%lld outside 1..2^24", (long long)p->n);
+    if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3SetAngleCdf.m=%lld outside 0..2^31-1", (long long)p->m);
+    if (ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes == 0)
+        return fail("RnfSo3SetAngleCdf: the workspace of G=%d, T=%d, n=%lld, m=%lld does not fit; tile the sets", p->G, p->T, (long long)p->n,
+                    (long long)p->m);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_set_angle_cdf_workspace_bytes(const RnfSo3SetAngleCdf *p) {
+    if (so3_set_angle_cdf_check(p)) return 0;
+    return ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes;
+}
+
+template <int TT, bool MOM>
+static void so3_set_angle_cdf_launch(const RnfSo3SetAngleCdf *p, int T, const ac::Taus &taus, const ac::Workspace &w, hipStream_t s) {
+    constexpr int GBS = sac::groups_for(TT + (MOM ? 2 : 0));
+    const int nchunk = (int)ks::chunks_for(p->n);
+    const long long q_group = p->group_queries ? 9 * (long long)p->m * p->K : 0;
+    const bool perq = T > 0 && p->query_tau;
+    if (sac::wave_per_set(p->m, nchunk, p->G, p->K)) {                                       // few sets: a wave per (group, set, chunk)
+        const dim3 waves((unsigned)p->m, nchunk, p->G);
+        if (perq)
+            hipLaunchKernelGGL((sac::so3_set_angle_cdf_wave_kernel<TT, MOM, true>), waves, dim3(64), 0, s, p->centres, p->queries, (const float *)w.wn,
+                               (int)p->n, (int)p->m, (int)p->K, q_group, taus, p->query_tau, T, w.psum);
+        else
+            hipLaunchKernelGGL((sac::so3_set_angle_cdf_wave_kernel<TT, MOM, false>), waves, dim3(64), 0, s, p->centres, p->queries, (const float *)w.wn,
+                               (int)p->n, (int)p->m, (int)p->K, q_group, taus, p->query_tau, T, w.psum);
+        return;
+    }
+    const int gb = !perq && !p->group_queries && p->G > 1 ? GBS : 1;                        // shared sets and thresholds: groups share the minima
+    const unsigned zblocks = (unsigned)((p->G + gb - 1) / gb);
+    const int block = ac::block_for(p->m, nchunk, zblocks);
+    const dim3 grid((unsigned)((p->m + block - 1) / block), nchunk, zblocks);
+#define RNF_SAC_LAUNCH(GB, PERQ)                                                                                                                 \
+    hipLaunchKernelGGL((sac::so3_set_angle_cdf_kernel<TT, MOM, GB, PERQ>), grid, dim3(block), 0, s, p->centres, p->queries, (const float *)w.wn, \
+                       (int)p->n, (int)p->m, (int)p->K, (int)p->G, q_group, taus, p->query_tau, T, w.psum)
+    if (perq) RNF_SAC_LAUNCH(1, true);
+    else if (gb > 1) RNF_SAC_LAUNCH(GBS, false);
+    else RNF_SAC_LAUNCH(1, false);
+#undef RNF_SAC_LAUNCH
+}
+
+extern "C" int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *p) {
+    if (so3_set_angle_cdf_check(p)) return 1;
+    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
+        return fail("RnfSo3SetAngleCdf: centres and queries must be 16-byte aligned");
+    const bool mom = p->mean_angle || p->mean_sq_angle;
+    if (p->T == 0 && !mom) return fail("RnfSo3SetAngleCdf.T=0 requires mean_angle or mean_sq_angle");
+    if (p->T == 0 && (p->thresholds || p->query_tau)) return fail("RnfSo3SetAngleCdf.T=0 with thresholds or query_tau");
+    if (p->T > 0 && p->thresholds && p->query_tau)
+        return fail("RnfSo3SetAngleCdf: both thresholds and query_tau are given; exactly one of the two");
+    if (p->T > 0 && !p->thresholds && !p->query_tau) return fail("RnfSo3SetAngleCdf: neither thresholds nor query_tau is given for T=%d", p->T);
+    ac::Taus taus;
+    for (int t = 0; t < ac::MAX_T; ++t) taus.t[t] = -1.f;
+    if (p->T > 0 && p->thresholds)
+        for (int t = 0; t < p->T; ++t) {
+            if (!(p->thresholds[t] >= 0.0 && p->thresholds[t] <= ac::PI))
+                return fail("RnfSo3SetAngleCdf.thresholds[%d]=%g outside 0..pi", t, p->thresholds[t]);
+            taus.t[t] = ac::tau_of(p->thresholds[t]);
+        }
+    if (p->m == 0) return 0;
+    if (!p->centres || !p->queries) return fail("RnfSo3SetAngleCdf: null centres or queries");
+    const int T = p->mass ? p->T : 0;              // masses nobody takes are not computed
+    if (T == 0 && !mom) return 0;
+    const size_t need = ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes;
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3SetAngleCdf.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_set_angle_cdf_workspace_bytes)",
+                    p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3SetAngleCdf.workspace must be 8-byte aligned");
+    const ac::Workspace w = ac::carve(p->workspace, p->n, p->m, p->G, so3_set_angle_cdf_slots(p));
+    const int nchunk = (int)ks::chunks_for(p->n);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ac::so3_angle_cdf_weights_kernel, dim3((unsigned)((p->n + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
+                       p->log_weights, (const double *)w.log_z, (int)p->n, w.wn);
+    HIP_TRY(hipGetLastError());
+#define RNF_SAC_CASE(TT)                                                       \
+    case TT:                                                                   \
+        if (mom) so3_set_angle_cdf_launch<TT, true>(p, T, taus, w, s);         \
+        else so3_set_angle_cdf_launch<TT, false>(p, T, taus, w, s);            \
+        break;
+    switch (ac::slots_for(T)) {
+        case 0: so3_set_angle_cdf_launch<0, true>(p, T, taus, w, s); break;
+        RNF_SAC_CASE(1) RNF_SAC_CASE(2) RNF_SAC_CASE(4) RNF_SAC_CASE(8)
+    }
+#undef RNF_SAC_CASE
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sac::so3_set_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
+                       (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m * p->K : 0LL, (int)p->m, (int)p->K, nchunk, T,
+                       (int)mom, taus, T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -309,7 +309,7 @@ def grid_error(logp: torch.Tensor, grid: torch.Tensor, est: torch.Tensor, thresh
     the ball about the estimate that just reaches the truth (one call with the squared chordal distance |est - gt|_F^2 as the query's
     threshold).  It is uniform on [0, 1] for a calibrated model: the radial counterpart of ``grid_pose_credible``'s HPD level.  A set of
     several symmetric truths per image is refused: the error about one estimate under a symmetric posterior needs a convention for
-    the closest mode.  All float32 on the device; no host synchronisation."""
+    the closest mode, which ``grid_error_symmetric`` and ``grid_set_error`` supply.  All float32 on the device; no host synchronisation."""
     from .utils.angles import so3_angle_cdf, so3_angle_quantile
     who = "grid_error"
     _error_args(logp, grid, who)
@@ -376,6 +376,133 @@ def grid_pose_error(flow: Flow, feature: torch.Tensor = None, est: torch.Tensor 
             index = torch.argmax(lp, dim=1)
             e = est[b0:b1] if est is not None else grid[index][:, None]
             res = grid_error(lp, grid, e, thresholds_deg, levels, gt[b0:b1] if gt is not None else None)
+            res.update(est=e, index=index, log_norm=(torch.logsumexp(lp.to(torch.float64), dim=1) - float(np.log(Q))).to(torch.float32))
+            outs.append(res)
+    out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}
+    out["offset"] = offset
+    return out
+
+
+def _error_options(thresholds_deg, levels, tol_deg, who: str):
+    """-> (thresholds in radians, levels) of the error functions, checked"""
+    th = [float(t) for t in (thresholds_deg if isinstance(thresholds_deg, (tuple, list)) else [thresholds_deg])]
+    if len(th) > 8 or not all(0.0 <= t <= 180.0 for t in th):
+        raise ValueError(f"{who}: thresholds_deg={tuple(th)}: up to 8 angles in 0..180 degrees")
+    lv = [float(a) for a in (levels if isinstance(levels, (tuple, list)) else [levels])]
+    if not all(0.0 < a < 1.0 for a in lv):
+        raise ValueError(f"{who}: level outside (0, 1) in levels={tuple(lv)}")
+    if not 0.0 < float(tol_deg) <= 180.0:
+        raise ValueError(f"{who}: tol_deg={tol_deg} outside (0, 180]")
+    return [float(np.pi) if t >= 180.0 else float(np.deg2rad(np.float64(t))) for t in th], lv
+
+
+def grid_set_error(logp: torch.Tensor, grid: torch.Tensor, sets: torch.Tensor, thresholds_deg=(15.0, 30.0), levels=(0.5, 0.9),
+                   tol_deg: float = 0.05) -> dict:
+    """``grid_error`` with a SET of rotations in place of each estimate: the posterior distribution of the angle to the nearest member
+    (``utils.angles.so3_set_angle_cdf``).  ``sets`` [g,k,K,3,3]: k sets of K members per image; a member with a non-finite entry is
+    padding and is skipped, a set of padding only gives NaN.  -> ``acc`` [g,k,T], the mass of the union of the balls of each threshold
+    about the members; ``expected_deg``, ``rms_deg`` [g,k] and ``radius_deg`` [g,k,L] of the angle to the nearest member.
+    With ``sets = modes["est"][:, None]`` -- the k modes of ``grid_pose_modes`` taken as ONE set, missing (NaN) modes counting
+    as padding -- ``acc`` is the predicted best-of-k Acc@theta, the counterpart of ``pose_accuracy(top_k=k)``; with the orbit of an
+    estimate under a symmetry group it is ``grid_error_symmetric``.  All float32 on the device; no host synchronisation."""
+    from .utils.angles import so3_set_angle_cdf, so3_set_angle_quantile
+    who = "grid_set_error"
+    _error_args(logp, grid, who)
+    if not (isinstance(sets, torch.Tensor) and sets.dim() == 5 and sets.shape[0] == logp.shape[0] and tuple(sets.shape[3:]) == (3, 3)):
+        raise ValueError(f"{who}: sets {tuple(getattr(sets, 'shape', ()))}, expected [{logp.shape[0]},k,K,3,3]")
+    if not 1 <= sets.shape[2] <= 4096:
+        raise ValueError(f"{who}: sets of {sets.shape[2]} members (1 to 4096)")
+    rad, lv = _error_options(thresholds_deg, levels, tol_deg, who)
+    if not (logp.is_cuda and grid.is_cuda and sets.is_cuda):
+        raise ValueError(f"{who}: logp, grid and sets must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    g, k = sets.shape[:2]
+    cdf = so3_set_angle_cdf(grid, sets, rad if rad else None, None, logp, group_queries=True)
+    out = dict(acc=cdf["mass"].permute(0, 2, 1).contiguous(), expected_deg=torch.rad2deg(cdf["mean_angle"]), rms_deg=torch.rad2deg(cdf["rms_angle"]))
+    if lv:
+        q = so3_set_angle_quantile(grid, sets, lv, logp, group_queries=True, tol=float(np.deg2rad(np.float64(tol_deg))))
+        out["radius_deg"] = torch.rad2deg(q["radius"]).permute(0, 2, 1).to(torch.float32).contiguous()
+    else:
+        out["radius_deg"] = torch.empty(g, k, 0, dtype=torch.float32, device=logp.device)
+    return out
+
+
+def grid_error_symmetric(logp: torch.Tensor, grid: torch.Tensor, est: torch.Tensor, symmetry: torch.Tensor = None, thresholds_deg=(15.0, 30.0),
+                         levels=(0.5, 0.9), gt: torch.Tensor = None, tol_deg: float = 0.05) -> dict:
+    """``grid_error`` for a symmetric object: the error of an estimate E is the angle to the nearest of the equivalent poses E S_s, S
+    the object's symmetry group acting in the body frame (``utils.symmetry``), which is how SYMSOL scores (the angle to the nearest of a
+    set of equivalent ground truths).  ``est`` [g,k,3,3]; ``symmetry`` [K,3,3] (``point_group``) or [g,K,3,3], one group per image, NaN
+    members as padding; None with ``gt`` [g,K',3,3]: the group recovered from the truths (``symmetry_from_truths``).
+    -> ``acc``, ``expected_deg``, ``rms_deg``, ``radius_deg`` as ``grid_set_error`` with ``orbit(est, symmetry)`` as its sets.
+    ``gt`` [g,3,3] or [g,K',3,3] (equivalent truths, the first is used) adds ``error_deg`` [g,k], the least angle from a member of the
+    orbit to the truth -- ``min_geodesic_distance(est, gt)`` when ``gt`` is the truth's orbit under the same group -- and ``pit`` [g,k]
+    = F(error), from one call with the threshold min_s |est S_s - gt_0|_F^2 formed in fp64 and rounded once."""
+    from .utils.angles import so3_set_angle_cdf
+    from .utils.symmetry import orbit, symmetry_from_truths
+    who = "grid_error_symmetric"
+    _error_args(logp, grid, who)
+    g = logp.shape[0]
+    if not (isinstance(est, torch.Tensor) and est.dim() == 4 and est.shape[0] == g and tuple(est.shape[2:]) == (3, 3)):
+        raise ValueError(f"{who}: est {tuple(getattr(est, 'shape', ()))}, expected [{g},k,3,3]")
+    if gt is not None and not (isinstance(gt, torch.Tensor) and ((gt.dim() == 3 and tuple(gt.shape) == (g, 3, 3)) or (
+            gt.dim() == 4 and gt.shape[0] == g and gt.shape[1] >= 1 and tuple(gt.shape[2:]) == (3, 3)))):
+        raise ValueError(f"{who}: gt {tuple(getattr(gt, 'shape', ()))}, expected [{g},3,3] or [{g},K,3,3]")
+    if symmetry is None:
+        if gt is None or gt.dim() != 4:
+            raise ValueError(f"{who}: symmetry=None needs gt [{g},K,3,3], a set of equivalent truths per image to recover the group from")
+        symmetry = symmetry_from_truths(gt.to(device=est.device, dtype=torch.float32))
+    if not (isinstance(symmetry, torch.Tensor) and symmetry.dim() in (3, 4) and tuple(symmetry.shape[-2:]) == (3, 3) and (
+            symmetry.dim() == 3 or symmetry.shape[0] == g)):
+        raise ValueError(f"{who}: symmetry {tuple(getattr(symmetry, 'shape', ()))}, expected [K,3,3] or [{g},K,3,3]")
+    if not (logp.is_cuda and grid.is_cuda and est.is_cuda and symmetry.is_cuda and (gt is None or gt.is_cuda)):
+        raise ValueError(f"{who}: logp, grid, est, symmetry and gt must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    sym = symmetry.to(device=est.device, dtype=torch.float32)
+    sets = orbit(est.to(torch.float32), sym if sym.dim() == 3 else sym[:, None]).contiguous()    # [g,k,K,3,3]
+    out = grid_set_error(logp, grid, sets, thresholds_deg, levels, tol_deg)
+    if gt is not None:
+        gt0 = gt.reshape(g, -1, 3, 3)[:, 0].to(est.device)
+        d2s = _chord2(sets, gt0[:, None, None])                                             # [g,k,K] fp64; NaN for padding members
+        dead = torch.isnan(d2s)
+        d2 = torch.where(dead, torch.full_like(d2s, float("inf")), d2s).amin(dim=2)
+        d2 = torch.where(dead.all(dim=2), torch.full_like(d2, float("nan")), d2)            # NaN where the estimate or the truth is
+        out["error_deg"] = torch.rad2deg(2.0 * torch.asin(torch.sqrt(d2 / 8.0).clamp(max=1.0))).to(torch.float32)
+        tau = d2.to(torch.float32)[:, None, :]                                              # rounded once: the threshold of the one call
+        out["pit"] = so3_set_angle_cdf(grid, sets, None, tau, logp, group_queries=True, moments=False)["mass"][:, 0]
+    return out
+
+
+def grid_pose_error_symmetric(flow: Flow, feature: torch.Tensor = None, symmetry: torch.Tensor = None, est: torch.Tensor = None,
+                              gt_rotation: torch.Tensor = None, thresholds_deg=(15.0, 30.0), levels=(0.5, 0.9), number_queries: int = None,
+                              recursion_level: int = None, offset=None, base=None, images_per_launch: int = None) -> dict:
+    """``grid_error_symmetric`` of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk
+    gathering of ``grid_pose_modes``), as ``grid_pose_error`` is to ``grid_error``.  ``symmetry`` [K,3,3] or [B,K,3,3]; None: recovered
+    from ``gt_rotation`` [B,K,3,3].  ``est`` [B,k,3,3] or [B,3,3]; None: each image's grid arg-max.  ``gt_rotation`` [B,3,3] or
+    [B,K,3,3] for ``error_deg`` and ``pit``.
+    -> the dict of ``grid_error_symmetric`` (every entry with a leading B) plus ``est``, ``index``, ``log_norm`` and ``offset``."""
+    who = "grid_pose_error_symmetric"
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    B = gf.B
+    if est is not None:
+        if not (isinstance(est, torch.Tensor) and est.dim() in (3, 4) and est.shape[0] == B and tuple(est.shape[-2:]) == (3, 3)):
+            raise ValueError(f"{who}: est {tuple(getattr(est, 'shape', ()))}, expected [{B},k,3,3] or [{B},3,3]")
+        est = est.reshape(B, -1, 3, 3).to(device=gf.dev, dtype=torch.float32)
+    gt = None
+    if gt_rotation is not None:
+        if not (isinstance(gt_rotation, torch.Tensor) and gt_rotation.dim() in (3, 4) and gt_rotation.shape[0] == B):
+            raise ValueError(f"{who}: gt_rotation {tuple(getattr(gt_rotation, 'shape', ()))}, expected [{B},3,3] or [{B},K,3,3]")
+        gt = gt_rotation.to(device=gf.dev, dtype=torch.float32)
+    if symmetry is not None:
+        if not (isinstance(symmetry, torch.Tensor) and symmetry.dim() in (3, 4) and (symmetry.dim() == 3 or symmetry.shape[0] == B)):
+            raise ValueError(f"{who}: symmetry {tuple(getattr(symmetry, 'shape', ()))}, expected [K,3,3] or [{B},K,3,3]")
+        symmetry = symmetry.to(device=gf.dev, dtype=torch.float32)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        Q = grid.shape[0]
+        outs = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            index = torch.argmax(lp, dim=1)
+            e = est[b0:b1] if est is not None else grid[index][:, None]
+            sym = symmetry[b0:b1] if symmetry is not None and symmetry.dim() == 4 else symmetry
+            res = grid_error_symmetric(lp, grid, e, sym, thresholds_deg, levels, gt[b0:b1] if gt is not None else None)
             res.update(est=e, index=index, log_norm=(torch.logsumexp(lp.to(torch.float64), dim=1) - float(np.log(Q))).to(torch.float32))
             outs.append(res)
     out = outs[0] if len(outs) == 1 else {key: torch.cat([o[key] for o in outs]) for key in outs[0]}

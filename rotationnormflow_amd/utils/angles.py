@@ -209,3 +209,129 @@ def so3_angle_quantile(centres, queries, levels, log_weights=None, group_queries
 
     out = _quantile_search(cdf, G, m, lv, passes, dev)                    # [G,L,m]
     return out if grouped else {key: v[0] for key, v in out.items()}
+
+
+MAX_MEMBERS = 4096                                  # K of rnf_so3_set_angle_cdf (include/rnf_hip.h)
+
+
+def _set_inputs(centres, query_sets, log_weights, group_queries, who: str):
+    """``_inputs`` for sets: query_sets [m,K,3,3] or, with ``group_queries``, [G,m,K,3,3] -> (centres, sets [m,K,3,3] or [G,m,K,3,3],
+    log-weights [G,n] or None, G, whether the outputs carry a leading G)"""
+    dims = 5 if group_queries else 4
+    if not isinstance(query_sets, torch.Tensor) or query_sets.dim() != dims or tuple(query_sets.shape[-2:]) != (3, 3):
+        want = "[G,m,K,3,3] with group_queries" if group_queries else "[m,K,3,3]"
+        raise ValueError(f"{who}: query_sets {tuple(getattr(query_sets, 'shape', ()))}, expected {want}")
+    K = query_sets.shape[-3]
+    if not 1 <= K <= MAX_MEMBERS:
+        raise ValueError(f"{who}: sets of {K} members (1 to {MAX_MEMBERS})")
+    flat = query_sets.reshape(*query_sets.shape[:-4], query_sets.shape[-4] * K, 3, 3)      # members as queries: the checks of _inputs
+    Cn, Qr, lw, G, grouped = _inputs(centres, flat, log_weights, group_queries, who)
+    return Cn, Qr.reshape(*query_sets.shape), lw, G, grouped
+
+
+def so3_set_angle_cdf(centres, query_sets, thresholds=None, query_tau=None, log_weights=None, group_queries: bool = False,
+                      moments: bool = True, workspace_cap: int = None) -> dict:
+    """The distribution function of the angle to the NEAREST member of a set (``rnf_so3_set_angle_cdf``): ``so3_angle_cdf`` with
+    d2_ij = min over the live members s of |Q_is - C_j|_F^2 in place of the single distance.  ``query_sets`` [m,K,3,3], shared by the
+    groups, or with ``group_queries`` [G,m,K,3,3]: m sets of K members; a member with a non-finite entry is padding and is skipped (sets
+    of unequal size are padded with NaN), a set of padding only is NaN.  The set is the orbit of an estimate under a symmetry group
+    (``utils.symmetry.orbit``) for the error of a symmetric object, or k modes for a best-of-k error.  The other arguments, the
+    outputs (``mass`` [T,m], ``mean_angle``, ``mean_sq_angle``, ``rms_angle`` [m], a leading G as ``so3_angle_cdf``) and the edge cases
+    are ``so3_angle_cdf``'s; ``query_tau`` is [T,m] or [G,T,m], one set of thresholds per set.  A set's outputs do not depend on the
+    order of its members or on padding among them; with K = 1 they are ``so3_angle_cdf``'s bits.  The sets and groups are tiled under
+    ``workspace_cap`` exactly as ``so3_angle_cdf`` tiles queries (the workspace does not grow with K), bit-identically.  Stream-ordered,
+    no host synchronisation, no gradient."""
+    who = "so3_set_angle_cdf"
+    Cn, Qr, lw, G, grouped = _set_inputs(centres, query_sets, log_weights, bool(group_queries), who)
+    n, dev, m, K = Cn.shape[0], Cn.device, Qr.shape[-4], Qr.shape[-3]
+    if thresholds is not None and query_tau is not None:
+        raise ValueError(f"{who}: both thresholds and query_tau are given; pass one of the two")
+    th, tau, T = None, None, 0
+    if thresholds is not None:
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().reshape(-1).tolist()
+        th = [float(thresholds)] if not isinstance(thresholds, (list, tuple)) else [float(t) for t in thresholds]
+        T = len(th)
+        for t in th:
+            if not (math.isfinite(t) and 0.0 <= t <= math.pi):
+                raise ValueError(f"{who}: threshold {t} outside 0..pi radians")
+    elif query_tau is not None:
+        want = "[G,T,m]" if grouped else "[T,m]"
+        if not isinstance(query_tau, torch.Tensor) or query_tau.dim() != (3 if grouped else 2) or query_tau.shape[-1] != m or (
+                grouped and query_tau.shape[0] != G):
+            raise ValueError(f"{who}: query_tau {tuple(getattr(query_tau, 'shape', ()))} for {G} groups of {m} sets, expected {want}")
+        if not query_tau.is_cuda:
+            raise ValueError(f"{who}: query_tau is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        tau = query_tau.detach().to(device=dev, dtype=torch.float32).reshape(G, -1, m).contiguous()
+        T = tau.shape[1]
+    if T > MAX_THRESHOLDS or (T == 0 and (th is not None or tau is not None)):
+        raise ValueError(f"{who}: {T} thresholds (1 to {MAX_THRESHOLDS})")
+    if T == 0 and not moments:
+        raise ValueError(f"{who}: no thresholds, no query_tau and no moments: nothing to compute")
+    cap = WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    out = {"mass": torch.empty(G, T, m, dtype=torch.float32, device=dev)}
+    if moments:
+        out["mean_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
+        out["mean_sq_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
+    per_set = SLOT_BYTES * (T + (2 if moments else 0)) * ((n + CHUNK - 1) // CHUNK)        # bytes per set and group
+    if per_set > cap:
+        raise ValueError(f"{who}: one set's partial sums take {per_set} bytes, above workspace_cap={cap}; pass a larger workspace_cap")
+    host = (C.c_double * T)(*th) if th is not None else None
+    if m > 0:
+        g_tile = max(1, min(G, cap // (per_set * min(m, 256))))
+        m_tile = max(1, min(m, cap // (per_set * g_tile)))
+        m_tile = m_tile if m_tile < 4 or m_tile == m else m_tile // 4 * 4          # sets of 36 K bytes: every fourth is 16-byte aligned
+        for g0 in range(0, G, g_tile):
+            g1 = min(G, g0 + g_tile)
+            for i0 in range(0, m, m_tile):
+                i1 = min(m, i0 + m_tile)
+                tile = _aligned(Qr[g0:g1, i0:i1].contiguous() if group_queries else Qr[i0:i1])
+                part = {name: v[g0:g1, ..., i0:i1] for name, v in out.items() if name != "mass" or T > 0}
+                dst = {name: v if v.is_contiguous() else torch.empty(v.shape, dtype=torch.float32, device=dev) for name, v in part.items()}
+                tau_tile = tau[g0:g1, :, i0:i1].contiguous() if tau is not None else None
+                args = _lib.So3SetAngleCdf(centres=Cn.data_ptr(), queries=tile.data_ptr(),
+                                           log_weights=lw[g0:g1].data_ptr() if lw is not None else None, n=n, m=i1 - i0, K=K, G=g1 - g0,
+                                           group_queries=int(bool(group_queries)), T=T,
+                                           thresholds=C.cast(host, C.c_void_p) if host is not None else None,
+                                           query_tau=tau_tile.data_ptr() if tau_tile is not None else None,
+                                           **{name: v.data_ptr() for name, v in dst.items()})
+                _lib.call("so3_set_angle_cdf", args, dev)
+                for name, v in part.items():
+                    if dst[name] is not v:
+                        v.copy_(dst[name])
+    if moments:
+        out["rms_angle"] = torch.sqrt(out["mean_sq_angle"])
+    return out if grouped else {name: v[0] for name, v in out.items()}
+
+
+def so3_set_angle_quantile(centres, query_sets, levels, log_weights=None, group_queries: bool = False, tol: float = 1e-3,
+                           workspace_cap: int = None) -> dict:
+    """``so3_angle_quantile`` for sets: the angle at which the union of the balls about a set's members reaches each level -- the
+    quantiles of the angle to the nearest member.  The same 9-way bracket search on ``so3_set_angle_cdf``; ``query_sets`` as there, the
+    other arguments and the result ([L,m], a leading G) as ``so3_angle_quantile``.  Bit-identical however the call is tiled."""
+    who = "so3_set_angle_quantile"
+    Cn, Qr, lw, G, grouped = _set_inputs(centres, query_sets, log_weights, bool(group_queries), who)
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().reshape(-1).tolist()
+    lv = [float(levels)] if not isinstance(levels, (list, tuple)) else [float(a) for a in levels]
+    if not lv:
+        raise ValueError(f"{who}: levels is empty")
+    for a in lv:
+        if not 0.0 < a < 1.0:
+            raise ValueError(f"{who}: level {a} outside (0, 1)")
+    if not (math.isfinite(float(tol)) and 0.0 < float(tol) <= math.pi):
+        raise ValueError(f"{who}: tol={tol} outside (0, pi] radians")
+    dev, m = Cn.device, Qr.shape[-4]
+    passes = max(1, math.ceil(math.log(math.pi / float(tol)) / math.log(9.0) - 1e-12))
+    kw = dict(log_weights=lw, group_queries=bool(group_queries), moments=False, workspace_cap=workspace_cap)
+    lead = lw is not None or bool(group_queries)
+    Qrep = torch.cat([Qr] * len(lv), dim=-4) if len(lv) > 1 else Qr      # level-major: one call per pass serves every level
+
+    def cdf(thresholds=None, query_tau=None):
+        if query_tau is not None and not lead:
+            query_tau = query_tau[0]
+        out = so3_set_angle_cdf(Cn, Qrep, thresholds, query_tau, **kw)["mass"].to(torch.float64)
+        return out if lead else out[None]                                 # [G,T,L*m]
+
+    out = _quantile_search(cdf, G, m, lv, passes, dev)                    # [G,L,m]
+    return out if grouped else {key: v[0] for key, v in out.items()}
