@@ -744,6 +744,37 @@ int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *cdf);
  * at, for being NULL; none is read through); 0 when struct_bytes, T, K, G, n or m are out of range or the size does not fit. */
 size_t rnf_so3_set_angle_cdf_workspace_bytes(const RnfSo3SetAngleCdf *cdf);
 
+/* Neighbour-limited sums of matrix-Fisher kernels over the rows of the HEALPix SO(3) grid (csrc/so3_grid_local.h): the prediction step of
+ * a Bayes filter on the grid at the levels where rnf_so3_kernel_sum's Q^2 pairs cannot run.  With the grid rows G_j of
+ * rnf_so3_healpix_grid(level, offset), d^2 = |G_j - Q_i|_F^2 = 4 (1 - cos omega) and k_kappa the kernel of rnf_so3_kernel_sum,
+ *   out[g][i] = log sum_{j : d^2(G_j, Q_i) <= d2_cut} exp(log_weights[g][j]) k_kappa(G_j, Q_i),     count[i] = the number of such j.
+ * The log-weights are NOT normalised (rnf_so3_kernel_sum normalises its weights; this pass does not).  The neighbourhood is listed from
+ * the grid's structure -- rings, an azimuth window per ring, a tilt window per pixel, each a superset -- and membership is decided by the
+ * fp32 distance of the stored rows alone, which is symmetric bit for bit: neighbourhoods among grid rows are symmetric, and every row
+ * counts once.  grid must hold the rows rnf_so3_healpix_grid wrote for the same level and offset; the queries may be any rotations.
+ * Edge cases: an empty or massless neighbourhood gives -inf; a row with log-weight -inf drops out; a NaN log-weight inside a query's
+ * neighbourhood makes that output NaN; a query with a non-finite entry gives NaN and count 0.  m = 0 is a no-op.
+ * Deterministic: one thread per query, its terms in the order (ring, pixel, tilt) of increasing index, max-then-sum, fp32 within a
+ * pixel's tilt run and fp64 above, no floating-point atomics.  A result is bit-identical from run to run and whatever m, G, the
+ * query's position and the group's position are: queries and groups may be tiled over calls.
+ * One launch, no workspace.  Stream-ordered, no host synchronisation, capturable in a HIP graph. */
+typedef struct RnfSo3GridLocalSum {
+    size_t struct_bytes;        /* sizeof(RnfSo3GridLocalSum); any other value is refused (header and library differ) */
+    int32_t level;              /* 0..6: Q = 72 * 8^level grid rows */
+    const float *offset;        /* dev float[9], the grid's offset O (row-major, a rotation), or NULL (the identity) */
+    const float *grid;          /* dev float[Q][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9] row-major, 16-byte aligned, or NULL: the grid rows (then m must be Q) */
+    const float *log_weights;   /* dev float[G][Q], or NULL (zeros) */
+    int64_t m;                  /* queries, 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    double kappa;               /* finite, 0..1e6 */
+    double d2_cut;              /* finite, 0..8; 8 (180 degrees) covers every row: rows whose fp32 distance rounds above 8 included */
+    float *out;                 /* dev float[G][m] */
+    int32_t *count;             /* dev int32[m], or NULL */
+    void *stream;
+} RnfSo3GridLocalSum;
+int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *sum);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

@@ -103,6 +103,13 @@ class So3SetAngleCdf(_Pass):
                 ("mean_sq_angle", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class So3GridLocalSum(_Pass):
+    """RnfSo3GridLocalSum (include/rnf_hip.h): neighbour-limited sums of matrix-Fisher kernels over the rows of the SO(3) grid."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("offset", C.c_void_p), ("grid", C.c_void_p), ("queries", C.c_void_p),
+                ("log_weights", C.c_void_p), ("m", C.c_int64), ("G", C.c_int32), ("kappa", C.c_double), ("d2_cut", C.c_double),
+                ("out", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
+
+
 GRID_FIT_STATS =("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
@@ -205,6 +212,7 @@ _SIGNATURES = {
     "rnf_so3_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3AngleCdf)]),
     "rnf_so3_set_angle_cdf": (C.c_int, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_set_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3SetAngleCdf)]),
+    "rnf_so3_grid_local_sum": (C.c_int, [C.POINTER(So3GridLocalSum)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -35,6 +35,7 @@
 #include "so3_kernel_moments.h"
 #include "so3_angle_cdf.h"
 #include "so3_set_angle_cdf.h"
+#include "so3_grid_local.h"
 
 using namespace rnf;
 
@@ -1995,6 +1996,46 @@ extern "C" int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *p) {
     hipLaunchKernelGGL(sac::so3_set_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
                        (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m * p->K : 0LL, (int)p->m, (int)p->K, nchunk, T,
                        (int)mom, taus, T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Neighbour-limited kernel sums over the rows of the SO(3) grid (csrc/so3_grid_local.h): one launch, no workspace.
+template <int GB, bool W>
+static void so3_grid_local_launch(const RnfSo3GridLocalSum *p, const sgl::Geometry &ge, const float *Q, double l_kappa, hipStream_t s) {
+    const dim3 grid((unsigned)((p->m + sgl::THREADS - 1) / sgl::THREADS), (unsigned)((p->G + GB - 1) / GB));
+    hipLaunchKernelGGL((sgl::so3_grid_local_kernel<GB, W>), grid, dim3(sgl::THREADS), 0, s, ge, p->offset, p->grid, Q, p->log_weights,
+                       sgl::rows_of(p->level), (int)p->m, (int)p->G, l_kappa, p->out, p->count);
+}
+
+extern "C" int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3GridLocalSum))
+        return fail("RnfSo3GridLocalSum.struct_bytes does not match the library's %zu", sizeof(RnfSo3GridLocalSum));
+    if (p->level < 0 || p->level > sgl::MAX_LEVEL) return fail("RnfSo3GridLocalSum.level=%d outside 0..%d", p->level, sgl::MAX_LEVEL);
+    if (p->G < 1 || p->G > sgl::MAX_G) return fail("RnfSo3GridLocalSum.G=%d outside 1..65535", p->G);
+    if (p->m < 0 || p->m > sgl::MAX_M) return fail("RnfSo3GridLocalSum.m=%lld outside 0..2^31-1", (long long)p->m);
+    if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("RnfSo3GridLocalSum.kappa=%g outside 0..1e6", p->kappa);
+    if (!(p->d2_cut >= 0.0 && p->d2_cut <= sgl::MAX_D2)) return fail("RnfSo3GridLocalSum.d2_cut=%g outside 0..8", p->d2_cut);
+    if (reinterpret_cast<uintptr_t>(p->grid) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
+        return fail("RnfSo3GridLocalSum: grid and queries must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(p->offset) % 4 || reinterpret_cast<uintptr_t>(p->log_weights) % 4 || reinterpret_cast<uintptr_t>(p->out) % 4 ||
+        reinterpret_cast<uintptr_t>(p->count) % 4)
+        return fail("RnfSo3GridLocalSum: offset, log_weights, out and count must be 4-byte aligned");
+    const long long Q = sgl::rows_of(p->level);
+    if (!p->queries && p->m != Q)
+        return fail("RnfSo3GridLocalSum: null queries stand for the grid rows, but m=%lld and level %d has %lld", (long long)p->m, p->level, Q);
+    if (p->m == 0) return 0;
+    if (!p->grid || !p->out) return fail("RnfSo3GridLocalSum: null grid or out");
+    const sgl::Geometry ge = sgl::geometry_of(p->level, p->kappa, p->d2_cut);
+    const double l_kappa = ks::log_normaliser(p->kappa);
+    const float *queries = p->queries ? p->queries : p->grid;
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    if (!p->log_weights)
+        so3_grid_local_launch<1, false>(p, ge, queries, l_kappa, s);
+    else if (p->G == 1)
+        so3_grid_local_launch<1, true>(p, ge, queries, l_kappa, s);
+    else
+        so3_grid_local_launch<sgl::GROUPS_PER_THREAD, true>(p, ge, queries, l_kappa, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

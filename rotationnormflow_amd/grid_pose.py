@@ -743,6 +743,97 @@ def grid_diffuse(logp: torch.Tensor, grid: torch.Tensor, kappa: float) -> torch.
     return (out.to(torch.float64) + torch.logsumexp(lw.to(torch.float64), dim=1, keepdim=True)).to(torch.float32)   # .. so their normaliser comes back
 
 
+def _local_args(logp, grid, who: str, name: str = "logp"):
+    if not isinstance(logp, torch.Tensor) or logp.dim() != 2:
+        raise ValueError(f"{who}: {name} {tuple(getattr(logp, 'shape', ()))} (want [B,Q])")
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape) != (logp.shape[1], 3, 3):
+        raise ValueError(f"{who}: grid {tuple(getattr(grid, 'shape', ()))} for {name} {tuple(logp.shape)} (want [Q,3,3])")
+    if logp.shape[0] < 1:
+        raise ValueError(f"{who}: {name} holds no image")
+    if not logp.is_cuda or not grid.is_cuda:
+        raise ValueError(f"{who}: {name} and grid must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+
+
+def grid_diffuse_local(logp: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None) -> torch.Tensor:
+    """``grid_diffuse``'s operator on the TRUNCATED motion kernel, for the levels where Q^2 pairs cannot run: each image's grid posterior
+    diffused by the isotropic matrix-Fisher kernel of concentration ``kappa`` cut off at ``radius_deg`` (default: where (kappa/2) d^2 = 18
+    nats, capped at 180 degrees; ``utils.kde.so3_grid_local_log_sum``).  ``logp`` [B,Q] on the rows of ``grid`` [Q,3,3] =
+    ``sd.generate_healpix_grid(level, offset=offset)``.  With N(j) the rows within the radius of row j, p_b = softmax(logp_b) and
+    Z_j = (1/Q) sum_{i in N(j)} k(R_j, R_i),
+        out[b][i] = log sum_{j in N(i)} p_bj k(R_j, R_i) / Z_j.
+    The neighbourhoods are symmetric (membership is one bit-symmetric fp32 distance), so this is a Markov kernel on the grid:
+    sum_i exp(out[b][i]) / Q = 1 whatever kappa and radius.  Two calls of the neighbour-limited sum: Z without weights, then the sum with
+    the log-weights log_softmax(logp) - log Z, formed in fp64 and rounded once.  The cost is Q |N| terms per image, not Q^2.
+    -> float32 [B,Q], a log-density w.r.t. Haar on the grid rows.  At radius 180 it is ``grid_diffuse`` (which stays the dense form)."""
+    from .utils.kde import so3_grid_local_log_sum
+    who = "grid_diffuse_local"
+    _local_args(logp, grid, who)
+    Q = grid.shape[0]
+    lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64) - float(np.log(Q))   # log Z_j
+    lw = (torch.log_softmax(logp.detach().to(torch.float64), dim=1) - lz).to(torch.float32)
+    return so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
+
+
+def grid_filter_step(log_prior: torch.Tensor, log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float,
+                     radius_deg: float = None, offset=None) -> dict:
+    """One step of a Bayes filter on the SO(3) grid: predict with ``grid_diffuse_local`` (motion kernel ``kappa``, ``radius_deg``), multiply
+    by the likelihood, normalise.  ``log_prior`` [B,Q] (any normalisation) and ``log_likelihood`` [B,Q] (log of the observation's density
+    at each grid rotation) on the rows of ``grid`` [Q,3,3] of ``level`` and ``offset``.
+    -> dict(posterior [B,Q] float32 with sum_i exp(posterior) / Q = 1, log_evidence [B] float64 = log (1/Q) sum_i predicted_i
+    likelihood_i, the log predictive density of the observation, predicted [B,Q] float32, the diffused prior).  The product and its
+    normaliser are formed in fp64 and rounded once."""
+    who = "grid_filter_step"
+    if not isinstance(log_likelihood, torch.Tensor) or tuple(log_likelihood.shape) != tuple(getattr(log_prior, "shape", ())):
+        raise ValueError(f"{who}: log_likelihood {tuple(getattr(log_likelihood, 'shape', ()))} for log_prior "
+                         f"{tuple(getattr(log_prior, 'shape', ()))} (want the same shape)")
+    _local_args(log_prior, grid, who, "log_prior")
+    if not log_likelihood.is_cuda:
+        raise ValueError(f"{who}: log_likelihood must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    predicted = grid_diffuse_local(log_prior, grid, level, kappa, radius_deg, offset)
+    joint = predicted.to(torch.float64) + log_likelihood.detach().to(torch.float64)
+    log_evidence = torch.logsumexp(joint, dim=1) - float(np.log(grid.shape[0]))
+    return dict(posterior=(joint - log_evidence[:, None]).to(torch.float32), log_evidence=log_evidence, predicted=predicted)
+
+
+def grid_pose_filter(flow: Flow, features: torch.Tensor = None, kappa: float = None, recursion_level: int = 4, radius_deg: float = None, offset=None,
+                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None) -> dict:
+    """A Bayes filter over a SEQUENCE of frames of one object: ``features`` [T,F], one row per frame (for an unconditional flow, the T rows
+    of ``base``).  Each frame's log-density on the level-``recursion_level`` grid -- the launches of ``grid_estimate_rotations`` -- is the
+    frame's likelihood; between frames the posterior is diffused by the motion kernel ``kappa`` (``grid_filter_step``).  Frame 0 starts
+    from ``log_prior`` [Q] (None: uniform, and no diffusion before it: its posterior is its normalised likelihood, its estimate that of
+    ``grid_estimate_rotations``).  ``offset`` as ``grid_estimate_rotations``.  Flows with batch-coupled layers are refused.
+    -> dict(est [T,3,3] the posterior's arg-max rotation per frame, index [T], log_evidence [T] float64 (the log predictive density of
+    each frame given the earlier ones), posterior [Q] float32 after the last frame (sum exp / Q = 1), grid [Q,3,3], offset [3,3])."""
+    who = "grid_pose_filter"
+    if kappa is None:
+        raise ValueError(f"{who}: kappa is required")
+    _refuse_batch_coupled(flow, who, ", so a frame's likelihood would depend on the frames that share its launch")
+    gf, level, offset = _grid_inputs(flow, features, None, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        Q = grid.shape[0]
+        post = None
+        if log_prior is not None:
+            if not isinstance(log_prior, torch.Tensor) or tuple(log_prior.shape) != (Q,):
+                raise ValueError(f"{who}: log_prior {tuple(getattr(log_prior, 'shape', ()))}, expected [{Q}]")
+            post = log_prior.detach().to(device=gf.dev, dtype=torch.float32)[None]
+        indices, evidences = [], []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            for k in range(b1 - b0):
+                ll = lp[k:k + 1]
+                if post is None:                                            # a uniform prior: nothing to diffuse
+                    ll64 = ll.to(torch.float64)
+                    ev = torch.logsumexp(ll64, dim=1) - float(np.log(Q))
+                    post = (ll64 - ev[:, None]).to(torch.float32)
+                else:
+                    step = grid_filter_step(post, ll, grid, level, kappa, radius_deg, offset)
+                    post, ev = step["posterior"], step["log_evidence"]
+                indices.append(torch.argmax(post[0]).reshape(1))
+                evidences.append(ev)
+        index = torch.cat(indices)
+    return dict(est=grid[index], index=index, log_evidence=torch.cat(evidences), posterior=post[0], grid=grid, offset=offset)
+
+
 def grid_pose_fit(flow: Flow, feature: torch.Tensor = None, samples: torch.Tensor = None, n_samples: int = 1 << 18, recursion_level: int = 2,
                   offset=None, base=None, images_per_launch: int = None) -> dict:
     """Samples against the flow's density, on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk gathering of

@@ -32,6 +32,8 @@ from .grid_pose import (grid_ball_estimate, grid_beam_estimate_rotations, grid_b
                         grid_error, grid_estimate_rotations, grid_fit, grid_modes, grid_modes_refine, grid_pose_ball_estimate, grid_pose_credible,
                         grid_pose_error, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes, grid_pose_modes_refined)
 from .grid_pose import grid_error_symmetric, grid_pose_error_symmetric, grid_set_error  # noqa: F401
+from .grid_pose import grid_diffuse_local, grid_filter_step, grid_pose_filter  # noqa: F401
+from .utils.kde import so3_grid_local_log_sum  # noqa: F401
 
 
 def load_reference_checkpoint(path, map_location="cpu") -> dict:

@@ -129,7 +129,104 @@ def so3_kernel_log_density(centres, queries=None, kappa=None, log_weights=None, 
     return out if grouped else out[0]
 
 
-MOMENT_BYTES = 92                                   # workspace bytes per (group, chunk, query) of rnf_so3_kernel_moments: 11 fp64 sums, one fp32 max
+LOCAL_MAX_LEVEL = 6                                 # levels of rnf_so3_grid_local_sum (include/rnf_hip.h)
+LOCAL_QUERY_TILE = 1 << 22                          # queries per launch of so3_grid_local_log_sum (a multiple of 4: rows of 36 bytes) ..
+LOCAL_GROUP_TILE = 4096                             # .. and groups per launch; a result does not depend on either
+LOCAL_NATS = 18.0                                   # the default cut: where (kappa/2) d^2 reaches 18 nats, e^-18 of the peak
+
+
+def local_radius_to_d2_cut(radius_deg: float) -> float:
+    """The squared chordal distance 4 (1 - cos omega) of a radius in degrees (0..180)"""
+    r = float(radius_deg)
+    if not (math.isfinite(r) and 0.0 <= r <= 180.0):
+        raise ValueError(f"so3_grid_local_log_sum: radius_deg={radius_deg} outside 0..180")
+    return 8.0 if r == 180.0 else 4.0 * (1.0 - math.cos(math.radians(r)))
+
+
+def local_default_d2_cut(kappa: float) -> float:
+    """The default cut of ``so3_grid_local_log_sum``: the d^2 at which (kappa/2) d^2 = 18 nats -- such a term is e^-18 = 1.5e-8 of the
+    peak, below fp32 resolution -- capped at 8 (180 degrees)."""
+    k = float(kappa)
+    return 8.0 if k * 8.0 <= 2.0 * LOCAL_NATS else 2.0 * LOCAL_NATS / k
+
+
+def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
+                           offset=None, return_count: bool = False):
+    """The neighbour-limited kernel sum over the rows of the SO(3) grid on the device (``rnf_so3_grid_local_sum``,
+    csrc/so3_grid_local.h): out[g][i] = log sum_{j: d^2(G_j, Q_i) <= cut} exp(log_weights[g][j]) k_kappa(G_j, Q_i) with the kernel of
+    ``so3_kernel_log_density`` and d^2 = |G_j - Q_i|_F^2 = 4 (1 - cos angle).  The log-weights are NOT normalised.
+    ``grid`` [Q,3,3]: the rows of ``sd.generate_healpix_grid(level, offset=offset)``, Q = 72 * 8^level, level 0..6 (``offset`` [3,3] must be
+    the grid's own; None: the identity).  ``queries`` [m,3,3] any rotations (None: the grid rows).  ``log_weights`` None (zeros), [Q] or [G,Q].
+    The cut: ``d2_cut`` (0..8), or ``radius_deg`` (0..180), or by default the distance at which (kappa/2) d^2 = 18 nats, capped at 180 degrees.
+    -> float32 [m] or [G,m] (with ``return_count`` also int32 [m], the rows within the cut).  An empty or massless neighbourhood gives -inf,
+    a row with log-weight -inf drops out, a NaN log-weight inside a query's neighbourhood gives NaN, a non-finite query NaN and count 0.
+    A result is bit-identical from run to run and however the call is tiled, so the tiling of queries and groups is invisible.
+    Stream-ordered, no host synchronisation, no workspace, no gradient."""
+    who = "so3_grid_local_log_sum"
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape[-2:]) != (3, 3):
+        raise ValueError(f"{who}: grid {tuple(getattr(grid, 'shape', ()))}, expected [Q,3,3]")
+    level = int(level)
+    if not 0 <= level <= LOCAL_MAX_LEVEL:
+        raise ValueError(f"{who}: level={level} outside 0..{LOCAL_MAX_LEVEL}")
+    Q = 72 * 8 ** level
+    if grid.shape[0] != Q:
+        raise ValueError(f"{who}: grid holds {grid.shape[0]} rows, level {level} has {Q}")
+    Gr = _rotations(grid, "grid", who)
+    dev = Gr.device
+    (k,), scalar = _kappas(kappa, who)
+    if not scalar:
+        raise ValueError(f"{who}: kappa is one concentration, not a sequence")
+    if radius_deg is not None and d2_cut is not None:
+        raise ValueError(f"{who}: give radius_deg or d2_cut, not both")
+    cut = local_default_d2_cut(k) if radius_deg is None and d2_cut is None else (
+        local_radius_to_d2_cut(radius_deg) if radius_deg is not None else float(d2_cut))
+    if not (math.isfinite(cut) and 0.0 <= cut <= 8.0):
+        raise ValueError(f"{who}: d2_cut={cut} outside 0..8")
+    Qr = Gr if queries is None or queries is grid else _rotations(queries, "queries", who)
+    if Qr.device != dev:
+        raise ValueError(f"{who}: queries on {Qr.device}, grid on {dev}")
+    m = Qr.shape[0]
+    if m >= 1 << 31:
+        raise ValueError(f"{who}: queries holds {m} rotations (below 2^31)")
+    lw, grouped = None, False
+    if log_weights is not None:
+        if not isinstance(log_weights, torch.Tensor) or log_weights.dim() not in (1, 2) or log_weights.shape[-1] != Q:
+            raise ValueError(f"{who}: log_weights {tuple(getattr(log_weights, 'shape', ()))} for {Q} grid rows, expected [Q] or [G,Q]")
+        if not log_weights.is_cuda:
+            raise ValueError(f"{who}: log_weights is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        grouped = log_weights.dim() == 2
+        lw = log_weights.detach().to(device=dev, dtype=torch.float32).reshape(-1, Q).contiguous()
+    G = lw.shape[0] if lw is not None else 1
+    if G < 1:
+        raise ValueError(f"{who}: log_weights holds no group")
+    off = None
+    if offset is not None:
+        off = offset.detach().reshape(9).to(device=dev, dtype=torch.float32).contiguous()
+    out = torch.empty(G, m, dtype=torch.float32, device=dev)
+    count = torch.empty(m, dtype=torch.int32, device=dev) if return_count else None
+    m_tile = max(4, int(LOCAL_QUERY_TILE) // 4 * 4)
+    g_tile = max(1, min(int(LOCAL_GROUP_TILE), MAX_GROUPS))
+    for g0 in range(0, G, g_tile):
+        g1 = min(G, g0 + g_tile)
+        for i0 in range(0, m, m_tile):
+            i1 = min(m, i0 + m_tile)
+            part = out[g0:g1, i0:i1]
+            whole = part.is_contiguous()
+            dst = part if whole else torch.empty(g1 - g0, i1 - i0, dtype=torch.float32, device=dev)
+            all_rows = Qr is Gr and i0 == 0 and i1 == m                      # a null pointer stands for the grid rows
+            tile = None if all_rows else _aligned(Qr[i0:i1])
+            args = _lib.So3GridLocalSum(level=level, offset=None if off is None else off.data_ptr(), grid=Gr.data_ptr(),
+                                        queries=None if all_rows else tile.data_ptr(), log_weights=lw[g0:g1].data_ptr() if lw is not None else None,
+                                        m=i1 - i0, G=g1 - g0, kappa=k, d2_cut=cut, out=dst.data_ptr(),
+                                        count=count[i0:i1].data_ptr() if return_count and g0 == 0 else None)
+            _lib.call("so3_grid_local_sum", args, dev)
+            if not whole:
+                part.copy_(dst)
+    out = out if grouped else out[0]
+    return (out, count) if return_count else out
+
+
+MOMENT_BYTES = 92                                 # workspace bytes per (group, chunk, query) of rnf_so3_kernel_moments: 11 fp64 sums, one fp32 max
 
 
 def so3_kernel_moments(centres, queries, kappa, log_weights=None, project: bool = False, group_queries: bool = False,
