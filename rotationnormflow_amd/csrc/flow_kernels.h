@@ -532,8 +532,12 @@ struct Mlp<1> {
     template <class GF, bool KEEPX0 = false, class FairT = Fair, bool DEEP = false>
     static __device__ __forceinline__ void head(const float *lds, int lane, int h, float y0, float y1, float y2,
                                                 const GF &g, Act &out, FairT &fair, bool &bad, const f32x16 *pre = nullptr) {
-        const float bA = h ? y1 : y0;
-        const float bB = h ? 1.0f : y2;
+        head_ab<GF, KEEPX0, FairT, DEEP>(lds, lane, h, h ? y1 : y0, h ? 1.0f : y2, g, out, fair, bad, pre);
+    }
+    // the same with the two fc_first operands of this lane half already chosen: bA = h ? y1 : y0, bB = h ? 1 : y2
+    template <class GF, bool KEEPX0 = false, class FairT = Fair, bool DEEP = false>
+    static __device__ __forceinline__ void head_ab(const float *lds, int lane, int h, const float bA, const float bB,
+                                                   const GF &g, Act &out, FairT &fair, bool &bad, const f32x16 *pre = nullptr) {
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float m1 = -1.0f;
         asm("" : "+s"(m1));                                     // see split_act
@@ -921,6 +925,23 @@ __device__ __forceinline__ void mobius_begin(const Rot &R, int perm_row, MobiusC
     if (S7) c.f = scale_frame(c.f, kSquash);
 }
 
+// STATIC COLUMNS (lean forward split-precision kernels).  perm_row is the same for every lane, so the three column roles of a layer --
+// input P0, conditioning P1 = P0 + 1, rewritten P2 = P0 + 2 (mod 3) -- can be compile-time names: the kernel selects one of three copies
+// of this begin, and of mobius_fwd_cols below, with a scalar switch on perm_row % 3; everything between them is one shared copy that sees
+// only the frame and the fc_first operands.  With a run-time column index every get_col / set_col is a v_cndmask chain (or a ladder of
+// wave-uniform branches around register copies) per lane.  The frame is what mobius_begin<0, true> computes, bit for bit; the conditioning
+// column is NOT copied into the context (mobius_fwd_cols reads it from R, where it still is), only its two fc_first operands leave.
+template <int P0>
+__device__ __forceinline__ void mobius_begin_cols(const Rot &R, int h, Frame &f, float &bA, float &bB) {
+    const v3f y = get_col<(P0 + 1) % 3>(R);
+    f = make_frame_scaled(get_col<P0>(R), y, kSquash);
+    bA = h ? y.y : y.x;                                 // Mlp<1>::head's operands of the two exact fc_first steps
+    bB = h ? 1.0f : y.z;
+    // pinned inside the copy: left alone the optimiser sinks the three identical computations behind the switch and selects their INPUTS
+    // instead (six register copies per layer)
+    asm volatile("" : "+v"(f.r.x), "+v"(f.r.y), "+v"(f.r.z), "+v"(f.v.x), "+v"(f.v.y), "+v"(f.v.z), "+v"(bA), "+v"(bB));
+}
+
 // HALF (split-precision kernels): A accumulates sp * atan(t), mobius_fwd_finish<true> adds the constant part (so3_math.h)
 template <bool HALF, bool SAFE = true>
 __device__ __forceinline__ void segments4(const f32x16 &o, const MobiusCtx &c, float &S, float &A, float &J) {
@@ -1188,6 +1209,33 @@ __device__ __forceinline__ void mobius_fwd_finish(const MobiusCtx &c, float S, f
     set_col(R, c.p0, tx);
     set_col(R, c.p2, tz);
     ldj = fmaf(0.693147180559945309f, hw_log2(J * invS), ldj);        // J / S in [0.18, 5.7]: the hardware log2 (1 ulp) needs none of logf's range handling
+}
+// STATIC COLUMNS (see mobius_begin_cols), the finish in two pieces.  mobius_fwd_angle: everything of mobius_fwd_finish<true, true> that
+// does not name a column -- the transformed angle's (sn, cs) in the 0.7-scaled frame and the log-det -- one copy in front of the switch.
+// (A second statement of the same arithmetic, operation for operation: taking it out of mobius_fwd_finish itself re-orders the finish of
+// every other forward instantiation, whose 128-register members have no slack.)
+__device__ __forceinline__ void mobius_fwd_angle(float S, float A, float J, float &sn, float &cs, float &ldj, bool &bad, float min_s) {
+    S = pair_sum(S);
+    A = pair_sum(A);
+    J = pair_sum(J);
+    bad |= !(S >= min_s);
+    const float invS = hw_rcp(S);
+    sincos_twice(A * invS, sn, cs);
+    sn *= -kInvSquash;
+    cs *= -kInvSquash;
+    ldj = fmaf(0.693147180559945309f, hw_log2(J * invS), ldj);
+}
+// mobius_fwd_cols: the two column writes with compile-time roles.  tx and tz are computed straight into the Rot members they replace; P1
+// follows P0 cyclically, which is the `cyc` branch of mobius_fwd_finish (the only one perm_row ever selects: (p0 + 1) % 3 - p0 is 1 or -2).
+template <int P0>
+__device__ __forceinline__ void mobius_fwd_cols(const Frame &f, float sn, float cs, Rot &R) {
+    // (the copies must not share tx either: hoisted in front of the switch it lands in ONE register triple and is copied into its column)
+    asm volatile("; static columns: x = column %2" : "+v"(sn), "+v"(cs) : "n"(P0));
+    v3f tx = f.v * sn + f.r * cs;
+    v3f tz = normalize3(cross3(tx, get_col<(P0 + 1) % 3>(R)));                          // mobiusflow.py:75-79
+    asm volatile("" : "+v"(tx.x), "+v"(tx.y), "+v"(tx.z), "+v"(tz.x), "+v"(tz.y), "+v"(tz.z));       // (pinned inside the copy, as in mobius_begin_cols)
+    set_col<P0>(R, tx);
+    set_col<(P0 + 2) % 3>(R, tz);
 }
 
 // inverse: the 4*KT segment parameters of this lane stay in registers for the 15 bisection steps
@@ -1735,6 +1783,35 @@ __device__ __forceinline__ void dma_floats(float *lds_dst, const float *g_src, i
         if (idx < n4) dma_piece(g_src + 4 * (size_t)idx, lds_dst + 4 * base);
     }
 }
+// The same copy with most of its address arithmetic off the vector unit (lean forward split-precision kernels, once per layer and phase):
+// a wave takes FOUR consecutive pieces at a time.  They share ONE per-lane address (scalar source base + 16 * lane, the lane part
+// re-derived per call: see stage_table) and one LDS base (M0); the 1 KiB from piece to piece rides in the instruction's immediate offset,
+// which the hardware adds to the source AND the LDS address (13-bit signed: 3 KiB is the reach).  dma_floats builds a 64-bit per-lane
+// address and a bounds predicate per piece (4 VALU, a branch pair and an exec save each); here it is 4 VALU per group, and only the group
+// holding the end of the copy is predicated per lane.  Which wave requests which piece is of no consequence: every wave waits for its
+// own before the layer barrier.
+template <int K>
+__device__ __forceinline__ void dma_piece_at(const char *g_lane, float *lds_piece) {       // piece K behind (g_lane, lds_piece): + K KiB on both sides
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g_lane, (__attribute__((address_space(3))) void *)lds_piece, 16, 1024 * K, 0);
+}
+__device__ __forceinline__ void dma_floats4(float *lds_dst, const float *g_src, int nfloats, int wave, int lane, int nwaves) {
+    const int n4 = nfloats >> 2;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const unsigned off = 16u * (unsigned)ln;
+    for (int base = wave * 256; base < n4; base += nwaves * 256) {        // `base` is wave uniform: 4 KiB per trip
+        const char *g = reinterpret_cast<const char *>(g_src + 4 * (size_t)base) + off;
+        float *l = lds_dst + 4 * base;
+        if (base + 256 <= n4) {
+            dma_piece_at<0>(g, l); dma_piece_at<1>(g, l); dma_piece_at<2>(g, l); dma_piece_at<3>(g, l);
+        } else {
+            if (base + ln < n4) dma_piece_at<0>(g, l);
+            if (base + 64 + ln < n4) dma_piece_at<1>(g, l);
+            if (base + 128 + ln < n4) dma_piece_at<2>(g, l);
+            if (base + 192 + ln < n4) dma_piece_at<3>(g, l);
+        }
+    }
+}
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1879,6 +1956,9 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
 #else
     constexpr bool KEEP_X0 = PREC != 0 && NW <= 8 && LEAN != 1;
 #endif         // room for x0 beside the hidden layers (Mlp<1>::head), and something to re-read
+    // static column roles (mobius_begin_cols / mobius_fwd_cols): every width of the lean forward split-precision family, so that a
+    // rotation's bits do not depend on the workgroup width its launch picked
+    constexpr bool COLS = LEAN == 1 && DIR == 0 && PREC == 1;
 #ifndef RNF_DEEP_H
 #define RNF_DEEP_H 1
 #endif
@@ -2183,6 +2263,10 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                 __syncthreads();
             }
             RNF_STAMP(0)                                          // 0: G load + synchronous staging (SYNC mode)
+            auto dma = [&](float *dst, const float *src, int nfloats) {      // the two image requests of a layer (behind B1 and B2)
+                if constexpr (COLS) dma_floats4(dst, src, nfloats, wave, lane, NW);
+                else dma_floats(dst, src, nfloats, wave, lane, NW);
+            };
 
             MobiusCtx ctx;
             typename Mlp<PREC>::Act tt;
@@ -2195,6 +2279,14 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                 } else {
                     Mlp<2>::template head_ring<GF, KEEP_X0>(ring, lane, hh, 0.f, 0.f, 0.f, gfrag, tt, bad);
                 }
+            } else if constexpr (COLS) {
+                float bA, bB;
+                switch (perm_row % 3) {                           // wave uniform (see mobius_begin_cols)
+                    case 0: mobius_begin_cols<0>(R, hh, ctx.f, bA, bB); break;
+                    case 1: mobius_begin_cols<1>(R, hh, ctx.f, bA, bB); break;
+                    default: mobius_begin_cols<2>(R, hh, ctx.f, bA, bB); break;
+                }
+                Mlp<1>::template head_ab<GF, KEEP_X0, FairT, DEEP_H>(lds, lane, hh, bA, bB, gfrag, tt, fair, bad);
             } else if (LEAN == 1 || kind == RNF_KIND_MOBIUS) {
                 mobius_begin<DIR, DIR == 0 && PREC != 0>(R, perm_row, ctx);
                 Mlp<PREC>::template head<GF, KEEP_X0, FairT, DEEP_H>(lds, lane, hh, ctx.y.x, ctx.y.y, ctx.y.z, gfrag, tt, fair, bad, have_gpre ? gpre : nullptr);
@@ -2207,7 +2299,7 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                 dma_wait_all();
                 RNF_STAMP_FINE(8)                                 // (-DRNF_STAMPS_FINE) 8: B1's wait for this wave's own DMA pieces
                 RNF_LAYER_BARRIER();
-                if (nxt_off >= 0) dma_floats(lds, args.blob + nxt_off, Lay<PREC>::HEAD_FLOATS, wave, lane, NW);
+                if (nxt_off >= 0) dma(lds, args.blob + nxt_off, Lay<PREC>::HEAD_FLOATS);
             }
             RNF_STAMP(2)                                          // 2: barrier B1 (+ DMA issue)
             const int fq1 = FUSED ? next_in_tile(pos) : -1;       // FUSED: the next MLP layer of this tile, whose G is produced during this layer
@@ -2237,7 +2329,7 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                     ++seq;
                 }
                 if (PIPE) {
-                    if (nxt_off >= 0) dma_floats(lds + Lay<PREC>::LAST, args.blob + nxt_off + Lay<PREC>::LAST, l_floats(nxt_kind), wave, lane, NW);
+                    if (nxt_off >= 0) dma(lds + Lay<PREC>::LAST, args.blob + nxt_off + Lay<PREC>::LAST, l_floats(nxt_kind));
                     tab_parity = has_table(pos) ? (seq & 1) : -1;
                     ++seq;
                     stage_table(nxt_q, seq & 1);
@@ -2297,7 +2389,17 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                     else if (PIPE || KT <= MOB_MAX_TILES_IN_LDS) mobius_fwd_tiles<PREC, LEAN == 1, LEAN != 0, FairT>(lds, KT, args.K, lane, h, tt, ctx, S, A, J, fair);
                     else mobius_fwd_tiles_restage<PREC>(lds, params, KT, args.K, lane, h, tt, ctx, S, A, J, tid, NT);
                     barrier2();
-                    mobius_fwd_finish<PREC != 0, LEAN != 0 && PREC == 1>(ctx, S, A, J, R, ldj, bad, args.min_wsum);
+                    if constexpr (COLS) {
+                        float sn, cs;
+                        mobius_fwd_angle(S, A, J, sn, cs, ldj, bad, args.min_wsum);
+                        switch (perm_row % 3) {
+                            case 0: mobius_fwd_cols<0>(ctx.f, sn, cs, R); break;
+                            case 1: mobius_fwd_cols<1>(ctx.f, sn, cs, R); break;
+                            default: mobius_fwd_cols<2>(ctx.f, sn, cs, R); break;
+                        }
+                    } else {
+                        mobius_fwd_finish<PREC != 0, LEAN != 0 && PREC == 1>(ctx, S, A, J, R, ldj, bad, args.min_wsum);
+                    }
                 }
             } else {
                 const float *lrec = lds + Lay<PREC>::LAST;

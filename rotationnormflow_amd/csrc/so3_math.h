@@ -164,6 +164,21 @@ RNF_HD void set_col(Rot &R, int p, v3f c) {
     if (p == 1) R.c1 = c;
     if (p == 2) R.c2 = c;
 }
+// The same two with the column as a compile-time name: plain member accesses (no select, no branch, no register copy).
+template <int P>
+RNF_HD v3f get_col(const Rot &R) {
+    static_assert(P >= 0 && P < 3, "column 0..2");
+    if constexpr (P == 0) return R.c0;
+    else if constexpr (P == 1) return R.c1;
+    else return R.c2;
+}
+template <int P>
+RNF_HD void set_col(Rot &R, v3f c) {
+    static_assert(P >= 0 && P < 3, "column 0..2");
+    if constexpr (P == 0) R.c0 = c;
+    else if constexpr (P == 1) R.c1 = c;
+    else R.c2 = c;
+}
 RNF_HD float dot3(v3f a, v3f b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
 RNF_HD v3f cross3(v3f a, v3f b) {
     v3f c;
