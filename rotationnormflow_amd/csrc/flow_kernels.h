@@ -1752,13 +1752,7 @@ __device__ __forceinline__ void cond36_finish(const f32x16 &o0, const f32x16 &o1
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) m[7 * i] += 1.0f;
-    if (INVERSE) {
-        float mi[36];
-        inv6(m, mi);
-        gs36_apply(mi, R, ldj);
-    } else {
-        gs36_apply(m, R, ldj);
-    }
+    cond_gs36_apply(m, INVERSE, R, ldj);                  // scaled by a power of two; the inverse pass solves for four vectors, no inverse (so3_math.h)
 }
 
 // ------------------------------------------------------------------------------------------------------------

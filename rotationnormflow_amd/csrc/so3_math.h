@@ -791,6 +791,48 @@ RNF_HD void cond_gs9_apply(float (&m)[9], bool inverse, Rot &R, float &ldj) {   
     if (inverse) gs9_apply_inverse(m, R, ldj); else gs9_apply(m, R, ldj);
 }
 
+// gram_schmidt_tangent for the per-sample layer, whose matrix is whatever a network returns.
+// b1 = a1 - (t0.a1) t0 is projected against t0 a second time, as in gram_schmidt3, and the tangent images use the corrected b1: a single
+// projection leaves t0.t1 ~ 2^-23 |a1| / |b1|, up to 190 units of 2^-23 inside cond(M) <= 1e3 and without bound as a1 approaches a0.
+// "Rotation or NaN": R' and the ldj term are both NaN unless `ok` comes in true, the columns are orthonormal to kPolar3Orth,
+// |b1| >= 2^-20 |a1| after the first projection (gram_schmidt3's rule), and det J, of the 3x3 matrix of tangent images, is a normal
+// number beside rows j_k whose squared lengths have a finite product (|det J| <= |j0| |j1| |j2|): that keeps ldj finite beside a rotation.
+// The columns' 2^-20 rule is NOT carried over to det J.  The layer folds inside its domain: det J passes through zero at matrices of
+// cond(M) ~ 10 with R' itself perfectly conditioned (|det J| / |j0||j1||j2| down to 4e-8 among 20 000 samples of cond <= 1e3), so a
+// relative threshold would turn exact rotations of the gated domain into NaN.  How little ldj says there is what the cond(J) in its
+// error figure states; a singular M on the inverse pass, whose ldj such a rule was meant for, is refused by its pivot.
+RNF_HD void gram_schmidt_tangent_checked(bool ok, v3f a0, v3f a1, const v3f (&da0)[3], const v3f (&da1)[3], Rot &R, float &ldj) {
+    const float i0 = hw_rsq(dot3(a0, a0));
+    const v3f t0 = a0 * i0;
+    const float dot = dot3(t0, a1);
+    v3f b1 = a1 - t0 * dot;
+    ok = ok && dot3(b1, b1) >= kGsRank * dot3(a1, a1);
+    b1 = b1 - t0 * dot3(t0, b1);
+    const float i1 = hw_rsq(dot3(b1, b1));
+    const v3f t1 = b1 * i1;
+    const v3f t2 = cross3(t0, t1);
+    v3f vec[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const v3f dt0 = (da0[k] - t0 * dot3(t0, da0[k])) * i0;
+        const float ddot = dot3(dt0, a1) + dot3(t0, da1[k]);
+        const v3f db1 = da1[k] - t0 * ddot - dt0 * dot;
+        const v3f dt1 = (db1 - t1 * dot3(t1, db1)) * i1;
+        const v3f dt2 = cross3(dt0, t1) + cross3(t0, dt1);
+        // delta = dR' R'^T with R' = [t0 t1 t2] (columns): delta[a][b] = sum_c dR'[a][c] R'[b][c]
+        vec[k] = v3f{dt0.x * t0.y + dt1.x * t1.y + dt2.x * t2.y,       // delta[0][1]
+                     dt0.x * t0.z + dt1.x * t1.z + dt2.x * t2.z,       // delta[0][2]
+                     dt0.y * t0.z + dt1.y * t1.z + dt2.y * t2.z};      // delta[1][2]
+    }
+    const float det = det3v(vec[0], vec[1], vec[2]);
+    const float rows = dot3(vec[0], vec[0]) * dot3(vec[1], vec[1]) * dot3(vec[2], vec[2]);
+    const float t = kPolar3Orth;                           // comparisons, not fmaxf: a NaN must fail them
+    ok = ok && fabsf(dot3(t0, t0) - 1.0f) <= t && fabsf(dot3(t1, t1) - 1.0f) <= t && fabsf(dot3(t0, t1)) <= t;
+    ok = ok && rows <= 3.402823466e38f && fabsf(det) >= 1.17549435e-38f;
+    R.c0 = nan_unless(ok, t0); R.c1 = nan_unless(ok, t1); R.c2 = nan_unless(ok, t2);
+    ldj += ok ? 0.693147180559945309f * hw_log2(fabsf(det)) : __builtin_nanf("");
+}
+
 // calculate_36: (r0 (+) r1) as a 6-vector times M [6][6]; tangent directions G_k R (left multiplication):
 // G_0 c = (c.y, -c.x, 0), G_1 c = (c.z, 0, -c.x), G_2 c = (0, c.z, -c.y)
 RNF_HD void mat6_mul(const float *M, v3f u, v3f w, v3f &a0, v3f &a1) {
@@ -801,6 +843,8 @@ RNF_HD void mat6_mul(const float *M, v3f u, v3f w, v3f &a0, v3f &a1) {
     a0 = v3f{o[0], o[1], o[2]};
     a1 = v3f{o[3], o[4], o[5]};
 }
+// The unscaled core: M as it is given and gram_schmidt_tangent as it stands (the constant-matrix layer Uncondition36Trans, whose matrix
+// is one trained parameter of order one, not the output of a network).
 RNF_HD void gs36_apply(const float *M, Rot &R, float &ldj) {
     const v3f r0 = R.c0, r1 = R.c1;
     v3f a0, a1, da0[3], da1[3];
@@ -809,6 +853,102 @@ RNF_HD void gs36_apply(const float *M, Rot &R, float &ldj) {
     mat6_mul(M, v3f{r0.z, 0.f, -r0.x}, v3f{r1.z, 0.f, -r1.x}, da0[1], da1[1]);
     mat6_mul(M, v3f{0.f, r0.z, -r0.y}, v3f{0.f, r1.z, -r1.y}, da0[2], da1[2]);
     gram_schmidt_tangent(a0, a1, da0, da1, R, ldj);
+}
+
+// ---- the per-sample 6x6 layer (Condition36Trans) ------------------------------------------------------------------------------------
+// 2^pow2_exponent36(M) brings the largest of the 36 entries into [1, 2) (polar3_exponent for thirty-six entries).
+RNF_HD int pow2_exponent36(const float (&m)[36]) {
+    float amax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 36; ++i) amax = fmaxf(amax, fabsf(m[i]));
+    return (amax > 0.f && amax <= 3.402823466e38f) ? ilogbf(amax) : 0;
+}
+// a x_j = x0_j for four right-hand sides (x[j][0..5]) by Gaussian elimination with partial pivoting and back substitution, everything in
+// registers as in inv6 (compare-and-swap of whole rows, no dynamic indexing; the pivot row is divided through by its pivot).  The inverse pass of the layer needs M^-1 applied to four
+// 6-vectors only (v and its three tangent images): a ninth of the columns the 36-column inverse carries, and backward stable
+// ((a + E) x = x0 with |E| a small multiple of 2^-23 |a|), where a product with a computed inverse is not.  `a` must have its largest
+// entry in [1, 2): returns false where a pivot is below 2^-20 (rank deficient to three bits against the largest entry), zero or
+// infinite; a NaN pivot fails neither comparison but makes every x NaN, which the caller's orthonormality check refuses.  With
+// cond(a) <= 1e3 the smallest pivot is above 1e-3 / 2^5 / sqrt(6), the worst growth of six pivoted steps included.  The smallest and the
+// largest pivot travel as two floats and are compared once at the end: a lane mask carried through the whole elimination costs the
+// bf16x3 inverse stack kernels, which already spill SGPRs, a 68-byte private segment.
+constexpr float kGs36Pivot = 9.5367431640625e-7f;                                // 2^-20
+RNF_HD bool solve6x4(float (&a)[36], float (&x)[24]) {                          // right-hand side j in x[6 j .. 6 j + 5]
+    float pmin = 3.402823466e38f, pmax = 0.f;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {                 // bubble the largest |a[r][c]| up to row c
+            const bool sw = fabsf(a[6 * r + c]) > fabsf(a[6 * c + c]);
+#pragma unroll
+            for (int k = c; k < 6; ++k) {
+                const float ac = a[6 * c + k], ar = a[6 * r + k];
+                a[6 * c + k] = sw ? ar : ac; a[6 * r + k] = sw ? ac : ar;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float xc = x[6 * j + c], xr = x[6 * j + r];
+                x[6 * j + c] = sw ? xr : xc; x[6 * j + r] = sw ? xc : xr;
+            }
+        }
+        const float p = fabsf(a[6 * c + c]);
+        pmin = p < pmin ? p : pmin; pmax = p > pmax ? p : pmax;
+        const float ip = hw_rcp(a[6 * c + c]);            // the pivot row is divided through, so the back substitution divides by nothing
+#pragma unroll
+        for (int k = c + 1; k < 6; ++k) a[6 * c + k] *= ip;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[6 * j + c] *= ip;
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const float f = a[6 * r + c];
+#pragma unroll
+            for (int k = c + 1; k < 6; ++k) a[6 * r + k] = fmaf(-f, a[6 * c + k], a[6 * r + k]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[6 * j + r] = fmaf(-f, x[6 * j + c], x[6 * j + r]);
+        }
+    }
+#pragma unroll
+    for (int c = 4; c >= 0; --c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = x[6 * j + c];
+#pragma unroll
+            for (int k = c + 1; k < 6; ++k) s = fmaf(-a[6 * c + k], x[6 * j + k], s);
+            x[6 * j + c] = s;
+        }
+    return pmin >= kGs36Pivot && pmax <= 3.402823466e38f;
+}
+// calculate_36 with a per-sample M (Condition36Trans; the inverse pass applies M^-1, squeezetrans.py:339-361) on Ms = 2^-e M,
+// e = pow2_exponent36(M) (exact): nothing is squared before the largest entry lies in [1, 2).  R' and ldj are of degree 0 in M, so
+// nothing is multiplied back and cond_gs36_apply(2^k M) is bit-equal to cond_gs36_apply(M).  The forward pass forms Ms v, the inverse pass
+// solves Ms x = v (solve6x4), for v = (r0; r1) and its three tangent images.  A rotation to kPolar3Orth beside a finite ldj, or both NaN
+// (gram_schmidt_tangent_checked; a refused pivot).  M itself is not written.  Domain and figures against fp32 LAPACK and the fp32
+// reference: DESIGN.md section 3.7d, tests/test_gs36_host.py.
+RNF_HD void cond_gs36_apply(const float (&m)[36], bool inverse, Rot &R, float &ldj) {
+    const int e = pow2_exponent36(m);
+    float a[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) a[i] = ldexpf(m[i], -e);
+    const v3f r0 = R.c0, r1 = R.c1;
+    v3f a0, a1, da0[3], da1[3];
+    bool ok = true;
+    if (inverse) {
+        float x[24];
+        x[0] = r0.x; x[1] = r0.y; x[2] = r0.z; x[3] = r1.x; x[4] = r1.y; x[5] = r1.z;
+        x[6] = r0.y; x[7] = -r0.x; x[8] = 0.f; x[9] = r1.y; x[10] = -r1.x; x[11] = 0.f;
+        x[12] = r0.z; x[13] = 0.f; x[14] = -r0.x; x[15] = r1.z; x[16] = 0.f; x[17] = -r1.x;
+        x[18] = 0.f; x[19] = r0.z; x[20] = -r0.y; x[21] = 0.f; x[22] = r1.z; x[23] = -r1.y;
+        ok = solve6x4(a, x);
+        a0 = v3f{x[0], x[1], x[2]}; a1 = v3f{x[3], x[4], x[5]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { da0[k] = v3f{x[6 * k + 6], x[6 * k + 7], x[6 * k + 8]}; da1[k] = v3f{x[6 * k + 9], x[6 * k + 10], x[6 * k + 11]}; }
+    } else {
+        mat6_mul(a, r0, r1, a0, a1);
+        mat6_mul(a, v3f{r0.y, -r0.x, 0.f}, v3f{r1.y, -r1.x, 0.f}, da0[0], da1[0]);
+        mat6_mul(a, v3f{r0.z, 0.f, -r0.x}, v3f{r1.z, 0.f, -r1.x}, da0[1], da1[1]);
+        mat6_mul(a, v3f{0.f, r0.z, -r0.y}, v3f{0.f, r1.z, -r1.y}, da0[2], da1[2]);
+    }
+    gram_schmidt_tangent_checked(ok, a0, a1, da0, da1, R, ldj);
 }
 
 // ---- conditional 3x3 layers: per-sample M (row-major) ---------------------------------------------------------------------------
