@@ -602,6 +602,244 @@ RNF_HD void gs36_backward(const float *M, const Rot &R, const Rot &gRout, float 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Condition36Trans backward for a per-sample M, both passes, on Ms = 2^-e M as so3_math.h cond_gs36_apply computes the layer
+// (e = pow2_exponent36(M)): R' and ldj are of degree 0 in M and dL/dM of degree -1, so dL/dMs is formed from Ms and dL/dM = 2^-e dL/dMs
+// (exact): dL/dM(2^k M) = 2^-k dL/dM(M) bit for bit, dL/dRin does not change, and nothing cubic in M is formed before the largest entry
+// lies in [1, 2).
+//
+// The elimination of solve6x4, kept as factors.  lu6_factor does to `a` exactly what solve6x4 does (same swaps, same pivots, the pivot
+// row divided through, the same fmaf), leaves the multipliers where they were used (a[6 r + c], r > c: no later swap moves them, the
+// swaps of column c' > c exchange columns c'..5 only), the reciprocal pivots in ip and the fifteen swap decisions as bits.  A right-hand
+// side replays them: lu6_solve (M x = b, bit-equal to what solve6x4 returns for the same b) and lu6_solve_t (M^T y = w: the same
+// factors read in the opposite order, equally backward stable).  The inverse pass needs X = Ms^-1 applied to seven and X^T to four
+// vectors in four dependent groups; one factorisation serves all of them, and no 36-column inverse is formed.
+RNF_HD bool lu6_factor(float (&a)[36], float (&ip)[6], unsigned &swaps) {
+    float pmin = 3.402823466e38f, pmax = 0.f;
+    swaps = 0u;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {                 // bubble the largest |a[r][c]| up to row c
+            const bool sw = fabsf(a[6 * r + c]) > fabsf(a[6 * c + c]);
+            swaps |= sw ? (1u << (c * 5 - c * (c - 1) / 2 + r - c - 1)) : 0u;
+#pragma unroll
+            for (int k = c; k < 6; ++k) {
+                const float ac = a[6 * c + k], ar = a[6 * r + k];
+                a[6 * c + k] = sw ? ar : ac; a[6 * r + k] = sw ? ac : ar;
+            }
+        }
+        const float p = fabsf(a[6 * c + c]);
+        pmin = p < pmin ? p : pmin; pmax = p > pmax ? p : pmax;
+        ip[c] = hw_rcp(a[6 * c + c]);
+#pragma unroll
+        for (int k = c + 1; k < 6; ++k) a[6 * c + k] *= ip[c];
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const float f = a[6 * r + c];
+#pragma unroll
+            for (int k = c + 1; k < 6; ++k) a[6 * r + k] = fmaf(-f, a[6 * c + k], a[6 * r + k]);
+        }
+    }
+    return pmin >= kGs36Pivot && pmax <= 3.402823466e38f;
+}
+template <int NR>
+RNF_HD void lu6_solve(const float (&a)[36], const float (&ip)[6], unsigned swaps, float (&x)[6 * NR]) {      // right-hand side j in x[6 j .. 6 j + 5]
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const bool sw = (swaps >> (c * 5 - c * (c - 1) / 2 + r - c - 1)) & 1u;
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const float xc = x[6 * j + c], xr = x[6 * j + r];
+                x[6 * j + c] = sw ? xr : xc; x[6 * j + r] = sw ? xc : xr;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NR; ++j) x[6 * j + c] *= ip[c];
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r)
+#pragma unroll
+            for (int j = 0; j < NR; ++j) x[6 * j + r] = fmaf(-a[6 * r + c], x[6 * j + c], x[6 * j + r]);
+    }
+#pragma unroll
+    for (int c = 4; c >= 0; --c)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            float s = x[6 * j + c];
+#pragma unroll
+            for (int k = c + 1; k < 6; ++k) s = fmaf(-a[6 * c + k], x[6 * j + k], s);
+            x[6 * j + c] = s;
+        }
+}
+// M^-1 = U^-1 E with U the unit upper triangle left in `a` and E the replayed row operations, so M^-T w = E^T (U^-T w): a forward
+// substitution with U^T, then the row operations transposed, last to first.
+template <int NR>
+RNF_HD void lu6_solve_t(const float (&a)[36], const float (&ip)[6], unsigned swaps, float (&x)[6 * NR]) {
+#pragma unroll
+    for (int k = 1; k < 6; ++k)
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            float s = x[6 * j + k];
+#pragma unroll
+            for (int c = 0; c < k; ++c) s = fmaf(-a[6 * c + k], x[6 * j + c], s);
+            x[6 * j + k] = s;
+        }
+#pragma unroll
+    for (int c = 5; c >= 0; --c) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            float s = x[6 * j + c];
+#pragma unroll
+            for (int r = c + 1; r < 6; ++r) s = fmaf(-a[6 * r + c], x[6 * j + r], s);
+            x[6 * j + c] = s * ip[c];
+        }
+#pragma unroll
+        for (int r = 5; r > c; --r) {
+            const bool sw = (swaps >> (c * 5 - c * (c - 1) / 2 + r - c - 1)) & 1u;
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const float xc = x[6 * j + c], xr = x[6 * j + r];
+                x[6 * j + c] = sw ? xr : xc; x[6 * j + r] = sw ? xc : xr;
+            }
+        }
+    }
+}
+RNF_HD void put6(float *x, v3f u, v3f w) { x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = w.x; x[4] = w.y; x[5] = w.z; }
+RNF_HD v3f top6(const float *x) { return v3f{x[0], x[1], x[2]}; }
+RNF_HD v3f bot6(const float *x) { return v3f{x[3], x[4], x[5]}; }
+
+// The reverse step.  With X = Ms (forward pass) or Ms^-1 (inverse pass) and v = (r0; r1):
+//   1. (a0; a1) = X v and the three tangent images, formed as cond_gs36_apply forms them (mat6_mul; the elimination of solve6x4), and
+//      handed to gram_schmidt_tangent_checked itself: the step refuses exactly where the forward refuses (a pivot below 2^-20, zero,
+//      infinite or NaN; |b1| < 2^-20 |a1|; columns not orthonormal; det J not a normal number; a non-finite entry) and nowhere else.
+//      A refused row gets NaN in all of gM and gRin.  As there, no relative threshold on det J.
+//   2. t0, t1, t2 by the forward's own expressions, second projection included, and gs36_backward's closed form of ldj
+//      differentiated by hand as there:  c = X^T (t2; 0), e = X^T (t1; 0), f = X^T (0; t2);  the cotangents b1, b2, b3 of c, e, f;
+//      X b_k (their way back to t1, t2);  g_a = dL/d(a0; a1);  y = X^T g_a.
+//   3. dL/dX = (t2; 0) b1^T + (t1; 0) b2^T + (0; t2) b3^T + g_a v^T, a sum of four outer products.  Forward pass: that is dL/dMs.
+//      Inverse pass:  dL/dMs = -X^T (dL/dX) X^T = -(c (X b1)^T + e (X b2)^T + f (X b3)^T + y a^T): every factor is one of the solves of
+//      step 2, backward stable each, where inv6 and inverse_matrix_grad<6> carried cond(M) three times.
+// Figures per sample against fp64, and what the routine this replaces shows: DESIGN.md 3.7d, tests/test_gs36_host.py.
+// The pass is a template argument and the caller's flag selects one of two straight-line bodies: in one body with the flag tested at
+// each step, the cotangents b_k (needed to the end on the forward pass only) and the factors (inverse pass only) stay live together.
+template <bool inverse>
+RNF_HD void cond_gs36_backward_pass(const float (&M)[36], const Rot &Rin, const Rot &gRout, float g_ldj, float (&gM)[36], Rot &gRin) {
+    const int ex = pow2_exponent36(M);
+    float a[36], ip[6];
+    unsigned swaps = 0u;
+#pragma unroll
+    for (int i = 0; i < 36; ++i) a[i] = ldexpf(M[i], -ex);
+    const v3f r0 = Rin.c0, r1 = Rin.c1;
+    v3f a0, a1, da0[3], da1[3];
+    bool ok = true;
+    if constexpr (inverse) {
+        float x[24];
+        x[0] = r0.x; x[1] = r0.y; x[2] = r0.z; x[3] = r1.x; x[4] = r1.y; x[5] = r1.z;
+        x[6] = r0.y; x[7] = -r0.x; x[8] = 0.f; x[9] = r1.y; x[10] = -r1.x; x[11] = 0.f;
+        x[12] = r0.z; x[13] = 0.f; x[14] = -r0.x; x[15] = r1.z; x[16] = 0.f; x[17] = -r1.x;
+        x[18] = 0.f; x[19] = r0.z; x[20] = -r0.y; x[21] = 0.f; x[22] = r1.z; x[23] = -r1.y;
+        ok = lu6_factor(a, ip, swaps);
+        lu6_solve<4>(a, ip, swaps, x);
+        a0 = top6(x); a1 = bot6(x);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { da0[k] = top6(x + 6 * k + 6); da1[k] = bot6(x + 6 * k + 6); }
+    } else {
+        mat6_mul(a, r0, r1, a0, a1);
+        mat6_mul(a, v3f{r0.y, -r0.x, 0.f}, v3f{r1.y, -r1.x, 0.f}, da0[0], da1[0]);
+        mat6_mul(a, v3f{r0.z, 0.f, -r0.x}, v3f{r1.z, 0.f, -r1.x}, da0[1], da1[1]);
+        mat6_mul(a, v3f{0.f, r0.z, -r0.y}, v3f{0.f, r1.z, -r1.y}, da0[2], da1[2]);
+    }
+    {
+        Rot Rchk = Rin;
+        float lchk = 0.f;
+        gram_schmidt_tangent_checked(ok, a0, a1, da0, da1, Rchk, lchk);
+        ok = lchk == lchk;                                 // NaN unless the forward returns a rotation beside a finite ldj
+    }
+    const float i0 = hw_rsq(dot3(a0, a0));
+    const v3f t0 = a0 * i0;
+    const float d = dot3(t0, a1);
+    v3f b1 = a1 - t0 * d;
+    b1 = b1 - t0 * dot3(t0, b1);                           // the second projection: the t1 the forward returns
+    const float i1 = hw_rsq(dot3(b1, b1));
+    const v3f t1 = b1 * i1, t2 = cross3(t0, t1);
+    const v3f z3 = v3f{0.f, 0.f, 0.f};
+    float cef[18];                                         // c, e, f
+    if constexpr (inverse) {
+        put6(cef, t2, z3); put6(cef + 6, t1, z3); put6(cef + 12, z3, t2);
+        lu6_solve_t<3>(a, ip, swaps, cef);
+    } else {
+        put6(cef, blk_mtv(a, 0, 0, t2), blk_mtv(a, 0, 1, t2));
+        put6(cef + 6, blk_mtv(a, 0, 0, t1), blk_mtv(a, 0, 1, t1));
+        put6(cef + 12, blk_mtv(a, 1, 0, t2), blk_mtv(a, 1, 1, t2));
+    }
+    const v3f c0 = top6(cef), c1 = bot6(cef), e0 = top6(cef + 6), e1 = bot6(cef + 6), f0 = top6(cef + 12), f1 = bot6(cef + 12);
+    const v3f p = cross3(r0, c0) + cross3(r1, c1), q = cross3(r0, e0) + cross3(r1, e1), u = cross3(r0, f0) + cross3(r1, f1);
+    const v3f pq = cross3(p, q);
+    const float gD = g_ldj * hw_rcp(dot3(u, pq));
+    const v3f g_u = pq * gD, g_p = cross3(q, u) * gD, g_q = cross3(u, p) * gD;
+    // x = r x c:  g_r += c x g_x,  g_c = g_x x r
+    v3f g_r0 = cross3(c0, g_p) + cross3(e0, g_q) + cross3(f0, g_u);
+    v3f g_r1 = cross3(c1, g_p) + cross3(e1, g_q) + cross3(f1, g_u);
+    float b[18], xb[18];                                   // b1, b2, b3 and X b1, X b2, X b3
+    put6(b, cross3(g_p, r0), cross3(g_p, r1)); put6(b + 6, cross3(g_q, r0), cross3(g_q, r1)); put6(b + 12, cross3(g_u, r0), cross3(g_u, r1));
+    v3f g_t2, g_t1;
+    if constexpr (inverse) {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) xb[i] = b[i];
+        lu6_solve<3>(a, ip, swaps, xb);
+        g_t2 = gRout.c2 + top6(xb) + bot6(xb + 12);
+        g_t1 = gRout.c1 + top6(xb + 6);
+    } else {
+        g_t2 = gRout.c2 + blk_mv(a, 0, 0, top6(b)) + blk_mv(a, 0, 1, bot6(b)) + blk_mv(a, 1, 0, top6(b + 12)) + blk_mv(a, 1, 1, bot6(b + 12));
+        g_t1 = gRout.c1 + blk_mv(a, 0, 0, top6(b + 6)) + blk_mv(a, 0, 1, bot6(b + 6));
+    }
+    v3f g_t0 = gRout.c0;
+    // t2 = t0 x t1
+    g_t0 = g_t0 + cross3(t1, g_t2);
+    g_t1 = g_t1 + cross3(g_t2, t0);
+    // t1 = b1 / |b1|;  - log|b1|
+    const v3f g_b1 = normalize_bwd(t1, i1, g_t1) - t1 * (g_ldj * i1);
+    // b1 = a1 - d t0, d = t0 . a1
+    const float g_d = -dot3(g_b1, t0);
+    g_t0 = g_t0 - g_b1 * d + a1 * g_d;
+    const v3f g_a1 = g_b1 + t0 * g_d;
+    // t0 = a0 / |a0|;  - 2 log|a0|
+    const v3f g_a0 = normalize_bwd(t0, i0, g_t0) - t0 * (2.0f * g_ldj * i0);
+    float y[6];
+    if constexpr (inverse) {
+        put6(y, g_a0, g_a1);
+        lu6_solve_t<1>(a, ip, swaps, y);
+    } else {
+        put6(y, blk_mtv(a, 0, 0, g_a0) + blk_mtv(a, 1, 0, g_a1), blk_mtv(a, 0, 1, g_a0) + blk_mtv(a, 1, 1, g_a1));
+    }
+    g_r0 = g_r0 + top6(y);
+    g_r1 = g_r1 + bot6(y);
+    const float bad = ok ? 0.f : __builtin_nanf("");
+    float va[6], ga[6], tt[12];
+    put6(va, inverse ? a0 : r0, inverse ? a1 : r1);
+    put6(ga, g_a0, g_a1);
+    put6(tt, t2, t1);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            float g;
+            if constexpr (inverse) {
+                g = -(cef[i] * xb[j] + cef[6 + i] * xb[6 + j] + cef[12 + i] * xb[12 + j] + y[i] * va[j]);
+            } else {                                       // rows 0..2: t2 b1^T + t1 b2^T, rows 3..5: t2 b3^T
+                g = ga[i] * va[j] + (i < 3 ? tt[i] * b[j] + tt[3 + i] * b[6 + j] : tt[i - 3] * b[12 + j]);
+            }
+            gM[6 * i + j] = ldexpf(g, -ex) + bad;
+        }
+    gRin.c0 = nan_unless(ok, g_r0); gRin.c1 = nan_unless(ok, g_r1); gRin.c2 = nan_unless(ok, z3);
+}
+RNF_HD void cond_gs36_backward(const float (&M)[36], bool inverse, const Rot &Rin, const Rot &gRout, float g_ldj, float (&gM)[36], Rot &gRin) {
+    if (inverse) cond_gs36_backward_pass<true>(M, Rin, gRout, g_ldj, gM, gRin);
+    else cond_gs36_backward_pass<false>(M, Rin, gRout, g_ldj, gM, gRin);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Conditional 3x3 rotation layers (flow/rottrans.py:68-91,108-181): per-sample M = I + reshape(net(feature), 3, 3).
 //   Condition9RotL:      R' = Q R      Condition9RotR: R' = R Q,      Q = U V^T of svd(M R) R^T = the orthogonal polar factor of M
 //                        (R is orthogonal), inverse pass: M^T, i.e. Q^T;  ldj = 0

@@ -304,14 +304,21 @@ RNF_RARE_FN void rare_side(int kind, int dir, const float *m, const Rot *Rin, co
     for (int i = 0; i < 16; ++i) gM_out[i] = gM[i];
     *gRin_p = gRin_v;
 }
-// calculate_36 with M[i] = src[i * stride] (+ diag on the diagonal); the inverse pass goes through M^-1
+// calculate_36 with M[i] = src[i * stride] (+ diag on the diagonal); the inverse pass goes through M^-1.  diag = 1 is the per-sample layer
+// (Condition36Trans, M = I + what a network returns): so3_grad.h cond_gs36_backward, scaled, refusing where the forward refuses.  diag = 0
+// is the constant layer (one trained matrix of order one), which keeps gs36_backward on the matrix as given, as its forward does.
 RNF_RARE_FN void rare_gs36(const float *src, int stride, float diag, int dir, const Rot *Rin, const Rot *gR, float g_ldj, float *gM,
                                                    Rot *gRin) {
     float M[36];
 #pragma unroll
     for (int i = 0; i < 36; ++i) { M[i] = src[i * stride] + ((i % 7) == 0 ? diag : 0.f); gM[i] = 0.f; }
     Rot g;
-    if (dir) {
+    if (diag != 0.f) {
+        float gm[36];
+        cond_gs36_backward(M, dir != 0, *Rin, *gR, g_ldj, gm, g);
+#pragma unroll
+        for (int i = 0; i < 36; ++i) gM[i] = gm[i];
+    } else if (dir) {
         float Mi[36], gMi[36];
 #pragma unroll
         for (int i = 0; i < 36; ++i) gMi[i] = 0.f;

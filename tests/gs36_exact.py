@@ -1,5 +1,5 @@
-"""fp64 references for the per-sample 6x6 layer Condition36Trans (csrc/so3_math.h cond_gs36_apply), the
-figures every sample is judged by, the inputs, and the two fp32 yardsticks.  No GPU, no pytest.
+"""fp64 references for the per-sample 6x6 layer Condition36Trans (csrc/so3_math.h cond_gs36_apply, csrc/so3_grad.h cond_gs36_backward),
+the figures every sample is judged by, the inputs, and the fp32 yardsticks.  No GPU, no pytest.
 
 The layer (flow/squeezetrans.py:293-361):  v = (r0; r1), the first two columns of R as a 6-vector;  (a0; a1) = X v with X = M on the forward
 and X = M^-1 on the inverse pass;  R' = Gram-Schmidt [t0 t1 t0 x t1] of A = [a0 a1];  ldj = log|det J|, J the 3x3 matrix of the images of
@@ -159,6 +159,133 @@ def rot_figure(Q, want, k):
 def ldj_figure(l, want, kj):
     """|ldj - want| / (2^-23 kappa cond(J)); kj = kappa cond(J)"""
     return _maxabs(np.asarray(l, np.float64) - want) / (U23 * kj)
+
+
+# ---- the reverse step: reference, conditioning, figures -----------------------------------------------------------------------------------
+
+def layer_grad64(M, R, gR, gl, inverse=False, at=None):
+    """(dL/dM [n,6,6], dL/dR [n,3,3]) of L = <gR, R'> + <gl, ldj> by fp64 autograd of the oracle's layer.  `at`: evaluate at this matrix in
+    place of M."""
+    Mt = _t(M if at is None else at, 6).requires_grad_(True)
+    Rt = _t(R, 3).requires_grad_(True)
+    Ro, l = layer_torch(Mt, Rt, inverse)
+    ((Ro * _t(gR, 3)).sum() + (l * torch.from_numpy(np.asarray(gl, np.float64))).sum()).backward()
+    return Mt.grad.numpy(), Rt.grad.numpy()
+
+
+def rho(M, R, inverse=False):
+    """|j0| |j1| |j2| / |det J| >= 1 (Hadamard), J = jacobian64: how far the rows of J are from orthogonal, whatever their lengths."""
+    J = jacobian64(M, R, inverse, check=False)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.linalg.norm(J, axis=-1).prod(-1) / np.abs(np.linalg.det(J))
+
+
+def grad_conditioning(M, R, inverse=False):
+    """(k, kl): what a relative perturbation eps of M does to the two parts of a gradient, relative to the part's own size.
+
+    L = <gR, R'> + gl ldj, so a gradient is the sum of a part linear in gR and a part linear in gl, and fp64 autograd gives each exactly
+    (gl = 0, and the difference).  Both are derivatives of functions of A = X v (and of the tangent images X dv_k), X = M or M^-1.
+
+    Rotation part.  R' is the Gram-Schmidt factor of A; eps |M| in M turns it by eps kappa (kappa of the module docstring: through
+    sqrt(2) |M|_2 / s2(A) forward, through the backward-stable solve cond(M) |A|_F / s2(A) inverse).  Its derivative g -> (g - t (t.g)) / |a|
+    is made of the same unit vectors and inverse lengths, each of which moves by the same relative eps kappa, so
+        d(part) <= c eps kappa |part|:                                  k = kappa.
+    ldj part.  ldj = log|det J|, its gradient is grad(det J) / det J = sum_k <row k of adj(J)^T, D j_k> / det J, j_k the rows of J.  A row
+    is a tangent image X dv_k pushed through the same normalisations as R' (j ~ P da / |a|, without dimension).  eps |M| in M moves da_k
+    by eps |M| |dv_k| whatever |da_k| itself is, so a row moves by eps kappa ABSOLUTELY (through da_k) and by eps kappa |j_k| (through
+    the frame and the lengths):  |dj_k| <= eps kappa (1 + |j_k|).  The rows have lengths of their own (dv_k may lie along a small singular
+    direction of X: |J|_2 ~ 1e-2 occurs at cond(M) ~ 500), so the absolute part cannot be dropped.  Two things move:
+      * 1 / det J, by tr(J^-1 dJ).  Norm-wise |J^-1 dJ| <= |J^-1|_2 |dJ| <= eps kappa sqrt(3) |J^-1|_2 (1 + |J|_2), which is the forward's
+        cond(J) where |J|_2 >= 1.  Row-wise, column k of J^-1 is (j_l x j_m) / det J, so |J^-1 dJ| <= sum_k |j_l| |j_m| |dj_k| / |det J|
+        <= 3 eps kappa rho (1 + 1 / min|j_k|) with rho = |j0| |j1| |j2| / |det J|.  Either holds; neither implies the other (rows of unequal
+        length: the second is smaller; three nearly parallel rows: rho ~ cond(J)^2).
+      * the cofactors j_l x j_m, by eps kappa (1 + 1 / min|j|) |j_l| |j_m| against |j_l x j_m| >= |det J| / |j_k|: the row-wise form again.
+    The first is bounded by the smaller of the two forms, the second by the row-wise one; a figure that must be O(1) for every sample takes
+        kl = kappa (|J^-1|_2 (1 + |J|_2) + rho (1 + 1 / min|j_k|)),
+    the sum standing for both terms.  Next to a fold (det J -> 0 inside the domain) both grow without bound while kappa stays
+    O(1): that is the conditioning the rotation figure does not carry.
+    The derivation is checked in tests/test_gs36_host.py: fp64 autograd at M (1 + 2^-23 U(-1, 1)) shows figures of O(1) in all 20 cells."""
+    k = kappa(M, R, inverse)
+    J = jacobian64(M, R, inverse, check=False)
+    with np.errstate(all="ignore"):
+        sv = np.linalg.svd(J, compute_uv=False)
+        rows = np.linalg.norm(J, axis=-1)
+        return k, k * ((1 + sv[:, 0]) / sv[:, -1] + rho(M, R, inverse) * (1 + 1 / rows.min(-1)))
+
+
+def tangent(R, g):
+    """The part of dL/dR a rotation can feel: vee(R^T g - g^T R), [n,3]."""
+    A = np.einsum("nki,nkj->nij", _as64(R, 3), _as64(g, 3))
+    A = A - A.transpose(0, 2, 1)
+    return np.stack([A[:, 2, 1], A[:, 0, 2], A[:, 1, 0]], 1)
+
+
+def grad_figure(g, want, want_rot, k, kl):
+    """max|g - want| / (2^-23 (k max|want_rot| + kl max|want - want_rot|)): want_rot is the gradient with g_ldj = 0 (the rotation part),
+    want - want_rot the ldj part; each is measured in its own conditioning (grad_conditioning).  With g_ldj = 0 this is
+    max|g - want| / max|want| / (2^-23 kappa), the figure of tests/gs3_exact.py."""
+    d = _as64(g).shape[-1]
+    want, want_rot = _as64(want, d), _as64(want_rot, d)
+    return _maxabs(_as64(g, d) - want) / (U23 * (k * _maxabs(want_rot) + kl * _maxabs(want - want_rot)))
+
+
+def tangent_figure(R, g, want, want_rot, k, kl):
+    """grad_figure of the tangent parts of dL/dR."""
+    a, b, br = tangent(R, g), tangent(R, want), tangent(R, want_rot)
+    return _maxabs(a - b) / (U23 * (k * _maxabs(br) + kl * _maxabs(b - br)))
+
+
+def product_terms(M, R, gR, gl, inverse=False):
+    """(terms of dL/dM, terms of dL/dR): the sizes of what the reverse step MULTIPLIES, per sample, from the fp64 inputs alone.  An fp32
+    product of terms rounds to 2^-23 of its terms, however small the sum comes out (tests/test_gs3_host.py backward_gates); restated for
+    this layer, whose reverse step is so3_grad.h cond_gs36_backward (the closed form ldj = log|u.(p x q)| - 2 log|a0| - log|b1|):
+      * the reverse of normalising, g -> (g - t (t.g)) / |a|, rounds the 3-term product t.g to 2^-23 c (c = the largest cotangent entry,
+        of R' or of ldj) and divides by |a0| or |b1|, both >= s2(A): dL/dA carries c / s2(A); the two logarithms of lengths add
+        |gl| (2 / |a0| + 1 / |b1|) <= 3 c / s2(A).
+      * the determinant D = u.(p x q): dL/du = gl (p x q) / D and its like have the sizes gl |p| |q| / |D|, gl |q| |u| / |D|,
+        gl |u| |p| / |D|, and reach dL/dX as outer products with unit vectors: S = |gl| (|p||q| + |q||u| + |u||p|) / |D|.  On their way back
+        to t1, t2 they are multiplied by X (terms |X|_2 S, without dimension as a cotangent of a unit vector is), which the division by
+        |b1|, |a0| in the reverse of normalising turns into |X|_2 S / s2(A) at most.
+      so dL/dX is made of terms T = 4 c / s2(A) + S (1 + |X|_2 / s2(A)), of the dimension 1 / X as dL/dX is.
+      * forward pass: dL/dM = dL/dX.  Inverse pass: dL/dM = -X^T (dL/dX) X^T, every term times |X|_2^2.
+      * dL/dR = X^T dL/dA + (cross products of c, e, f = X^T t with the cotangents of p, q, u): terms |X|_2 T."""
+    X = applied(M, inverse)
+    a, _ = images(M, R, inverse)
+    a0, a1 = a[:, :3], a[:, 3:]
+    R = _as64(R, 3)
+    r0, r1 = R[..., 0], R[..., 1]
+    with np.errstate(all="ignore"):
+        t0 = a0 / np.linalg.norm(a0, axis=-1, keepdims=True)
+        b1 = a1 - t0 * (t0 * a1).sum(-1, keepdims=True)
+        t1 = b1 / np.linalg.norm(b1, axis=-1, keepdims=True)
+        t2 = np.cross(t0, t1)
+        z = np.zeros_like(t2)
+        xt = lambda top, bot: np.einsum("nba,nb->na", X, np.concatenate([top, bot], -1))  # noqa: E731
+        c, e, f = xt(t2, z), xt(t1, z), xt(z, t2)
+        row = lambda w: np.cross(r0, w[:, :3]) + np.cross(r1, w[:, 3:])  # noqa: E731
+        p, q, u = row(c), row(e), row(f)
+        D = np.abs((u * np.cross(p, q)).sum(-1))
+        n = lambda w: np.linalg.norm(w, axis=-1)  # noqa: E731
+        S = np.abs(np.asarray(gl, np.float64)) * (n(p) * n(q) + n(q) * n(u) + n(u) * n(p)) / D
+        A = np.stack([a0, a1], -1)
+        s2 = np.linalg.svd(A, compute_uv=False)[:, -1]
+        x2 = np.linalg.svd(X, compute_uv=False)[:, 0]
+        cmax = np.maximum(np.abs(_as64(gR, 3)).reshape(len(R), -1).max(-1), np.abs(gl))
+        T = 4 * cmax / s2 + S * (1 + x2 / s2)
+        return T * (x2 ** 2 if inverse else 1.0), x2 * T
+
+
+def perturbed(M, seed=0):
+    """M (1 + 2^-23 U(-1, 1)) entry by entry, in fp64: what one rounding of every entry would do."""
+    M = _as64(M)
+    return M * (1 + U23 * np.random.default_rng(seed).uniform(-1, 1, M.shape))
+
+
+def recomposed32(M):
+    """The fp64 product Q R of LAPACK's fp32 QR factors of the fp32 matrix M: a matrix one backward-stable fp32 step away from M.  fp64
+    autograd evaluated there is what such a step costs a gradient: the yardstick of the reverse step, independent of the code under test."""
+    Q, U = torch.linalg.qr(_t32(M, 6))
+    return (Q.double() @ U.double()).numpy()
 
 
 # ---- the yardsticks -------------------------------------------------------------------------------------------------------------------------

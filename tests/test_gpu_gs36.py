@@ -17,6 +17,8 @@ columns, and the Moebius layer's ldj plus the layer's own at M = I.  The first r
 measured on the host build (tests/test_gs36_host.py: GS36_IDENTITY_UNITS, GS36_IDENTITY_LDJ_UNITS): these numbers of units are ADDED to the
 gates' figures, for that reason and no other.  The two ldj also carry the Moebius layer's ldj, summed in fp32: 2^-24 (|ldj| + |ldj0|).
 
+The training kernels' reverse step (csrc/so3_grad.h cond_gs36_backward) is judged per sample at the end of the file, on both block sizes.
+
 Measured on an MI355X: see the docstrings of the tests and DESIGN.md section 3.7d.
 """
 import functools
@@ -31,7 +33,9 @@ from rotationnormflow_amd import make_config, runtime, synth
 from tests import gs36_exact as gx
 from tests.gpu_helpers import product_flow
 from tests.test_gpu_polar3 import device, rotations, run
-from tests.test_gs36_host import (GS36_IDENTITY_LDJ_UNITS, GS36_IDENTITY_UNITS, apply36, h36, strictest)  # noqa: F401  (h36: a fixture)
+from tests.test_gpu_grad import train_block  # noqa: F401  (a fixture: rnf_set_train_block)
+from tests.test_gs36_host import (GS36_IDENTITY_LDJ_UNITS, GS36_IDENTITY_UNITS, apply36, backward_gates, h36, references_grad, strictest,  # noqa: F401  (h36: a fixture)
+                                  yardstick_grad)
 
 pytestmark = pytest.mark.gpu
 
@@ -371,3 +375,171 @@ def test_device_build_against_host_build(fp32, h36, inverse):
     print(f"inverse {inverse}: device R' within 4 x 2^-23 of the host build's on {np.mean(d <= 4 * U23):.4f} of the batch, max difference / bound "
           f"{np.max(d / bound):.3f}; ldj {np.max(dl / bound_l):.3f}")
     assert (d <= bound).all() and (dl <= bound_l).all(), (int(np.argmax(d / bound)), np.max(d / bound), np.max(dl / bound_l))
+
+
+# ---- training backward: so3_grad.h cond_gs36_backward inside both training kernels ---------------------------------------------------------
+
+DMAX_TRAIN = 3000.0            # the features stay far inside the half range (65504) the activations travel in
+N_TRAIN = 512
+RAGGED = 65                    # a multiple of neither 16 nor 64
+
+
+@functools.lru_cache(maxsize=None)
+def training_table():
+    """(seen [512,6,6], features, kind index): every family, sign-fixed, scales 10^U(-2, 2.7), no exact zero in D (so every entry of dL/dD
+    is readable from a feature gradient); four times as many are drawn and the first 103 of each family that are inside the domain as
+    the kernel sees them, with |D| <= DMAX_TRAIN, are kept (a condition on the input)."""
+    per = -(-N_TRAIN // len(gx.KINDS))
+    seen, feat = [], []
+    for kind in gx.KINDS:
+        f, s = as_features(sign_fix(gx.random_batch(kind, 4 * per, 7, (-2.0, 2.7))[0]))
+        keep = gx.in_domain(s) & ((s - EYE32) != 0).all((-1, -2)) & (np.abs(s - EYE32).max((-1, -2)) <= DMAX_TRAIN)
+        assert keep.sum() >= per, (kind, keep.sum())
+        seen.append(s[keep][:per]); feat.append(f[keep][:per])
+    return np.concatenate(seen)[:N_TRAIN], np.concatenate(feat)[:N_TRAIN], np.repeat(np.arange(len(gx.KINDS)), per)[:N_TRAIN]
+
+
+def _train_pass(fl, inverse, R, feat):
+    Rd = torch.from_numpy(np.ascontiguousarray(R)).cuda().requires_grad_(True)
+    fd = torch.from_numpy(np.ascontiguousarray(feat)).cuda().requires_grad_(True)
+    Ro, l = fl.inverse(Rd, fd) if inverse else fl(Rd, fd)
+    return Rd, fd, Ro, l
+
+
+def feature_grad_to_gD(gfeat, seen):
+    """dL/dD [n,6,6] from the feature gradient: the steering net's ReLUs and +-1 weights pass it unchanged.  ONE entries from gfeat[:, :10],
+    SIGNED entries from gfeat[:, 10:36] where D > 0 and from -gfeat[:, 36:62] where D < 0."""
+    n = len(seen)
+    D = (seen - EYE32).reshape(n, 36)
+    gD = np.empty((n, 36))
+    gD[:, ONE] = gfeat[:, :10]
+    gD[:, SIGNED] = np.where(D[:, SIGNED] > 0, gfeat[:, 10:36], -gfeat[:, 36:62])
+    return gD.reshape(n, 6, 6)
+
+
+@pytest.mark.parametrize("n", [N_TRAIN, RAGGED])
+@pytest.mark.parametrize("block", [16, 64])
+@pytest.mark.parametrize("inverse", PASSES)
+def test_training_backward_per_sample(inverse, block, n, train_block):
+    """.train(), default arithmetic: cond_gs36_backward inside the training kernels, the block forced to 16 (train_block16.h) and to 64
+    (train_kernels.h; the same binary that serves large batches), n = 512 and a ragged n = 65 (every eighth row of the same table).
+
+    dL/dM per sample is read from the feature gradient (feature_grad_to_gD; the Moebius layer does not see the features) and judged
+    against fp64 autograd of the fp64 layer, fed with the rotation the training forward returns for M = I (zero features: the
+    re-normalised input, module docstring).  Gate per sample: the host test's (tests/test_gs36_host.py backward_gates: 2 x the yardstick
+    of the sample's family at realistic scales, plus 4 x 2^-23 of the fp32 products), plus, in the figure, what is not the kernel's
+    doing: GS36_IDENTITY_UNITS for the rounding of the M = I run, 4 units for the 2^-22 resolution of gD on its way through the net's
+    backward, and 12 x the forward's format term (format_units): the arithmetic's error E of D moves a, its two lengths, the frame and
+    the solve, each by (|E|_2 / s0) kappa relatively, and max-entry against 2-norm costs a factor 3 (the count of tests/test_gpu_aff16.py).
+    How much of the format term is used is printed.
+    The cotangents are damped per sample by min(1, 1 / max|dL/dM of the undamped cotangents|) (fp64; the gradient is linear in them), so
+    that |dL/dM| stays of order one, inside the half range the backward's activations travel in: the overflow report must stay quiet.
+    The share of samples whose forward ldj gate is vacuous is printed and must not exceed 0.12; no sample is left out.
+    fc_last.bias.grad = sum_n gD_n to the training tests' REL = 2e-4 of its maximum against the fp64 sum.  dL/dR on the tangent space
+    against fp64 autograd of the whole oracle flow: REL of the batch maximum (the Moebius layer's share, tests/test_gpu_grad.py) plus the
+    host gate of the 6x6 layer's own dL/dR with the same additions.  Measured figures: DESIGN.md section 3.7d."""
+    from tests.test_gpu_grad import REL, tangent
+    seen, feat, kind_of = training_table()
+    if n != N_TRAIN:
+        pick = np.arange(n) * (N_TRAIN // n)
+        seen, feat, kind_of = seen[pick], feat[pick], kind_of[pick]
+    assert len(seen) == n and len(np.unique(kind_of)) == len(gx.KINDS)
+    assert_net_returns_D(inverse, feat, seen)
+    train_block(block)
+    R = rotations(n, 11)
+    cfg, w, i36 = steering(inverse)
+    fl = product_flow(cfg, w).train()
+    _, _, base, _ = _train_pass(fl, inverse, R, np.zeros_like(feat))          # the rotation that enters the 6x6 layer, re-normalised
+    base = base.detach().cpu().numpy()
+    rng = np.random.default_rng(60 + inverse)
+    gR1, gl1 = rng.standard_normal((n, 3, 3)), rng.standard_normal(n)
+    damp = np.minimum(1.0, 1.0 / gx._maxabs(gx.layer_grad64(seen, base, gR1, gl1, inverse)[0]))
+    gR, gl = (gR1 * damp[:, None, None]).astype(np.float32), (gl1 * damp).astype(np.float32)
+    Rd, fd, Ro, l = _train_pass(fl, inverse, R, feat)
+    ((Ro * torch.from_numpy(gR).cuda()).sum() + (l * torch.from_numpy(gl).cuda()).sum()).backward()
+    torch.cuda.synchronize()
+    gD = feature_grad_to_gD(fd.grad.cpu().numpy().astype(np.float64), seen)
+    assert np.isfinite(Ro.detach().cpu().numpy()).all() and np.isfinite(gD).all()
+    k, kl = gx.grad_conditioning(seen, base, inverse)
+    want = references_grad(seen, base, gR, gl, inverse)
+    yg = np.array([yardstick_grad(inverse, kd, "realistic")["grad"]["all"] for kd in gx.KINDS])[kind_of]
+    yt = np.array([yardstick_grad(inverse, kd, "realistic")["tan"]["all"] for kd in gx.KINDS])[kind_of]
+    gate, gate_R = backward_gates(inverse, seen, base, gR, gl, want["all"], want["rot"], k, kl, yg, yt)
+    den_M = k * gx._maxabs(want["rot"][0]) + kl * gx._maxabs(want["all"][0] - want["rot"][0])
+    den_R = k * gx._maxabs(gx.tangent(base, want["rot"][1])) + kl * gx._maxabs(gx.tangent(base, want["all"][1]) - gx.tangent(base, want["rot"][1]))
+    fmt = 12 * format_units(seen)
+    host_gate = gate + (4 + GS36_IDENTITY_UNITS) * U23 * den_M                      # everything but the format term
+    gate = host_gate + fmt * U23 * den_M
+    err = gx._maxabs(gD - want["all"][0])
+    used = np.maximum(err - host_gate, 0.0) / (U23 * den_M)
+    vac = float(np.mean(U23 * k * gx.cond_J(seen, base, inverse) > gx.LDJ_VACUOUS))
+    print(f"train, block {block}, n {n}, inverse {inverse}: dL/dM figure max {gx.grad_figure(gD, want['all'][0], want['rot'][0], k, kl).max():.2f}, error / gate max {np.max(err / gate):.3f}, "
+          f"max |gM| {np.abs(gD).max():.2f}; of the format term's units at most {used.max():.2f} are used (the term: {fmt.min():.0f} .. {fmt.max():.0f}), "
+          f"{np.mean(err <= host_gate):.4f} of the batch is inside the gate without it; vacuous ldj gates {vac:.4f}")
+    assert (err <= gate).all(), (int(np.argmax(err / gate)), np.max(err / gate))
+    assert vac <= 0.12
+    gb = dict(fl.named_parameters())[f"layers.{i36}.net.fc_last.bias"].grad.cpu().numpy().astype(np.float64)
+    wb = want["all"][0].reshape(n, 36).sum(0)
+    print(f"train, block {block}, n {n}, inverse {inverse}: fc_last.bias.grad error / max {np.abs(gb - wb).max() / np.abs(wb).max():.2e}")
+    assert np.abs(gb - wb).max() <= REL * np.abs(wb).max()
+    # dL/dR on the tangent space against the whole oracle flow in fp64
+    p = {kk: torch.from_numpy(v).double() for kk, v in w.items()}
+    Rt = torch.from_numpy(R).double().requires_grad_(True)
+    fn = orc.flow_inverse if inverse else orc.flow_forward
+    Rw, lw = fn(cfg, p, Rt, torch.from_numpy(feat).double(), dtype=torch.float64, grad=True)
+    ((Rw * torch.from_numpy(gR).double()).sum() + (lw * torch.from_numpy(gl).double()).sum()).backward()
+    tg, tw = tangent(R.astype(np.float64), Rd.grad.cpu().numpy().astype(np.float64)), tangent(R.astype(np.float64), Rt.grad.numpy())
+    et = np.abs(tg - tw).reshape(n, -1).max(-1)
+    gate_t = REL * np.abs(tw).max() + gate_R + (fmt + 4 + GS36_IDENTITY_UNITS) * U23 * den_R
+    print(f"train, block {block}, n {n}, inverse {inverse}: dL/dR tangent error / gate max {np.max(et / gate_t):.3f}")
+    assert np.isfinite(et).all() and (et <= gate_t).all(), (int(np.argmax(et / gate_t)), np.max(et / gate_t))
+    # The half-range overflow report stays quiet.  An overflow of the backward's half-range activations is reported one call LATER, as
+    # runtime.HalfRangeError from the next pass (tests/test_gpu_grad.py test_half_range_overflow_is_reported): these two passes are the
+    # check, not left-over code.
+    try:
+        for _ in range(2):
+            _train_pass(fl, inverse, R, feat)
+            torch.cuda.synchronize()
+    except runtime.HalfRangeError as e:
+        pytest.fail(f"the backward left the half range: {e}")
+
+
+@pytest.mark.parametrize("block", [16, 64])
+@pytest.mark.parametrize("inverse", PASSES)
+def test_a_refused_row_gets_a_nan_feature_gradient_and_no_other_row_does(fp32, inverse, block, train_block):
+    """A row the forward refuses (the zero matrix, a1 = a0, and on the inverse pass two equal rows; exact on the way in) among 97 clean
+    rows of the training table, a ragged batch: R' of that row is NaN, its feature gradient is NaN on every unit the matrix keeps active
+    and holds no finite non-zero entry, and every other row's feature gradient is finite and bit-equal to the all-clean run's."""
+    seen, feat, _ = training_table()
+    n = 97
+    pick = np.arange(n) * (N_TRAIN // n)
+    feat = feat[pick].copy()
+    train_block(block)
+    R = rotations(n, 12)
+    cfg, w, _ = steering(inverse)
+    rng = np.random.default_rng(70)
+    gR, gl = rng.standard_normal((n, 3, 3)).astype(np.float32) * 1e-3, rng.standard_normal(n).astype(np.float32) * 1e-3
+
+    def grads(f):
+        fl = product_flow(cfg, w).train()
+        Rd, fd, Ro, l = _train_pass(fl, inverse, R, f)
+        ((Ro * torch.from_numpy(gR).cuda()).sum() + (l * torch.from_numpy(gl).cuda()).sum()).backward()
+        torch.cuda.synchronize()
+        return Ro.detach().cpu().numpy(), fd.grad.cpu().numpy(), Rd.grad.cpu().numpy()
+    Rc, gc, gRc = grads(feat)
+    assert np.isfinite(Rc).all() and np.isfinite(gc).all() and np.isfinite(gRc).all()
+    bad = bad_rows()
+    rows = {5: "zero", 40: "a1_equals_a0"}
+    if inverse:
+        rows[96] = "two_equal_rows"
+    for r, what in rows.items():
+        feat[r] = bad[what]
+    Rb, gb, gRb = grads(feat)
+    rest = np.array([i not in rows for i in range(n)])
+    assert np.array_equal(Rb[rest], Rc[rest]) and np.array_equal(gb[rest], gc[rest]) and np.array_equal(gRb[rest], gRc[rest])
+    for r, what in rows.items():
+        active = feat[r, :62] > 0
+        print(f"block {block}, inverse {inverse}, {what}: R' {'NaN' if np.isnan(Rb[r]).all() else Rb[r]}, feature gradient NaN on {int(np.isnan(gb[r, :62][active]).sum())} of {int(active.sum())} active units")
+        assert np.isnan(Rb[r]).all(), (what, Rb[r])
+        assert active.any() and np.isnan(gb[r, :62][active]).all(), (what, gb[r, :62])
+        assert not (np.isfinite(gb[r]) & (gb[r] != 0)).any(), (what, gb[r])

@@ -1,10 +1,15 @@
-"""CPU: the per-sample 6x6 layer Condition36Trans (csrc/so3_math.h cond_gs36_apply: exactly what cond36_finish calls), host build without contraction, EVERY sample against fp64 (tests/gs36_exact.py) over the whole gated
-domain: cond(M) <= 1e3 at every scale, det < 0 included, both passes.
+"""CPU: the per-sample 6x6 layer Condition36Trans (csrc/so3_math.h cond_gs36_apply: exactly what cond36_finish calls; csrc/so3_grad.h
+cond_gs36_backward: exactly what the training kernels' rare_gs36 calls), host build without contraction, EVERY sample against fp64
+(tests/gs36_exact.py) over the whole gated domain: cond(M) <= 1e3 at every scale, det < 0 included, both passes.
 
 The yardsticks are computed inside the tests on the same batch: LAPACK's fp32 QR of the fp32 matrix [a0 a1 a0 x a1] for the rotation and
 |Q Q^T - I|, the oracle's own layer in fp32 torch for ldj.  The header may show twice the yardstick's batch
 maximum of the same figure in the same cell (family x window x pass).  Figures: tests/gs36_exact.py.  The measured tables (header /
 yardstick per cell), the vacuous-gate shares and what the routine this replaces shows in the same tests: DESIGN.md section 3.7d.
+
+The reverse step is judged the same way (second half of the file): dL/dM and the tangent part of dL/dR per sample against fp64 autograd of
+the oracle's layer, in the conditioning gs36_exact.grad_conditioning derives; the yardstick is fp64 autograd at the fp64 product of
+LAPACK's fp32 QR factors of M, a matrix one backward-stable fp32 step away, computed here on the same batch.
 """
 import ctypes as C
 import functools
@@ -21,7 +26,7 @@ from tests.test_host_grad import f32, ptr
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "host_gs36.cpp")
 OUT = os.path.join(HERE, "csrc", "_host_gs36.so")
-HDRS = [os.path.join(os.path.dirname(HERE), "rotationnormflow_amd", "csrc", h) for h in ("so3_math.h",)]
+HDRS = [os.path.join(os.path.dirname(HERE), "rotationnormflow_amd", "csrc", h) for h in ("so3_math.h", "so3_grad.h")]
 
 U23 = gx.U23
 ORTH_NAN = 16 * U23                                          # kPolar3Orth: what the header itself accepts as a rotation
@@ -247,3 +252,239 @@ def test_gs36_of_identity_moves_a_rotation_by_rounding_only(h36):
         d = np.abs(Ro.astype(np.float64) - R).max() / U23
         print(f"gs36(I, R), inverse {inverse}: max|R' - R| = {d:.2f} units, max|ldj| = {np.abs(l).max() / U23:.2f} units")
         assert d <= GS36_IDENTITY_UNITS and np.abs(l).max() <= GS36_IDENTITY_LDJ_UNITS * U23
+
+
+# ================================================================================================================================================
+# the reverse step: so3_grad.h cond_gs36_backward
+# ================================================================================================================================================
+
+def backward36(h36, M, R, gR, gl, inverse):
+    n = len(M)
+    gM, gRin = np.zeros((n, 36), np.float32), np.zeros((n, 9), np.float32)
+    h36.h36_backward(ptr(f32(np.asarray(M).reshape(n, 36))), ptr(f32(np.asarray(R).reshape(n, 9))), ptr(f32(np.asarray(gR).reshape(n, 9))),
+                     ptr(f32(gl)), int(inverse), n, ptr(gM), ptr(gRin))
+    return gM.reshape(-1, 6, 6), gRin.reshape(-1, 3, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def cotangents(n=N_BATCH):
+    rng = np.random.default_rng(78)
+    gR, gl = rng.standard_normal((n, 3, 3)).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    gR.setflags(write=False)
+    gl.setflags(write=False)
+    return gR, gl
+
+
+COTANGENT_SETS = ("rot", "all")                              # g_ldj = 0, and random g_ldj beside the same gR
+
+
+def references_grad(M, R, gR, gl, inverse, at=None):
+    """fp64 autograd for both cotangent sets at once: {"rot": (dL/dM, dL/dR) with g_ldj = 0, "all": with g_ldj = gl}."""
+    return {"rot": gx.layer_grad64(M, R, gR, np.zeros_like(gl), inverse, at=at), "all": gx.layer_grad64(M, R, gR, gl, inverse, at=at)}
+
+
+def figures_grad(R, got, want, k, kl):
+    """{set: (dL/dM figure, dL/dR tangent figure)} of `got` against `want` (both as references_grad returns them)."""
+    return {s: (gx.grad_figure(got[s][0], want[s][0], want["rot"][0], k, kl), gx.tangent_figure(R, got[s][1], want[s][1], want["rot"][1], k, kl))
+            for s in COTANGENT_SETS}
+
+
+@functools.lru_cache(maxsize=None)
+def yardstick_grad(inverse, kind, window, n=N_BATCH):
+    """The backward yardstick on batch(kind, window): the batch maxima of the figures of fp64 autograd evaluated at the matrix recomposed
+    from LAPACK's fp32 QR factors (gx.recomposed32), for both cotangent sets; and the fp64 gradients and conditionings themselves."""
+    M, R = batch(kind, window, n), rotations(n)
+    gR, gl = cotangents(n)
+    k, kl = gx.grad_conditioning(M, R, inverse)
+    want = references_grad(M, R, gR, gl, inverse)
+    fig = figures_grad(R, references_grad(M, R, gR, gl, inverse, at=gx.recomposed32(M)), want, k, kl)
+    vac = U23 * yardstick(inverse, kind, window, n)["kj"] > gx.LDJ_VACUOUS
+    for a in (k, kl, vac) + tuple(x for s in COTANGENT_SETS for x in want[s]):
+        a.setflags(write=False)
+    return {"grad": {s: fig[s][0].max() for s in COTANGENT_SETS}, "tan": {s: fig[s][1].max() for s in COTANGENT_SETS},
+            "want": want, "k": k, "kl": kl, "vacuous": vac}
+
+
+def strictest_grad(inverse, key, cset):
+    return min(yardstick_grad(inverse, k, w)[key][cset] for k, w in CASES)
+
+
+def backward_gates(inverse, M, R, gR, gl, want, want_rot, k, kl, y_grad, y_tan):
+    """Per-sample ABSOLUTE gates of dL/dM and of the tangent part of dL/dR: twice the yardstick's figure, turned back into an error
+    (x 2^-23 (k max|rotation part| + kl max|ldj part|), the denominators of gx.grad_figure), plus 4 x 2^-23 times the size of the terms of
+    the fp32 products the header forms.
+
+    Why the second part (the argument of tests/test_gs3_host.py backward_gates).  The yardstick is fp64 autograd at a matrix 2^-23 away:
+    it carries the conditioning of the gradient and none of the roundings an fp32 evaluation makes on the way.  Those are absolute errors
+    of the size of what is multiplied, not of the result.  Where the reference gradient is small by cancellation (a cotangent nearly
+    normal to what the layer can move) the figure alone, which divides by max|reference|, would hold the header to a relative accuracy no
+    fp32 evaluation has.  The sizes of this layer's terms are derived in gx.product_terms."""
+    tM, tR = gx.product_terms(M, R, gR, gl, inverse)
+    den_M = k * gx._maxabs(want_rot[0]) + kl * gx._maxabs(want[0] - want_rot[0])
+    den_R = k * gx._maxabs(gx.tangent(R, want_rot[1])) + kl * gx._maxabs(gx.tangent(R, want[1]) - gx.tangent(R, want_rot[1]))
+    return 2 * y_grad * U23 * den_M + 4 * U23 * tM, 2 * y_tan * U23 * den_R + 4 * U23 * tR
+
+
+def backward_errors(R, got, want):
+    return gx._maxabs(got[0].astype(np.float64) - want[0]), gx._maxabs(gx.tangent(R, got[1]) - gx.tangent(R, want[1]))
+
+
+@pytest.mark.parametrize("kind", gx.KINDS)
+def test_gradient_conditioning_is_checked_by_a_perturbation(kind):
+    """gx.grad_conditioning's derivation, checked: fp64 autograd at M (1 + 2^-23 U(-1, 1)), one rounding of every entry, shows figures of
+    O(1) in both cotangent sets, both windows, both passes.  Thirty-six entries perturbed by 2^-23 |M_ij| make |E|_2 <= 2^-23 |M|_F <=
+    sqrt(6) 2^-23 |M|_2, and the derivation's constants are 1 (rotation part) and 3 + 3 (ldj part): under 6 sqrt(6) < 15.  The figures
+    divide by the size of the reference gradient itself, which a cotangent nearly normal to what the layer can move (three directions
+    of nine) makes small by cancellation without making the perturbation's effect small: a tail no conditioning of the input removes
+    (tests/test_gs3_host.py counts the same samples as "over twice"; the gates carry them by their product terms).  So the bound is
+    asked of the 99.9th percentile of each cell and the maximum is printed.  The conditioning is a product of worst cases (cond(M) for a
+    solve, cond(J) + rho for a determinant), which a random perturbation rarely meets, so the medians are small (down to 0.003 on the
+    inverse pass); what is asked from below is that the worst sample of each cell comes within a factor ten of the bound, so that it is
+    not an over-estimate by orders of magnitude in any cell.  The yardstick's own maxima are printed beside them."""
+    for window in gx.WINDOWS:
+        for inverse in PASSES:
+            M, R, y = batch(kind, window), rotations(), yardstick_grad(inverse, kind, window)
+            gR, gl = cotangents()
+            fig = figures_grad(R, references_grad(M, R, gR, gl, inverse, at=gx.perturbed(M)), y["want"], y["k"], y["kl"])
+            for s in COTANGENT_SETS:
+                q = [np.quantile(f, 0.999) for f in fig[s]]
+                md = [np.median(f) for f in fig[s]]
+                print(f"{kind}, {window}, inverse {inverse}, cotangents {s}: figure of a 2^-23 perturbation, median / 99.9th percentile / max: dL/dM {md[0]:.3f} / {q[0]:.2f} / "
+                      f"{fig[s][0].max():.2f}, dL/dR tangent {md[1]:.3f} / {q[1]:.2f} / {fig[s][1].max():.2f}; the yardstick's maxima {y['grad'][s]:.2f}, {y['tan'][s]:.2f}")
+                assert q[0] < 15 and q[1] < 15 and fig[s][0].max() > 0.1 and fig[s][1].max() > 0.1, (window, inverse, s, q, md)
+                assert np.isfinite(y["grad"][s]) and np.isfinite(y["tan"][s])
+
+
+def test_gradient_reference_agrees_with_a_finite_difference():
+    M, R = batch("singular_values", "realistic")[:4].astype(np.float64), rotations()[:4].astype(np.float64)
+    gR, gl = (a[:4] for a in cotangents())
+    E = np.random.default_rng(4).standard_normal((4, 6, 6))
+    for inverse in PASSES:
+        g = gx.layer_grad64(M, R, gR, gl, inverse)[0]
+
+        def loss(A):
+            Ro, l = gx.gs36_64(A, R, inverse)
+            return (Ro * gR).sum((-1, -2)) + l * gl
+        h = 1e-6 * np.abs(M).max((-1, -2), keepdims=True)
+        fd = (loss(M + h * E) - loss(M - h * E)) / (2 * h[:, 0, 0])
+        assert (np.abs(fd - (g * E).sum((-1, -2))) < 1e-4 * np.abs(g * E).sum((-1, -2))).all(), (inverse, fd, (g * E).sum((-1, -2)))
+
+
+@pytest.mark.parametrize("kind,window", CASES)
+@pytest.mark.parametrize("inverse", PASSES)
+def test_every_sample_backward_is_the_fp64_gradient(h36, inverse, kind, window):
+    """cond_gs36_backward, all 20 000 matrices of each family and scale window, both passes, uniform rotations, random normal cotangents,
+    two sets: g_ldj = 0 and random g_ldj.  dL/dM and the tangent part of dL/dR per sample against fp64 autograd of the oracle's layer, each
+    within 2x the figure fp64 autograd shows at the matrix recomposed from LAPACK fp32's QR factors, plus the 4 x 2^-23 of the fp32
+    products (backward_gates).  No sample is left out of either set (the issue allows leaving the vacuous-ldj samples out of the second;
+    the gates hold with them in); the share of samples whose forward ldj gate is vacuous is printed and must not exceed 0.12.  The
+    gradient is finite on every sample: the forward returns a rotation on all of them."""
+    M, R, y = batch(kind, window), rotations(), yardstick_grad(inverse, kind, window)
+    gR, gl = cotangents()
+    got = {"rot": backward36(h36, M, R, gR, np.zeros_like(gl), inverse), "all": backward36(h36, M, R, gR, gl, inverse)}
+    fig = figures_grad(R, got, y["want"], y["k"], y["kl"])
+    share = float(y["vacuous"].mean())
+    for s in COTANGENT_SETS:
+        eM, eR = backward_errors(R, got[s], y["want"][s])
+        gate_M, gate_R = backward_gates(inverse, M, R, gR, gl if s == "all" else np.zeros_like(gl), y["want"][s], y["want"]["rot"], y["k"], y["kl"],
+                                        y["grad"][s], y["tan"][s])
+        g, t = fig[s]
+        print(f"inverse {inverse}, {kind}, {window}, cotangents {s}: header / yardstick: dL/dM {g.max():.2f} / {y['grad'][s]:.2f} ({int((g > 2 * y['grad'][s]).sum())} over twice), "
+              f"dL/dR tangent {t.max():.2f} / {y['tan'][s]:.2f} ({int((t > 2 * y['tan'][s]).sum())} over twice); error / gate max {np.max(eM / gate_M):.3f}, {np.max(eR / gate_R):.3f}; "
+              f"vacuous ldj gates {share:.4f}")
+        assert np.isfinite(got[s][0]).all() and np.isfinite(got[s][1]).all()
+        assert (eM <= gate_M).all(), (s, int(np.argmax(eM / gate_M)), np.max(eM / gate_M), int((eM > gate_M).sum()))
+        assert (eR <= gate_R).all(), (s, int(np.argmax(eR / gate_R)), np.max(eR / gate_R), int((eR > gate_R).sum()))
+    assert share <= VACUOUS_MAX
+
+
+@pytest.mark.parametrize("inverse", PASSES)
+def test_in_domain_edges_backward(h36, inverse):
+    """The named in-domain edges against the strictest yardstick of the twenty cells, both cotangent sets."""
+    names, M, R, inside = gx.edges(inverse)
+    names, M, R = np.array(names)[inside], M[inside], R[inside]
+    n = len(M)
+    gR, gl = (a[:n] for a in cotangents())
+    k, kl = gx.grad_conditioning(M, R, inverse)
+    want = references_grad(M, R, gR, gl, inverse)
+    got = {"rot": backward36(h36, M, R, gR, np.zeros_like(gl), inverse), "all": backward36(h36, M, R, gR, gl, inverse)}
+    for s in COTANGENT_SETS:
+        eM, eR = backward_errors(R, got[s], want[s])
+        gate_M, gate_R = backward_gates(inverse, M, R, gR, gl if s == "all" else np.zeros_like(gl), want[s], want["rot"], k, kl,
+                                        strictest_grad(inverse, "grad", s), strictest_grad(inverse, "tan", s))
+        print(f"inverse {inverse}, in-domain edges, cotangents {s}, dL/dM error / gate:", dict(zip(names, np.round(eM / gate_M, 3))))
+        print("  dL/dR tangent error / gate:", dict(zip(names, np.round(eR / gate_R, 3))))
+        assert (eM <= gate_M).all(), [(n_, v) for n_, v in zip(names, eM / gate_M) if not v <= 1]
+        assert (eR <= gate_R).all(), [(n_, v) for n_, v in zip(names, eR / gate_R) if not v <= 1]
+
+
+def test_backward_power_of_two_scaling_is_exact(h36):
+    """dL/dM(2^k M) = 2^-k dL/dM(M) bit for bit and dL/dR unchanged, k = +-30, +-60, both passes, random g_ldj."""
+    n = 2000
+    R = rotations(n)
+    gR, gl = (a[:n] for a in cotangents())
+    for kind in ("near_identity", "singular_values"):
+        M = batch(kind, "realistic")[:n]
+        for inverse in PASSES:
+            gM, gRin = backward36(h36, M, R, gR, gl, inverse)
+            assert np.isfinite(gM).all() and np.isfinite(gRin).all()
+            for k in (-60, -30, 30, 60):
+                gMk, gRink = backward36(h36, np.ldexp(M, k), R, gR, gl, inverse)
+                assert np.array_equal(gMk, np.ldexp(gM, -k)) and np.array_equal(gRink, gRin), (kind, inverse, k, int((gMk != np.ldexp(gM, -k)).any((-1, -2)).sum()))
+
+
+@pytest.mark.parametrize("inverse", PASSES)
+def test_backward_refuses_where_the_forward_refuses(h36, inverse):
+    """A finite gradient never stands beside a NaN forward.  The named out-of-domain rows among in-domain rows: the rows asked to be NaN
+    (gx.ASKED_NAN; two equal rows on the inverse pass) have NaN in ALL of gM and gRin, every other row is bit-equal to what it is in a
+    batch without them.  Then 2 000 random matrices each of cond 1e4 .. 1e8 and of exact rank 5 at scales 10^U(-12,12), and 2 000 each
+    with the lower rows within 1e-5 .. 1e-7 of the upper rows: gM and gRin are NaN throughout exactly on the rows whose forward is NaN,
+    and hold no NaN elsewhere.  Last the ends of the fp32 range (gx.EXTREME_SCALES): inside the strictest in-domain gate."""
+    names, M, R, inside = gx.edges(inverse)
+    n = len(M)
+    gR, gl = (a[:n] for a in cotangents())
+    gM, gRin = backward36(h36, M, R, gR, gl, inverse)
+    Q, l = apply36(h36, M, R, inverse)
+    fwd_nan = np.isnan(Q).all((-1, -2)) & np.isnan(l)
+    all_nan = np.isnan(gM).all((-1, -2)) & np.isnan(gRin).all((-1, -2))
+    any_nan = np.isnan(gM).any((-1, -2)) | np.isnan(gRin).any((-1, -2))
+    print(f"inverse {inverse}: NaN gradient rows:", [nm for nm, b in zip(names, all_nan) if b])
+    for nm in gx.ASKED_NAN + (("two_equal_rows",) if inverse else ()):
+        assert all_nan[names.index(nm)], nm
+    assert np.array_equal(all_nan, fwd_nan) and np.array_equal(any_nan, all_nan), (list(zip(names, fwd_nan, all_nan, any_nan)))
+    gM_in, gRin_in = backward36(h36, M[inside], R[inside], gR[inside], gl[inside], inverse)
+    assert np.array_equal(gM[inside], gM_in) and np.array_equal(gRin[inside], gRin_in) and np.isfinite(gM_in).all() and np.isfinite(gRin_in).all()
+    rng = np.random.default_rng(12)
+    n = 2000
+    Rn = rotations(n)
+    gR, gl = (a[:n] for a in cotangents())
+
+    def same_rows(Mc, tag):
+        Q, l = apply36(h36, Mc, Rn, inverse)
+        gM, gRin = backward36(h36, Mc, Rn, gR, gl, inverse)
+        fwd_nan = np.isnan(Q).all((-1, -2)) & np.isnan(l)
+        all_nan = np.isnan(gM).all((-1, -2)) & np.isnan(gRin).all((-1, -2))
+        any_nan = np.isnan(gM).any((-1, -2)) | np.isnan(gRin).any((-1, -2))
+        print(f"inverse {inverse}, {tag}: forward NaN on {int(fwd_nan.sum())} of {n}, gradient NaN on {int(all_nan.sum())}")
+        assert np.array_equal(all_nan, fwd_nan) and np.array_equal(any_nan, all_nan), (tag, int((all_nan != fwd_nan).sum()), int((any_nan != all_nan).sum()))
+    U, V = np.linalg.qr(rng.standard_normal((n, 6, 6)))[0], np.linalg.qr(rng.standard_normal((n, 6, 6)))[0]
+    for c in (1e4, 1e5, 1e6, 1e7, 1e8, np.inf):
+        s = np.concatenate([np.ones((n, 1)), 10.0 ** rng.uniform(-3, 0, (n, 4)), np.full((n, 1), 1 / c)], 1) * 10.0 ** rng.uniform(-12, 12, (n, 1))
+        same_rows(np.einsum("nik,nk,njk->nij", U, s, V).astype(np.float32), f"cond {c:g}")
+    base = np.eye(6) + 0.2 * rng.standard_normal((n, 6, 6))
+    for eps in (1e-5, 1e-6, 1e-7):
+        Mt = base.copy()
+        Mt[:, 3:] = Mt[:, :3] * (1 + eps * rng.standard_normal((n, 3, 6)))
+        same_rows(Mt.astype(np.float32), f"lower rows within {eps:g} of the upper")
+    for scale in gx.EXTREME_SCALES:
+        Ms = (base * scale).astype(np.float32)
+        good = gx.in_domain(Ms)
+        Mg, Rg, gRg, glg = Ms[good], Rn[good], gR[good], gl[good]
+        k, kl = gx.grad_conditioning(Mg, Rg, inverse)
+        want = references_grad(Mg, Rg, gRg, glg, inverse)
+        got = backward36(h36, Mg, Rg, gRg, glg, inverse)
+        eM, eR = backward_errors(Rg, got, want["all"])
+        gate_M, gate_R = backward_gates(inverse, Mg, Rg, gRg, glg, want["all"], want["rot"], k, kl, strictest_grad(inverse, "grad", "all"),
+                                        strictest_grad(inverse, "tan", "all"))
+        print(f"inverse {inverse}, scale {scale:g}: error / gate max {np.max(eM / gate_M):.3f}, {np.max(eR / gate_R):.3f}")
+        assert good.mean() > 0.9 and np.isfinite(got[0]).all() and (eM <= gate_M).all() and (eR <= gate_R).all(), (scale, np.max(eM / gate_M), np.max(eR / gate_R))
