@@ -572,6 +572,74 @@ int rnf_grid_fit(const RnfGridFit *fit);
 /* The workspace rnf_grid_fit requires for the same struct (the pointers are not read); 0 when struct_bytes, g or Q are out of range. */
 size_t rnf_grid_fit_workspace_bytes(const RnfGridFit *fit);
 
+/* The chart of a grid cell (csrc/grid_sample.h): point k is the rotation at (u0, u1, u2) in [0, 1]^3 of the cell of row rows[k] of the
+ * level's grid (the cells of rnf_so3_grid_locate).  Row r = t * npix + p: ring2nest(p) gives (face, ix, iy) at nside = 2^level;
+ *   x = (ix + u0) / nside, y = (iy + u1) / nside, jr = jrll(face) - x - y;
+ *   jr < 1 (north cap): nr = jr, z = 1 - nr^2 / 3;  jr > 3 (south cap): nr = 4 - jr, z = nr^2 / 3 - 1;  else nr = 1, z = (2 - jr) 2 / 3;
+ *   phi = (pi / 4) ((jpll(face) nr + x - y) mod 8) / nr;  tau = (t + u2 - 1/2) 2 pi / (6 nside);  rot = Rx(phi) Rz(theta) Rx(tau) O
+ * (HEALPix's continuous face-to-sphere map, Gorski et al. 2005; sin(theta) = sqrt(tmp (2 - tmp)), tmp = nr^2 / 3, in the caps).  That map
+ * is equal-area and the tilt is linear, so uniform u are Haar-uniform in the cell; u = (1/2, 1/2, 1/2) is the grid's own row to rounding.
+ * fp64 inside, one rounding per entry at the store, one thread per point.  A row outside 0..72 * 8^level - 1 or a u outside [0, 1] (NaN
+ * included) gives nine NaNs and no access.  A point on a cell's boundary (u = 0 or 1, or within rounding of it) may locate to the
+ * neighbouring cell.  n = 0 is a no-op.  Stream-ordered, no host synchronisation, capturable. */
+typedef struct RnfGridCellPoints {
+    size_t struct_bytes;        /* sizeof(RnfGridCellPoints); any other value is refused (header and library differ) */
+    int32_t level;              /* 0..6 */
+    const float *offset;        /* dev float[9] row-major, or NULL (identity) */
+    const int64_t *rows;        /* dev int64[n] */
+    const float *u;             /* dev float[n][3] */
+    int64_t n;                  /* points, 0..2^36 */
+    float *rot_out;             /* dev float[n][9] row-major */
+    void *stream;
+} RnfGridCellPoints;
+int rnf_so3_grid_cell_points(const RnfGridCellPoints *points);
+
+/* Draws from g posteriors on grid rows (csrc/grid_sample.h).  Image b's masses are rnf_grid_credible's: W_i = rint(expf(lp_i - m) 2^S),
+ * m the image's maximum, S = 62 - ceil(log2 Q); C is their inclusive prefix sum in row order and T = C_{Q-1} <= 2^62.  A target v in
+ * [0, T) draws the row i with C_{i-1} <= v < C_i, so a row with W_i = 0 (lp_i = -inf, or more than (63 - ceil(log2 Q)) ln 2 below m: 26.3 at level 6) is never
+ * drawn.  r64(k, b, s) = (word0 << 32) | word1 of Philox4x32-10 with key (seed low, seed high) on the counter (k, b low, b high, s),
+ * k = draw_base + the draw's index in the call, b = image_base + the image's index in the call; mulhi = the high 64 bits of a product:
+ *   RNF_GRID_SAMPLE_MULTINOMIAL  v_k = mulhi(r64(k, b, 0), T): independent draws;
+ *   RNF_GRID_SAMPLE_SYSTEMATIC   a = mulhi(r64(0, b, 0), T), N = draws_total, T = q N + r: v_k = k q + (k r + a) / N (integer division)
+ *                                = floor((k T + a) / N): one offset, N evenly spaced targets, |count_i - N p_i| < 1, ascending in k.
+ * rot_out (needs level >= 0, Q = 72 * 8^level): with jitter the drawn row goes through rnf_so3_grid_cell_points' chart at
+ * u_j = (word_j of the counter (k, b, 1) + 1/2) / 2^32, j = 0..2 (fp64) -- Haar-uniform within the drawn cell, so the draws follow the
+ * piecewise-constant density; without jitter it is the row of rnf_so3_healpix_grid, bit for bit.  level = -1: any Q, rows only.
+ * An image with a NaN, a maximum of +inf or no finite value (T = 0): index -1, target 0, total 0, NaN rotations, for that image alone.
+ * Cost: one pass over the g Q values for the maximum, one for the sums of chunks of 64 rows, a scan of Q / 64 sums per image, then
+ * O(log Q) + at most 64 masses per draw; every call pays the passes again, so tile the draws coarsely.  Deterministic: integer sums only, block
+ * counts depend on Q alone, a draw's numbers on (seed, k, b) alone -- bit-identical from run to run, whatever images share a call and
+ * however the draws are tiled.  Stream-ordered, no host synchronisation, capturable (the seed is an argument, so a replay repeats it). */
+#define RNF_GRID_SAMPLE_MULTINOMIAL 0
+#define RNF_GRID_SAMPLE_SYSTEMATIC 1
+typedef struct RnfGridSample {
+    size_t struct_bytes;        /* sizeof(RnfGridSample); any other value is refused (header and library differ) */
+    const float *logp;          /* dev float[g][Q] */
+    int64_t Q;                  /* 1..2^26 */
+    int32_t g;                  /* images, 1..65535 */
+    int32_t level;              /* -1, or 0..6 with Q == 72 * 8^level */
+    int64_t draws;              /* per image in this call, >= 0 */
+    int64_t draw_base;          /* global index of the call's first draw, >= 0; draw_base + draws <= draws_total */
+    int64_t draws_total;        /* N, 1..2^30: the draws per image over all calls (systematic spacing) */
+    int64_t image_base;         /* global index of the call's first image, >= 0 */
+    int32_t method;             /* RNF_GRID_SAMPLE_* */
+    int32_t jitter;             /* 0 or 1; read with rot_out alone */
+    uint64_t seed;
+    const float *offset;        /* dev float[9] row-major, or NULL (identity); read with rot_out alone */
+    int64_t *index_out;         /* dev int64[g][draws] */
+    uint64_t *target_out;       /* dev uint64[g][draws], or NULL: v_k */
+    uint64_t *total_out;        /* dev uint64[g], or NULL: T */
+    float *rot_out;             /* dev float[g][draws][9], or NULL */
+    /* dev scratch, 8-byte aligned, of at least rnf_grid_sample_workspace_bytes(this struct) bytes =
+     * g * (16 min(ceil(Q / 2048), 2048) + 8 ceil(Q / 64) + 20) rounded up to 16: the maximum's partials and the chunk prefix */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfGridSample;
+int rnf_grid_sample(const RnfGridSample *sample);
+/* The workspace rnf_grid_sample requires for the same struct (the pointers are not read); 0 when struct_bytes, g or Q are out of range. */
+size_t rnf_grid_sample_workspace_bytes(const RnfGridSample *sample);
+
 /* Pairwise sums of isotropic matrix-Fisher kernels between two sets of rotations (csrc/so3_kernel_sum.h): the kernel density estimate
  * on SO(3) and the prediction step of a Bayes filter on the SO(3) grid.  With w_g = softmax(log_weights[g]) over the n centres (w = 1/n
  * without log-weights),

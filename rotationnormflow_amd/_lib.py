@@ -72,6 +72,24 @@ class GridFit(_Pass):
                 ("stats_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class GridCellPoints(_Pass):
+    """RnfGridCellPoints (include/rnf_hip.h): the chart of SO(3) grid cells, from (row, u in [0,1]^3) to a rotation inside the cell."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("offset", C.c_void_p), ("rows", C.c_void_p), ("u", C.c_void_p),
+                ("n", C.c_int64), ("rot_out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class GridSample(_Pass):
+    """RnfGridSample (include/rnf_hip.h): draws of grid rows, and of rotations inside their cells, from posteriors on the grid."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("logp", C.c_void_p), ("Q", C.c_int64), ("g", C.c_int32), ("level", C.c_int32),
+                ("draws", C.c_int64), ("draw_base", C.c_int64), ("draws_total", C.c_int64), ("image_base", C.c_int64), ("method", C.c_int32),
+                ("jitter", C.c_int32), ("seed", C.c_uint64), ("offset", C.c_void_p), ("index_out", C.c_void_p), ("target_out", C.c_void_p),
+                ("total_out", C.c_void_p), ("rot_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+GRID_SAMPLE_METHODS = {"multinomial": 0, "systematic": 1}   # RNF_GRID_SAMPLE_*
+
+
 class So3KernelSum(_Pass):
     """RnfSo3KernelSum (include/rnf_hip.h): pairwise sums of matrix-Fisher kernels between two sets of rotations."""
     _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("queries", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64),
@@ -204,6 +222,9 @@ _SIGNATURES = {
     "rnf_so3_grid_locate": (C.c_int, [C.POINTER(GridLocate)]),
     "rnf_grid_fit": (C.c_int, [C.POINTER(GridFit)]),
     "rnf_grid_fit_workspace_bytes": (C.c_size_t, [C.POINTER(GridFit)]),
+    "rnf_so3_grid_cell_points": (C.c_int, [C.POINTER(GridCellPoints)]),
+    "rnf_grid_sample": (C.c_int, [C.POINTER(GridSample)]),
+    "rnf_grid_sample_workspace_bytes": (C.c_size_t, [C.POINTER(GridSample)]),
     "rnf_so3_kernel_sum": (C.c_int, [C.POINTER(So3KernelSum)]),
     "rnf_so3_kernel_sum_workspace_bytes": (C.c_size_t, [C.POINTER(So3KernelSum)]),
     "rnf_so3_kernel_moments": (C.c_int, [C.POINTER(So3KernelMoments)]),

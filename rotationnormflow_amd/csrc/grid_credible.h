@@ -24,6 +24,7 @@
 #include <cstdint>
 
 #include "grid_beam.h"
+#include "grid_mass.h"                            // u64, fixed_point_shift, no_sets, fixed_mass
 #include "grid_modes.h"
 
 namespace rnf {
@@ -40,19 +41,10 @@ constexpr long long MAX_Q = 1LL << 26;
 constexpr long long ROWS_PER_BLOCK = 8192;
 constexpr long long MAX_BLOCKS = 512;
 
-typedef unsigned long long u64;
-
 // blocks of one image in every pass: a function of Q alone (the determinism rule above)
 inline long long blocks_for(long long Q) {
     const long long b = (Q + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     return b < MAX_BLOCKS ? b : MAX_BLOCKS;
-}
-
-// S = 62 - ceil(log2 Q): Q * 2^S <= 2^62, so T = sum W_i <= Q * 2^S cannot overflow (W_i <= 2^S because expf(lp_i - m) <= 1)
-inline int fixed_point_shift(long long Q) {
-    int c = 0;
-    while ((1LL << c) < Q) ++c;
-    return 62 - c;
 }
 
 struct Levels {                                   // the levels alpha_j, by value in the kernel arguments
@@ -103,13 +95,6 @@ inline Workspace carve(void *base, long long Q, int g, int J, int G) {
     w.query_count = reinterpret_cast<unsigned *>(p + query_count);
     w.max_value = reinterpret_cast<float *>(p + max_value);
     return w;
-}
-
-// the image has no set to report: a NaN or +inf maximum, or no finite value at all
-__device__ __forceinline__ bool no_sets(float m) { return !(fabsf(m) < INFINITY); }
-
-__device__ __forceinline__ u64 fixed_mass(float lp, float m, double scale) {
-    return (u64)__double2ull_rn((double)expf(lp - m) * scale);
 }
 
 // the query slots pass 0 is built with: the smallest of 0, 1 (grid_pose_credible's ground truth), 4 and 16 that holds G

@@ -31,6 +31,7 @@
 #include "grid_beam.h"
 #include "grid_credible.h"
 #include "grid_locate.h"
+#include "grid_sample.h"
 #include "so3_kernel_sum.h"
 #include "so3_kernel_moments.h"
 #include "so3_angle_cdf.h"
@@ -1659,6 +1660,87 @@ extern "C" int rnf_grid_fit(const RnfGridFit *p) {
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(gl::grid_fit_final_kernel, dim3(p->g), dim3(gl::THREADS), 0, s, (const gl::FitPart *)w.part, nb, Q,
                        (const float *)w.max_value, p->stats_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The chart of a grid cell (csrc/grid_sample.h): one thread per point.
+extern "C" int rnf_so3_grid_cell_points(const RnfGridCellPoints *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridCellPoints))
+        return fail("RnfGridCellPoints.struct_bytes does not match the library's %zu", sizeof(RnfGridCellPoints));
+    if (p->level < 0 || p->level > gsa::MAX_LEVEL) return fail("RnfGridCellPoints.level=%d outside 0..%d", p->level, gsa::MAX_LEVEL);
+    if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridCellPoints.n=%lld outside 0..2^36", (long long)p->n);
+    if (p->n == 0) return 0;
+    if (!p->rows || !p->u || !p->rot_out) return fail("RnfGridCellPoints: null rows, u or rot_out");
+    long long blocks = (p->n + gsa::THREADS - 1) / gsa::THREADS;
+    if (blocks > (1LL << 20)) blocks = 1LL << 20;
+    hipLaunchKernelGGL(gsa::so3_grid_cell_points_kernel, dim3((unsigned)blocks), dim3(gsa::THREADS), 0, reinterpret_cast<hipStream_t>(p->stream),
+                       (int)p->level, (long long)p->n, (const long long *)p->rows, p->u, p->offset, p->rot_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Draws from grid posteriors (csrc/grid_sample.h): the row maximum by grid_modes.h's arg-max pass, the chunk sums, their scan, the draws.
+static int grid_sample_check(const RnfGridSample *p) {
+    if (!p || p->struct_bytes != sizeof(RnfGridSample))
+        return fail("RnfGridSample.struct_bytes does not match the library's %zu", sizeof(RnfGridSample));
+    if (p->g < 1 || p->g > 65535) return fail("RnfGridSample.g=%d outside 1..65535", p->g);
+    if (p->Q < 1 || p->Q > gsa::MAX_Q) return fail("RnfGridSample.Q=%lld outside 1..2^26", (long long)p->Q);
+    return 0;
+}
+
+extern "C" size_t rnf_grid_sample_workspace_bytes(const RnfGridSample *p) {
+    if (grid_sample_check(p)) return 0;
+    return gsa::carve(nullptr, p->Q, p->g, gm::blocks_for(p->Q)).bytes;
+}
+
+extern "C" int rnf_grid_sample(const RnfGridSample *p) {
+    if (grid_sample_check(p)) return 1;
+    static_assert(sizeof(gm::ArgPart) == 16, "csrc/grid_sample.h carves 16 bytes per arg-max partial");
+    static_assert(gsa::MULTINOMIAL == RNF_GRID_SAMPLE_MULTINOMIAL && gsa::SYSTEMATIC == RNF_GRID_SAMPLE_SYSTEMATIC,
+                  "csrc/grid_sample.h and include/rnf_hip.h disagree on the methods");
+    if (p->level < -1 || p->level > gsa::MAX_LEVEL) return fail("RnfGridSample.level=%d outside -1..%d", p->level, gsa::MAX_LEVEL);
+    if (p->level >= 0 && p->Q != (72LL << (3 * p->level)))
+        return fail("RnfGridSample.Q=%lld is not the %lld rows of level %d", (long long)p->Q, 72LL << (3 * p->level), p->level);
+    if (p->rot_out && p->level < 0) return fail("RnfGridSample.rot_out needs a grid level (level=-1 draws rows only)");
+    if (p->method != RNF_GRID_SAMPLE_MULTINOMIAL && p->method != RNF_GRID_SAMPLE_SYSTEMATIC)
+        return fail("RnfGridSample.method=%d is neither RNF_GRID_SAMPLE_MULTINOMIAL nor RNF_GRID_SAMPLE_SYSTEMATIC", p->method);
+    if (p->draws_total < 1 || p->draws_total > gsa::MAX_DRAWS)
+        return fail("RnfGridSample.draws_total=%lld outside 1..2^30", (long long)p->draws_total);
+    if (p->draws < 0 || p->draw_base < 0 || p->draws > p->draws_total || p->draw_base > p->draws_total - p->draws)
+        return fail("RnfGridSample: draws %lld..%lld outside the draws_total=%lld", (long long)p->draw_base,
+                    (long long)p->draw_base + (long long)p->draws, (long long)p->draws_total);
+    if (p->image_base < 0 || p->image_base > (1LL << 62)) return fail("RnfGridSample.image_base=%lld outside 0..2^62", (long long)p->image_base);
+    if (!p->logp) return fail("RnfGridSample: null logp");
+    if (p->draws > 0 && !p->index_out) return fail("RnfGridSample: null index_out");
+    const size_t need = rnf_grid_sample_workspace_bytes(p);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfGridSample.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_sample_workspace_bytes)", p->workspace_bytes,
+                    need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridSample.workspace must be 8-byte aligned");
+    const long long Q = p->Q, nc = gsa::chunks_for(Q);
+    const int nbm = (int)gm::blocks_for(Q), nbs = (int)gsa::sum_blocks_for(Q);
+    const gsa::Workspace w = gsa::carve(p->workspace, Q, p->g, nbm);
+    const double scale = ldexp(1.0, gc::fixed_point_shift(Q));
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
+                       (const long long *)w.max_index, (const float *)w.max_value, (gm::ArgPart *)w.max_part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
+                       w.max_index, w.max_value);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gsa::grid_sample_sum_kernel, dim3(nbs, p->g), dim3(gsa::THREADS), 0, s, p->logp, Q, nc, scale, (const float *)w.max_value,
+                       w.prefix);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gsa::grid_sample_scan_kernel, dim3(p->g), dim3(gsa::SCAN_THREADS), 0, s, nc, (const float *)w.max_value, w.prefix, w.total);
+    HIP_TRY(hipGetLastError());
+    if (p->draws == 0 && !p->total_out) return 0;
+    long long blocks = (p->draws + gsa::THREADS - 1) / gsa::THREADS;
+    blocks = blocks < 1 ? 1 : blocks > (1LL << 22) ? (1LL << 22) : blocks;
+    hipLaunchKernelGGL(gsa::grid_sample_draw_kernel, dim3((unsigned)blocks, p->g), dim3(gsa::THREADS), 0, s, p->logp, Q, nc, scale, (int)p->level,
+                       (long long)p->draws, (long long)p->draw_base, (long long)p->draws_total, (long long)p->image_base, (int)p->method,
+                       (int)(p->jitter != 0), (gsa::u64)p->seed, p->offset, (const float *)w.max_value, (const gsa::u64 *)w.prefix,
+                       (const gsa::u64 *)w.total, (long long *)p->index_out, (gsa::u64 *)p->target_out, (gsa::u64 *)p->total_out, p->rot_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

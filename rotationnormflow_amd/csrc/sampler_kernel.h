@@ -9,28 +9,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "philox.h"
 #include "so3_math.h"
 
 namespace rnf {
-
-struct Philox {
-    unsigned k0, k1;
-    __device__ __forceinline__ void round(unsigned (&c)[4], unsigned a, unsigned b) const {
-        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ a, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ b, n3 = (unsigned)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    }
-    __device__ __forceinline__ void operator()(unsigned (&c)[4]) const {
-        unsigned a = k0, b = k1;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            round(c, a, b);
-            a += 0x9E3779B9u;
-            b += 0xBB67AE85u;
-        }
-    }
-};
 
 __device__ __forceinline__ float u01(unsigned x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0, 1)
 

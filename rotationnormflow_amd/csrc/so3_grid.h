@@ -22,7 +22,7 @@ namespace so3g {
 
 constexpr int MAX_LEVEL = 8;
 
-__device__ inline long long isqrt_ll(long long v) {
+__host__ __device__ inline long long isqrt_ll(long long v) {
     long long s = (long long)sqrt((double)v);
     while (s * s > v) --s;
     while ((s + 1) * (s + 1) <= v) ++s;
@@ -30,7 +30,7 @@ __device__ inline long long isqrt_ll(long long v) {
 }
 
 // row r of the level-`level` grid times O (o: row-major fp64) into dst[9]
-__device__ __forceinline__ void grid_row(int level, long long r, const double *o, float *dst) {
+__host__ __device__ __forceinline__ void grid_row(int level, long long r, const double *o, float *dst) {
     const long long nside = 1LL << level, npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1);
     const double pi = M_PI, tilt_step = 2.0 * M_PI / (double)(6LL << level);
     const long long t = r / npix, p = r - t * npix;
@@ -67,37 +67,39 @@ __device__ __forceinline__ void grid_row(int level, long long r, const double *o
             dst[row * 3 + col] = (float)(a[row * 3] * o[col] + a[row * 3 + 1] * o[3 + col] + a[row * 3 + 2] * o[6 + col]);
 }
 
-__device__ __forceinline__ void load_offset(const float *offset, double *o) {
+__host__ __device__ __forceinline__ void load_offset(const float *offset, double *o) {
     for (int c = 0; c < 9; ++c) o[c] = (c % 4 == 0) ? 1.0 : 0.0;
     if (offset)
         for (int c = 0; c < 9; ++c) o[c] = (double)offset[c];
 }
 
+#if defined(__HIPCC__) && !defined(RNF_SO3G_HOST_ONLY)     // the host builds of the tests define it: no device code to link
 __global__ void so3_healpix_grid_kernel(int level, long long rows, const float *offset, float *out) {
     double o[9];
     load_offset(offset, o);
     for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x)
         grid_row(level, r, o, out + r * 9);
 }
+#endif  // __HIPCC__ && !RNF_SO3G_HOST_ONLY
 
 // HEALPix face tables of Gorski et al. 2005: jrll = {2,2,2,2,3,3,3,3,4,4,4,4}, jpll = {1,3,5,7,0,2,4,6,1,3,5,7}
-__device__ __forceinline__ long long jrll(long long f) { return 2 + (f >> 2); }
-__device__ __forceinline__ long long jpll(long long f) { return 2 * (f & 3) + ((f >> 2) != 1); }
+__host__ __device__ __forceinline__ long long jrll(long long f) { return 2 + (f >> 2); }
+__host__ __device__ __forceinline__ long long jpll(long long f) { return 2 * (f & 3) + ((f >> 2) != 1); }
 
-__device__ __forceinline__ long long spread_bits(long long v) {           // bit b -> bit 2b (v < 2^16)
+__host__ __device__ __forceinline__ long long spread_bits(long long v) {           // bit b -> bit 2b (v < 2^16)
     long long r = 0;
     for (int b = 0; b < 16; ++b) r |= ((v >> b) & 1) << (2 * b);
     return r;
 }
 
-__device__ __forceinline__ long long compress_bits(long long v) {         // bit 2b -> bit b
+__host__ __device__ __forceinline__ long long compress_bits(long long v) {         // bit 2b -> bit b
     long long r = 0;
     for (int b = 0; b < 16; ++b) r |= ((v >> (2 * b)) & 1) << b;
     return r;
 }
 
 // RING pixel -> NESTED pixel at nside (ring2xyf, then xyf2nest)
-__device__ inline long long ring2nest(long long nside, long long pix) {
+__host__ __device__ inline long long ring2nest(long long nside, long long pix) {
     const long long npix = 12 * nside * nside, ncap = 2 * nside * (nside - 1), nl2 = 2 * nside;
     long long iring, iphi, kshift, nr, face;
     if (pix < ncap) {
@@ -131,7 +133,7 @@ __device__ inline long long ring2nest(long long nside, long long pix) {
 }
 
 // NESTED pixel -> RING pixel at nside (nest2xyf, then xyf2ring)
-__device__ inline long long nest2ring(long long nside, long long pix) {
+__host__ __device__ inline long long nest2ring(long long nside, long long pix) {
     const long long npface = nside * nside, npix = 12 * npface, ncap = 2 * nside * (nside - 1), nl4 = 4 * nside;
     const long long face = pix / npface, ipf = pix - face * npface;
     const long long ix = compress_bits(ipf), iy = compress_bits(ipf >> 1);
@@ -157,7 +159,7 @@ __device__ inline long long nest2ring(long long nside, long long pix) {
 }
 
 // child j (0..11) of level-`level` row r (0 <= r < 72 * 8^level), as a level-(level + 1) row
-__device__ __forceinline__ long long child_row(int level, long long r, int j) {
+__host__ __device__ __forceinline__ long long child_row(int level, long long r, int j) {
     const long long nside = 1LL << level, npix = 12 * nside * nside, tilts = 12 * nside;     // the child level's 6 * 2 nside tilts
     const long long t = r / npix, p = r - t * npix;
     const long long ct = (2 * t - 1 + (j >> 2) + tilts) % tilts;
@@ -165,6 +167,7 @@ __device__ __forceinline__ long long child_row(int level, long long r, int j) {
     return ct * (4 * npix) + cp;
 }
 
+#if defined(__HIPCC__) && !defined(RNF_SO3G_HOST_ONLY)
 // one thread per child: rows_out[q * 12 + j] = child j of parents[q] (-1 for a parent outside the level's rows), rot_out (optional) its
 // row of the level-(level + 1) grid times O (the rotation of row 0 for a missing child, so that every output is a rotation)
 __global__ void so3_grid_children_kernel(int level, long long n, const long long *parents, const float *offset, long long *rows_out,
@@ -179,6 +182,7 @@ __global__ void so3_grid_children_kernel(int level, long long n, const long long
         if (rot_out) grid_row(level + 1, c < 0 ? 0 : c, o, rot_out + k * 9);
     }
 }
+#endif  // __HIPCC__ && !RNF_SO3G_HOST_ONLY
 
 }  // namespace so3g
 }  // namespace rnf

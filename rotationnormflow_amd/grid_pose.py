@@ -1,10 +1,10 @@
 """The grid analyses: evaluate a flow's log-density on the HEALPix grid over SO(3) (``utils.sd``) and reduce each image's row on the
 device -- the arg-max of ``eval.py``'s ``log_pdf`` mode (``grid_estimate_rotations``), top-k modes with their mass (``grid_pose_modes``),
-highest-density credible sets (``grid_pose_credible``), samples against the density (``grid_pose_fit``), matrix-Fisher and mixture fits
-(``grid_pose_fisher``, ``grid_pose_mixture``), the error distribution of point estimates and the Acc@theta-optimal estimate
+highest-density credible sets (``grid_pose_credible``), samples against the density (``grid_pose_fit``), draws from it
+(``grid_pose_sample``), matrix-Fisher and mixture fits (``grid_pose_fisher``, ``grid_pose_mixture``), the error distribution of point estimates and the Acc@theta-optimal estimate
 (``grid_pose_error``, ``grid_pose_ball_estimate``) and the coarse-to-fine beam search (``grid_beam_estimate_rotations``).  They share one path
-from (flow, feature, base) to log-density rows (``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_fit``, ``grid_children`` and
-``grid_beam_select`` are the reductions' entry points of the library on rows already at hand.  ``harness`` re-exports the public functions.
+from (flow, feature, base) to log-density rows (``_GridFlow``); ``grid_modes``, ``grid_credible``, ``grid_fit``, ``grid_sample``, ``grid_children``
+and ``grid_beam_select`` are the reductions' entry points of the library on rows already at hand.  ``harness`` re-exports the public functions.
 """
 from __future__ import annotations
 
@@ -713,6 +713,125 @@ def grid_fit(logp: torch.Tensor, counts: torch.Tensor) -> dict:
     out["dof"] = Q - 1
     out["z"] = (out["g_stat"] - (Q - 1)) / float(np.sqrt(2.0 * (Q - 1))) if Q > 1 else torch.full_like(n, float("nan"))
     out["n"], out["occupied"] = n.to(torch.int64), out["occupied"].to(torch.int64)
+    return out
+
+
+GRID_SAMPLE_MAX_ROWS = 1 << 26                     # rnf_grid_sample's limits (include/rnf_hip.h): level 6 fits; draws per image
+GRID_SAMPLE_MAX_DRAWS = 1 << 30
+GRID_SAMPLE_MAX_LEVEL = 6
+
+
+def _sample_seed(seed) -> int:
+    """The Philox key: ``seed``, or one drawn from torch's default generator (``MatrixFisherN._sample``'s rule), so that
+    ``torch.manual_seed`` reproduces the draws."""
+    if seed is None:
+        return int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"grid_sample: seed={seed} outside 0..2^64-1")
+    return seed
+
+
+def _sample_options(n, recursion_level, method, who: str):
+    """Argument checks shared by ``grid_sample`` and ``grid_pose_sample`` -> (n, level or -1, the method's number)."""
+    n = int(n)
+    if not 1 <= n <= GRID_SAMPLE_MAX_DRAWS:
+        raise ValueError(f"{who}: n={n} draws per image (1 to 2^30)")
+    if method not in _lib.GRID_SAMPLE_METHODS:
+        raise ValueError(f"{who}: method must be 'systematic' or 'multinomial', got {method!r}")
+    level = -1 if recursion_level is None else int(recursion_level)
+    if recursion_level is not None and not 0 <= level <= GRID_SAMPLE_MAX_LEVEL:
+        raise ValueError(f"{who}: recursion_level={recursion_level} outside 0..{GRID_SAMPLE_MAX_LEVEL} (at most 2^26 grid rows)")
+    return n, level, _lib.GRID_SAMPLE_METHODS[method]
+
+
+def _grid_sample(lp, n, level, method, jitter, off, seed, image_base):
+    """``rnf_grid_sample`` on the checked arguments: lp float32 [g,Q] contiguous on the device, off [9] or None."""
+    g, Q = lp.shape
+    dev = lp.device
+    index = torch.empty(g, n, dtype=torch.int64, device=dev)
+    target = torch.empty(g, n, dtype=torch.int64, device=dev)      # uint64 values below 2^62: the same bits as int64
+    total = torch.empty(g, dtype=torch.int64, device=dev)
+    rot = torch.empty(g, n, 3, 3, dtype=torch.float32, device=dev) if level >= 0 else None
+    args = _lib.GridSample(logp=lp.data_ptr(), Q=Q, g=g, level=level, draws=n, draw_base=0, draws_total=n, image_base=image_base, method=method,
+                           jitter=1 if jitter else 0, seed=seed, offset=off.data_ptr() if off is not None else None,
+                           index_out=index.data_ptr(), target_out=target.data_ptr(), total_out=total.data_ptr(),
+                           rot_out=rot.data_ptr() if rot is not None else None)
+    _lib.call("grid_sample", args, dev)
+    # log(sum exp(lp) / Q) from the sum the draws were made from, T = sum rint(exp(lp - m) 2^S): within 2^-23 + Q / T of the real one, and
+    # no fp64 copy of the rows
+    S = 62 - max(Q - 1, 0).bit_length()
+    log_norm = lp.max(dim=1).values.to(torch.float64) + torch.log(total.to(torch.float64)) - (S * float(np.log(2.0)) + float(np.log(Q)))
+    picked = lp.gather(1, index.clamp(min=0)).to(torch.float64) - log_norm[:, None]
+    log_prob = torch.where(index >= 0, picked, torch.full_like(picked, float("nan"))).to(torch.float32)
+    return dict(index=index, rotations=rot, log_prob=log_prob, target=target)
+
+
+def grid_sample(logp: torch.Tensor, n: int, recursion_level: int = None, method: str = "systematic", jitter: bool = True, offset=None,
+                seed: int = None) -> dict:
+    """``rnf_grid_sample``: ``n`` draws per image from the posteriors ``logp`` [g,Q] (float32, any normalisation, on the device) on grid
+    rows -- a filtered, diffused, tempered or multiplied posterior as well as a flow's.  Row i is drawn with probability
+    softmax(logp)_i (in 62-bit fixed point: the masses of ``grid_credible``; a row at -inf, or more than about 26 nats below the
+    maximum at level 6, is never drawn).  ``method``: 'multinomial', independent draws, or 'systematic', one random offset and n evenly
+    spaced targets -- every row is drawn floor(n p_i) or ceil(n p_i) times and the draws come in ascending row order (shuffle them if the
+    order matters).  With ``recursion_level`` (0..6, Q = 72 * 8^level, the grid of ``offset``) the draws are rotations: ``jitter`` places
+    each uniformly (Haar) inside its drawn cell (``sd.grid_cell_points``), so they follow the piecewise-constant density and
+    ``sd.grid_index`` gives the drawn row back; without it they are the grid's own rows, bit for bit.  ``recursion_level`` None: any
+    Q <= 2^26, rows only.  ``seed`` None: the key comes from torch's default generator, so ``torch.manual_seed`` reproduces the draws;
+    draw k of image b depends on (seed, k, b) alone.  An image with a NaN, a +inf or no finite value has index -1 and NaN elsewhere.
+    -> dict(index int64 [g,n], rotations float32 [g,n,3,3] or None, log_prob float32 [g,n] = logp[index] - log(sum exp(logp) / Q), the
+    piecewise-constant posterior's density at the draw in the measure of ``logp``, target int64 [g,n] the integers that were inverted)"""
+    who = "grid_sample"
+    if not isinstance(logp, torch.Tensor) or logp.dim() != 2:
+        raise ValueError(f"{who}: logp {tuple(getattr(logp, 'shape', ()))} (want [g,Q])")
+    n, level, method = _sample_options(n, recursion_level, method, who)
+    g, Q = logp.shape
+    if not 1 <= Q <= GRID_SAMPLE_MAX_ROWS:
+        raise ValueError(f"{who}: {Q} grid rows (1 to 2^26)")
+    if not 1 <= g <= 65535:
+        raise ValueError(f"{who}: {g} images (1 to 65535)")
+    if level >= 0 and Q != sd.grid_size(level):
+        raise ValueError(f"{who}: {Q} rows are not the {sd.grid_size(level)} of level {level}")
+    if offset is not None and (level < 0 or offset.numel() != 9):
+        raise ValueError(f"{who}: offset of shape {tuple(offset.shape)} (want [3, 3], with a recursion_level)")
+    if seed is not None:
+        seed = _sample_seed(seed)
+    if not logp.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    seed = _sample_seed(seed)
+    lp = logp.detach().to(torch.float32).contiguous()
+    off = offset.detach().reshape(9).to(device=lp.device, dtype=torch.float32).contiguous() if offset is not None else None
+    return _grid_sample(lp, n, level, method, jitter, off, seed, 0)
+
+
+def grid_pose_sample(flow: Flow, feature: torch.Tensor = None, n: int = 1, recursion_level: int = 3, temperature: float = 1.0,
+                     method: str = "systematic", jitter: bool = True, offset=None, base=None, images_per_launch: int = None,
+                     seed: int = None) -> dict:
+    """``grid_sample`` of the flow's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches): ``n`` rotations per
+    image from softmax(log p / ``temperature``) over the level's cells -- temperature 1 the flow's posterior as the grid sees it, above 1
+    flatter, below 1 sharper (none of which ``flow.inverse`` can draw).  Image b of the batch is global image b of the stream, so the
+    result equals ``grid_sample`` of the materialised rows whatever ``images_per_launch``.  Flows with batch-coupled layers are refused.
+    -> ``grid_sample``'s dict (every entry [B,n,...]; ``log_prob`` is of the tempered rows) plus offset [3,3]"""
+    who = "grid_pose_sample"
+    n, level, method = _sample_options(n, recursion_level, method, who)
+    if level < 0:
+        raise ValueError(f"{who}: recursion_level is required (0..{GRID_SAMPLE_MAX_LEVEL})")
+    temperature = float(temperature)
+    if not 0.0 < temperature < float("inf"):
+        raise ValueError(f"{who}: temperature={temperature} (a positive number)")
+    _refuse_batch_coupled(flow, who, ", so an image's density would depend on the launch")
+    gf, level, offset = _grid_inputs(flow, feature, None, level, offset, base, who)
+    seed = _sample_seed(seed)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        off = offset.reshape(9).contiguous()
+        parts = []
+        for b0, b1, lp in gf.images(grid, images_per_launch, who):
+            if b1 - b0 > 65535:
+                raise ValueError(f"{who}: {b1 - b0} images in one launch (at most 65535)")
+            parts.append(_grid_sample((lp / temperature).contiguous(), n, level, method, jitter, off, seed, b0))
+    out = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    out["offset"] = offset
     return out
 
 

@@ -6,7 +6,8 @@ the right by an offset rotation (eval.py:440-442 ``grid @ random_rot``).  As in 
 ``device`` is given; the GPU does the work either way.
 
 ``grid_index`` and ``grid_histogram`` go the other way, from rotations on the device to the grid cells that hold them
-(``rnf_so3_grid_locate``).
+(``rnf_so3_grid_locate``); ``grid_cell_points`` is the chart of a cell, from a row and a point of the unit cube to a rotation inside the cell
+(``rnf_so3_grid_cell_points``).
 """
 import numpy as np
 import torch
@@ -145,3 +146,36 @@ def grid_histogram(rotations: torch.Tensor, recursion_level: int, offset=None, o
     _lib.call("so3_grid_locate", _lib.GridLocate(level=level, rotations=rot.data_ptr(), n=n, g=g,
                                                   offset=off.data_ptr() if off is not None else None, counts=out.data_ptr()), rot.device)
     return out
+
+
+GRID_CELL_POINTS_MAX_LEVEL = 6                     # rnf_so3_grid_cell_points' limit (include/rnf_hip.h)
+
+
+def grid_cell_points(index: torch.Tensor, u: torch.Tensor, recursion_level: int, offset=None) -> torch.Tensor:
+    """The chart of the grid's cells (``rnf_so3_grid_cell_points``, include/rnf_hip.h): the rotation at ``u`` [..., 3] in [0, 1]^3 inside
+    the cell of row ``index`` [...] (int64) of ``generate_healpix_grid(recursion_level, offset=offset)``, both on the device.  u[..., 0:2]
+    move across the HEALPix pixel in its face coordinates (an equal-area map), u[..., 2] along the tilt interval, so uniform ``u`` are
+    Haar-uniform in the cell (``grid_index`` of the result is ``index``, up to points within rounding of a cell's boundary) and
+    u = (0.5, 0.5, 0.5) is the grid's row.  A row outside the grid or a ``u`` outside [0, 1] gives NaNs.  Levels 0..6.
+    -> float32 [..., 3, 3]"""
+    level = int(recursion_level)
+    if not 0 <= level <= GRID_CELL_POINTS_MAX_LEVEL:
+        raise ValueError(f"grid_cell_points: recursion level {level} outside 0..{GRID_CELL_POINTS_MAX_LEVEL}")
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+        raise ValueError(f"grid_cell_points: index of dtype {getattr(index, 'dtype', type(index))} (want int64 grid rows)")
+    if not isinstance(u, torch.Tensor) or u.dim() < 1 or tuple(u.shape) != tuple(index.shape) + (3,):
+        raise ValueError(f"grid_cell_points: u of shape {tuple(getattr(u, 'shape', ()))} for index {tuple(index.shape)} (want [..., 3])")
+    if offset is not None and offset.numel() != 9:
+        raise ValueError(f"grid_cell_points: offset of shape {tuple(offset.shape)} (want [3, 3])")
+    if not index.is_cuda or not u.is_cuda:
+        raise RuntimeError("rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    dev = index.device
+    rows = index.detach().contiguous()
+    uu = u.detach().to(device=dev, dtype=torch.float32).contiguous()
+    off = offset.detach().reshape(9).to(device=dev, dtype=torch.float32).contiguous() if offset is not None else None
+    rot = torch.empty(tuple(index.shape) + (3, 3), dtype=torch.float32, device=dev)
+    if rows.numel() == 0:
+        return rot
+    _lib.call("so3_grid_cell_points", _lib.GridCellPoints(level=level, offset=off.data_ptr() if off is not None else None, rows=rows.data_ptr(),
+                                                           u=uu.data_ptr(), n=rows.numel(), rot_out=rot.data_ptr()), dev)
+    return rot
