@@ -10,6 +10,7 @@
 
 #include <type_traits>
 
+#include "fc_first.h"
 #include "layout.h"
 #include "so3_math.h"
 
@@ -500,6 +501,26 @@ struct Mlp<1> {
         c = RNF_MFMA(a.x, bA, c);
         return RNF_MFMA(a.y, bB, c);
     }
+    // FCH (the lean forward family, every width): the same product on ONE split-fp16 matrix step (fc_first.h), its A operand derived
+    // from the same fp32 image.  Both uses -- x0 and the residual -- take it, and neither keeps an operand across the hidden phase: each
+    // use derives A per out tile and B once from bA / bB (3 VALU and no cross-lane instruction each).
+    // Range: an fc_first weight, bias or input beyond the fp16 range splits into (inf, -inf) and its x0 row comes out NaN -- which the
+    // integer ReLU of the operand split launders into 0 when the sign bit is set (measured: the guard stayed quiet on a weight of 7e4;
+    // the exact steps hand the hidden layers a finite, huge x0 instead, whose split poisons them).  So the x0 use feeds the `hi` pairs of
+    // each lane's own operands through range_probe: v_dot2c_f32_f16 with a zero pair adds 0 to `acc`, or turns it NaN exactly when a half
+    // is inf or NaN.  head_ab adds the sum (0 or NaN) to the one accumulator register of hidden layer 0 that the existing NaN test reads
+    // behind its matrix steps, so the probe is 3 VALU and one add per layer and sets no flag of its own.  (A compare-and-flag form of the
+    // same test, on the fp16 pairs or on the fp32 values, cost the 16-wave instantiation two spilled registers: DESIGN.md section 6.)
+    static __device__ __forceinline__ float range_probe(const h8 v, float acc) {
+        const h2 p = {v[0], v[1]}, z = {(_Float16)0.0f, (_Float16)0.0f};
+        return __builtin_amdgcn_fdot2(p, z, acc, false);
+    }
+    static __device__ __forceinline__ f32x16 first_tile_h(const float *lds, int ot, int lane, const h8 b, float m1, f32x16 c, float *probe = nullptr) {
+        const float2 a = reinterpret_cast<const float2 *>(lds + MOB_FIRST)[ot * 64 + lane];
+        const h8 ah = fc_first_operand<false>(a.x, a.y, m1);
+        if (probe) *probe = range_probe(ah, *probe);
+        return RNF_MFMA_H(ah, b, c);
+    }
     // `bad`: set when a hidden layer comes out NaN.  An operand beyond the fp16 range splits into (inf, -inf) and turns EVERY output of
     // the next layer into NaN (each output row meets each input); the integer ReLU of split_pair would then launder a NaN with the sign
     // bit set into 0, so one accumulator register per hidden layer is tested before it is split (1 VALU each).  An overflow of the last
@@ -512,10 +533,11 @@ struct Mlp<1> {
     // ONE definition of the residual x0 + x3 (flow/condition.py:29) for every instantiation, so that a rotation's result does not depend on
     // the workgroup width its launch picked: fc_first(y) is accumulated onto x3 in the matrix unit, then the layer's projected features G
     // are added -- from the registers that kept them (KEEPX0: one read of the scratch) or from a second read of the scratch.
-    template <bool KEEPX0, class GF>
+    template <bool KEEPX0, bool FCH, class GF>
     static __device__ __forceinline__ void residual(const float *lds, int ot, int lane, int h, float bA, float bB, const GF &g,
-                                                    const f32x16 (&gk)[2], f32x16 &a, const float (&ga)[2], float gb) {
-        a = first_tile(lds, ot, lane, bA, bB, a);
+                                                    const f32x16 (&gk)[2], f32x16 &a, const float (&ga)[2], float gb, float m1) {
+        if constexpr (FCH) a = first_tile_h(lds, ot, lane, fc_first_operand<true>(bA, bB, m1), m1, a);
+        else a = first_tile(lds, ot, lane, bA, bB, a);
         if constexpr (GF::AS_BIAS) {                              // shared rows: G as one more fc_first step (see GFragRows)
             if (g) a = RNF_MFMA(ga[ot], gb, a);
         } else if (g) {
@@ -535,13 +557,14 @@ struct Mlp<1> {
         head_ab<GF, KEEPX0, FairT, DEEP>(lds, lane, h, h ? y1 : y0, h ? 1.0f : y2, g, out, fair, bad, pre);
     }
     // the same with the two fc_first operands of this lane half already chosen: bA = h ? y1 : y0, bB = h ? 1 : y2
-    template <class GF, bool KEEPX0 = false, class FairT = Fair, bool DEEP = false>
+    template <class GF, bool KEEPX0 = false, class FairT = Fair, bool DEEP = false, bool FCH = false>
     static __device__ __forceinline__ void head_ab(const float *lds, int lane, int h, const float bA, const float bB,
                                                    const GF &g, Act &out, FairT &fair, bool &bad, const f32x16 *pre = nullptr) {
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float m1 = -1.0f;
         asm("" : "+s"(m1));                                     // see split_act
         ActFrag &f = out;                                       // the fragments are rewritten in place, layer after layer
+        float probe = 0.0f;                                     // FCH only: 0, or NaN when an fc_first operand left the fp16 range (range_probe)
         f32x16 x0k[2];                                          // KEEPX0 only (dead otherwise): the projected features G of this layer
         float ga[2] = {0.f, 0.f}, gb = 0.f;                     // AS_BIAS only: the row records' A operands and the sample's row indicator
         if constexpr (GF::AS_BIAS) {                            // (for the tile-shaped sources the same re-derivation changes nothing: C4 7.87 / 7.93 ms)
@@ -558,6 +581,12 @@ struct Mlp<1> {
                     x0[ot] = first_tile(lds, ot, lane, bA, bB, zero);
                     if (g) x0[ot] = RNF_MFMA(ga[ot], gb, x0[ot]);
                 }
+            } else if constexpr (FCH) {
+                static_assert(std::is_same<GF, NoG>::value, "the split-fp16 fc_first serves the unconditional lean family only");
+                const h8 bh = fc_first_operand<true>(bA, bB, m1);
+                probe = range_probe(bh, 0.0f);
+#pragma unroll
+                for (int ot = 0; ot < 2; ++ot) x0[ot] = first_tile_h(lds, ot, lane, bh, m1, zero, &probe);
             } else {
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot) {
@@ -579,6 +608,7 @@ struct Mlp<1> {
             ah[0] = lds_h8(w(0, 0), 0 * 64 + lane); al[0] = lds_h8(w(0, 0), 1 * 64 + lane);
             ah[1] = lds_h8(w(0, 0), 2 * 64 + lane); al[1] = lds_h8(w(0, 0), 3 * 64 + lane);
             a0 = bias(0, 0); a1 = bias(0, 1);
+            if constexpr (FCH) a0[0] += probe;
             hidden_tile2<0, true>(w(0, 0), lane, f, a0, a0, m1, ah, al);
             bad |= a0[0] != a0[0];
             b0 = bias(1, 0);
@@ -591,11 +621,12 @@ struct Mlp<1> {
             a1 = bias(2, 1);
             hidden_tile2<1, true>(w(2, 0), lane, f, a0, b1, m1, ah, al);
             bad |= a0[0] != a0[0];
-            residual<KEEPX0>(lds, 0, lane, h, bA, bB, g, x0k, a0, ga, gb);
+            residual<KEEPX0, FCH>(lds, 0, lane, h, bA, bB, g, x0k, a0, ga, gb, m1);
             hidden_tile2<2, false>(w(2, 1), lane, f, a1, a0, m1, ah, al);
         } else {
         // layer 0: tile 0 bare (its input is complete), tile 1 carries the split of tile 0
         a0 = bias(0, 0); a1 = bias(0, 1);
+        if constexpr (FCH) a0[0] += probe;
         hidden_tile<0>(w(0, 0), lane, f, a0, a0, m1);
         bad |= a0[0] != a0[0];
         hidden_tile<2>(w(0, 1), lane, f, a1, a0, m1);
@@ -611,11 +642,11 @@ struct Mlp<1> {
         a1 = bias(2, 1);
         hidden_tile<1>(w(2, 0), lane, f, a0, b1, m1);
         bad |= a0[0] != a0[0];
-        residual<KEEPX0>(lds, 0, lane, h, bA, bB, g, x0k, a0, ga, gb);
+        residual<KEEPX0, FCH>(lds, 0, lane, h, bA, bB, g, x0k, a0, ga, gb, m1);
         hidden_tile<2>(w(2, 1), lane, f, a1, a0, m1);
         fair.tick();
         }
-        residual<KEEPX0>(lds, 1, lane, h, bA, bB, g, x0k, a1, ga, gb);
+        residual<KEEPX0, FCH>(lds, 1, lane, h, bA, bB, g, x0k, a1, ga, gb, m1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             split_pair(a1[2 * e], a1[2 * e + 1], m1, f.hi[2], f.lo[2], e);
@@ -778,6 +809,7 @@ struct Mlp<2> {
         const float bA = h ? y1 : y0;
         const float bB = h ? 1.0f : y2;
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float probe = 0.0f;                                     // FCH only: 0, or NaN when an fc_first operand left the fp16 range (range_probe)
         f32x16 x0k[2];                                          // KEEPX0 only
         float ga[2] = {0.f, 0.f}, gb = 0.f;                     // AS_BIAS only
         const float *ua = ctl.begin_unit();                     // Ha
@@ -2280,7 +2312,7 @@ __global__ __launch_bounds__(NW * 64) void flow_stack_kernel(const FlowArgs args
                     case 1: mobius_begin_cols<1>(R, hh, ctx.f, bA, bB); break;
                     default: mobius_begin_cols<2>(R, hh, ctx.f, bA, bB); break;
                 }
-                Mlp<1>::template head_ab<GF, KEEP_X0, FairT, DEEP_H>(lds, lane, hh, bA, bB, gfrag, tt, fair, bad);
+                Mlp<1>::template head_ab<GF, KEEP_X0, FairT, DEEP_H, true>(lds, lane, hh, bA, bB, gfrag, tt, fair, bad);
             } else if (LEAN == 1 || kind == RNF_KIND_MOBIUS) {
                 mobius_begin<DIR, DIR == 0 && PREC != 0>(R, perm_row, ctx);
                 Mlp<PREC>::template head<GF, KEEP_X0, FairT, DEEP_H>(lds, lane, hh, ctx.y.x, ctx.y.y, ctx.y.z, gfrag, tt, fair, bad, have_gpre ? gpre : nullptr);
