@@ -843,6 +843,80 @@ typedef struct RnfSo3GridLocalSum {
 } RnfSo3GridLocalSum;
 int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *sum);
 
+/* Harmonic analysis on SO(3) (csrc/so3_harmonics.h).  Y_l(x) is the vector of the 2l+1 orthonormal real spherical harmonics of degree
+ * l, m = -l..l: sqrt2 (-1)^m Re Y_l^m for m > 0, sqrt2 (-1)^m Im Y_l^|m| for m < 0, Y_l^0 for m = 0 (for l = 1: y, z, x).  The Wigner
+ * matrix D^l(R) is the real orthogonal (2l+1) x (2l+1) matrix with Y_l(R x) = D^l(R) Y_l(x): D^l(R1 R2) = D^l(R1) D^l(R2), D^0 = 1,
+ * D^1(R)[i][j] = R[p_i][p_j] with p = (1, 2, 0).  Layout of the C_L = (L+1)(2L+1)(2L+3)/3 entries of degrees 0..L: the degrees one after
+ * the other, degree l at l (4 l^2 - 1) / 3, row-major with m' (row) and m (column) from -l to l.  A 3x3 row is read through its
+ * normalised quaternion (no Euler angles: no singular chart), so a row that is not exactly orthogonal, or is scaled, is read as the
+ * rotation of that quaternion.  All three entries are stream-ordered, free of host synchronisation and capturable in a HIP graph as
+ * a linear chain; each builds its constants in its own workspace, none keeps state. */
+#define RNF_SO3_MAX_DEGREE 16
+
+/* out[i] = the entries of D^l(rotations[i]), l <= lmax.  A rotation with a non-finite entry gives NaN entries for that row alone.
+ * n = 0 is a no-op.  Two launches. */
+typedef struct RnfSo3Wigner {
+    size_t struct_bytes;        /* sizeof(RnfSo3Wigner); any other value is refused (header and library differ) */
+    const float *rotations;     /* dev float[n][9] row-major */
+    int64_t n;                  /* rotations, 0..2^24 */
+    int32_t lmax;               /* L, 0..16 */
+    float *out;                 /* dev float[n][C_L] */
+    void *workspace;            /* dev scratch, 16-byte aligned, of at least rnf_so3_wigner_workspace_bytes(this struct) bytes */
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3Wigner;
+int rnf_so3_wigner(const RnfSo3Wigner *wigner);
+/* 4 (2L+1)^2 (2 + 4L) rounded up to 16; 0 when struct_bytes, lmax or n are out of range (the pointers are not read) */
+size_t rnf_so3_wigner_workspace_bytes(const RnfSo3Wigner *wigner);
+
+/* The Fourier coefficients of weighted rotations: with w_g = softmax(log_weights[g]) (uniform without log-weights), formed as
+ * rnf_so3_kernel_sum forms them,   out[g] = sum_j w_gj D(centres[j])   (all degrees up to lmax; out[g][0] = 1 up to rounding).
+ * Edge cases: a centre with log-weight -inf is left out whatever its entries; another non-finite centre or a NaN log-weight makes its
+ * group NaN; a group with no mass is NaN.
+ * Deterministic: chunks of 4096 centres, normalised fp32 weights from a prepass, one fp64 partial per (group, chunk, coefficient) --
+ * the exact products w D added in fp64 in centre order -- added in chunk order in fp64 and rounded once; no floating-point atomics.  A group's coefficients are
+ * bit-identical from run to run and whatever G and the group's position are, and a coefficient's bits do not depend on lmax: groups and
+ * degrees may be split over calls.  Seven launches. */
+typedef struct RnfSo3Fourier {
+    size_t struct_bytes;        /* sizeof(RnfSo3Fourier) */
+    const float *centres;       /* dev float[n][9] row-major */
+    const float *log_weights;   /* dev float[G][n], or NULL (uniform weights) */
+    int64_t n;                  /* centres, 1..2^24 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    int32_t lmax;               /* L, 0..16 */
+    float *out;                 /* dev float[G][C_L] */
+    /* dev scratch, 16-byte aligned, of at least rnf_so3_fourier_workspace_bytes(this struct) bytes = 8 G ceil(n / 4096) C_L +
+     * 16 G ceil(n / 4096) + 8 G + 4 G n rounded up to 16, + 4 n (8L + 16) + 4 (2L+1)^2 (2 + 4L) rounded up to 16 */
+    void *workspace;
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3Fourier;
+int rnf_so3_fourier(const RnfSo3Fourier *fourier);
+size_t rnf_so3_fourier_workspace_bytes(const RnfSo3Fourier *fourier);
+
+/* The band-limited function with coefficients coeffs[g] at query rotations:   out[g][i] = sum_l sum_{m'm} coeffs[g][l, m', m]
+ * D^l_{m'm}(queries[i]).  With coeffs^l = (2l+1) h_l F^l of rnf_so3_fourier this is a density relative to the normalised Haar measure
+ * (uniform = 1), the measure convolved with the zonal kernel of multipliers h_l.  An entry's degrees are added in fp32 (at most 17
+ * terms), the entries in fp64 in a fixed order, rounded once: a (group, query)'s value is bit-identical however queries and groups are
+ * tiled over calls, and whether the queries are shared or given per group.  A non-finite query gives NaN for that query alone;
+ * non-finite coefficients stay in their own group.  m = 0 is a no-op.  Two launches. */
+typedef struct RnfSo3FourierEval {
+    size_t struct_bytes;        /* sizeof(RnfSo3FourierEval) */
+    const float *coeffs;        /* dev float[G][C_L] */
+    const float *queries;       /* dev float[m][9], or float[G][m][9] with group_queries */
+    int64_t m;                  /* queries (per group), 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of coefficients), 1..65535 */
+    int32_t group_queries;      /* 0: the groups share the queries; != 0: one set per group */
+    int32_t lmax;               /* L, 0..16 */
+    float *out;                 /* dev float[G][m] */
+    void *workspace;            /* dev scratch, 16-byte aligned, of at least rnf_so3_fourier_eval_workspace_bytes(this struct) bytes */
+    size_t workspace_bytes;
+    void *stream;
+} RnfSo3FourierEval;
+int rnf_so3_fourier_eval(const RnfSo3FourierEval *eval);
+/* 4 (2L+1)^2 (2 + 4L) rounded up to 16; 0 when struct_bytes, lmax, G or m are out of range (the pointers are not read) */
+size_t rnf_so3_fourier_eval_workspace_bytes(const RnfSo3FourierEval *eval);
+
 /* Proper SVD of B parameter matrices on the device (utils/fisher.py:53-76): A = U diag(s) V^T with U, V rotations (row-major, singular
  * vectors as columns), s[2] carrying the sign of det A; lam [B,4] = the Bingham parameters the sampler takes (utils/fisher.py:151-158).
  * Any output pointer may be NULL.  Stream-ordered, no host synchronisation. */

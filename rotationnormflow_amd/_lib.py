@@ -128,6 +128,27 @@ class So3GridLocalSum(_Pass):
                 ("out", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class So3Wigner(_Pass):
+    """RnfSo3Wigner (include/rnf_hip.h): the real Wigner matrices of rotations, degrees 0..lmax."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("rotations", C.c_void_p), ("n", C.c_int64), ("lmax", C.c_int32), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class So3Fourier(_Pass):
+    """RnfSo3Fourier (include/rnf_hip.h): the SO(3) Fourier coefficients of weighted rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("centres", C.c_void_p), ("log_weights", C.c_void_p), ("n", C.c_int64), ("G", C.c_int32),
+                ("lmax", C.c_int32), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class So3FourierEval(_Pass):
+    """RnfSo3FourierEval (include/rnf_hip.h): a band-limited function on SO(3) at query rotations."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("coeffs", C.c_void_p), ("queries", C.c_void_p), ("m", C.c_int64), ("G", C.c_int32),
+                ("group_queries", C.c_int32), ("lmax", C.c_int32), ("out", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+SO3_MAX_DEGREE = 16   # RNF_SO3_MAX_DEGREE
+
 GRID_FIT_STATS =("log_norm", "log_likelihood", "grid_log_likelihood", "g_stat", "chi2", "n", "occupied")   # RNF_GRID_FIT_*
 
 
@@ -234,6 +255,12 @@ _SIGNATURES = {
     "rnf_so3_set_angle_cdf": (C.c_int, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_set_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_grid_local_sum": (C.c_int, [C.POINTER(So3GridLocalSum)]),
+    "rnf_so3_wigner": (C.c_int, [C.POINTER(So3Wigner)]),
+    "rnf_so3_wigner_workspace_bytes": (C.c_size_t, [C.POINTER(So3Wigner)]),
+    "rnf_so3_fourier": (C.c_int, [C.POINTER(So3Fourier)]),
+    "rnf_so3_fourier_workspace_bytes": (C.c_size_t, [C.POINTER(So3Fourier)]),
+    "rnf_so3_fourier_eval": (C.c_int, [C.POINTER(So3FourierEval)]),
+    "rnf_so3_fourier_eval_workspace_bytes": (C.c_size_t, [C.POINTER(So3FourierEval)]),
     "rnf_grid_beam_select": (C.c_int, [C.POINTER(GridBeamSelect)]),
     "rnf_grid_beam_select_workspace_bytes": (C.c_size_t, [C.POINTER(GridBeamSelect)]),
     "rnf_fisher_log_const": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_void_p]),

@@ -37,6 +37,7 @@
 #include "so3_angle_cdf.h"
 #include "so3_set_angle_cdf.h"
 #include "so3_grid_local.h"
+#include "so3_harmonics.h"
 
 using namespace rnf;
 
@@ -2078,6 +2079,128 @@ extern "C" int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *p) {
     hipLaunchKernelGGL(sac::so3_set_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
                        (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m * p->K : 0LL, (int)p->m, (int)p->K, nchunk, T,
                        (int)mom, taus, T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// Harmonic analysis on SO(3) (csrc/so3_harmonics.h).  Every entry first writes the entry records into its workspace.
+static int so3_harmonics_records(int L, float *records, hipStream_t s) {
+    hipLaunchKernelGGL(sh::so3_harmonics_records_kernel, dim3((unsigned)((sh::entry_count(L) + sh::THREADS - 1) / sh::THREADS)), dim3(sh::THREADS), 0,
+                       s, L, records);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int so3_wigner_check(const RnfSo3Wigner *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3Wigner)) return fail("RnfSo3Wigner.struct_bytes does not match the library's %zu", sizeof(RnfSo3Wigner));
+    if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3Wigner.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
+    if (p->n < 0 || p->n > sh::MAX_N) return fail("RnfSo3Wigner.n=%lld outside 0..2^24", (long long)p->n);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_wigner_workspace_bytes(const RnfSo3Wigner *p) { return so3_wigner_check(p) ? 0 : sh::records_bytes(p->lmax); }
+
+extern "C" int rnf_so3_wigner(const RnfSo3Wigner *p) {
+    if (so3_wigner_check(p)) return 1;
+    if (p->n == 0) return 0;
+    if (!p->rotations || !p->out) return fail("RnfSo3Wigner: null rotations or out");
+    const size_t need = sh::records_bytes(p->lmax);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3Wigner.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_wigner_workspace_bytes)", p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3Wigner.workspace must be 16-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    float *records = static_cast<float *>(p->workspace);
+    if (so3_harmonics_records(p->lmax, records, s)) return 1;
+    hipLaunchKernelGGL(sh::so3_wigner_kernel, dim3((unsigned)((p->n + sh::THREADS - 1) / sh::THREADS)), dim3(sh::THREADS), 0, s, p->rotations,
+                       (long long)p->n, (int)p->lmax, (const float *)records, p->out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int so3_fourier_check(const RnfSo3Fourier *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3Fourier)) return fail("RnfSo3Fourier.struct_bytes does not match the library's %zu", sizeof(RnfSo3Fourier));
+    if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3Fourier.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3Fourier.G=%d outside 1..65535", p->G);
+    if (p->n < 1 || p->n > sh::MAX_N) return fail("RnfSo3Fourier.n=%lld outside 1..2^24", (long long)p->n);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_fourier_workspace_bytes(const RnfSo3Fourier *p) {
+    return so3_fourier_check(p) ? 0 : sh::carve(nullptr, p->n, p->G, p->lmax).bytes;
+}
+
+extern "C" int rnf_so3_fourier(const RnfSo3Fourier *p) {
+    if (so3_fourier_check(p)) return 1;
+    if (!p->centres || !p->out) return fail("RnfSo3Fourier: null centres or out");
+    const size_t need = sh::carve(nullptr, p->n, p->G, p->lmax).bytes;
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3Fourier.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_fourier_workspace_bytes)", p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3Fourier.workspace must be 16-byte aligned");
+    const sh::Workspace w = sh::carve(p->workspace, p->n, p->G, p->lmax);
+    const int nchunk = (int)ks::chunks_for(p->n), L = p->lmax, n = (int)p->n, G = p->G, CL = sh::coefficient_count(L);
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    if (so3_harmonics_records(L, w.records, s)) return 1;
+    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, n, w.wpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ac::so3_angle_cdf_weights_kernel, dim3((unsigned)((n + ks::THREADS - 1) / ks::THREADS), G), dim3(ks::THREADS), 0, s,
+                       p->log_weights, (const double *)w.log_z, n, w.wn);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sh::so3_fourier_table_kernel, dim3((unsigned)((n + sh::THREADS - 1) / sh::THREADS)), dim3(sh::THREADS), 0, s, p->centres, n, L,
+                       w.tab);
+    HIP_TRY(hipGetLastError());
+    const int gb = sh::groups_per_thread(L);
+    const dim3 grid((unsigned)((sh::entry_count(L) + sh::THREADS - 1) / sh::THREADS), nchunk, (unsigned)((G + gb - 1) / gb));
+    if (L <= 8)
+        hipLaunchKernelGGL((sh::so3_fourier_kernel<8, 4>), grid, dim3(sh::THREADS), 0, s, (const float *)w.tab, (const float *)w.wn,
+                           (const float *)w.records, n, L, G, w.psum);
+    else
+        hipLaunchKernelGGL((sh::so3_fourier_kernel<16, 2>), grid, dim3(sh::THREADS), 0, s, (const float *)w.tab, (const float *)w.wn,
+                           (const float *)w.records, n, L, G, w.psum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sh::so3_fourier_final_kernel, dim3((unsigned)((CL + sh::THREADS - 1) / sh::THREADS), G), dim3(sh::THREADS), 0, s,
+                       (const double *)w.psum, nchunk, CL, p->out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int so3_fourier_eval_check(const RnfSo3FourierEval *p) {
+    if (!p || p->struct_bytes != sizeof(RnfSo3FourierEval))
+        return fail("RnfSo3FourierEval.struct_bytes does not match the library's %zu", sizeof(RnfSo3FourierEval));
+    if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3FourierEval.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3FourierEval.G=%d outside 1..65535", p->G);
+    if (p->m < 0 || p->m > sh::MAX_M) return fail("RnfSo3FourierEval.m=%lld outside 0..2^31-1", (long long)p->m);
+    return 0;
+}
+
+extern "C" size_t rnf_so3_fourier_eval_workspace_bytes(const RnfSo3FourierEval *p) {
+    return so3_fourier_eval_check(p) ? 0 : sh::records_bytes(p->lmax);
+}
+
+extern "C" int rnf_so3_fourier_eval(const RnfSo3FourierEval *p) {
+    if (so3_fourier_eval_check(p)) return 1;
+    if (p->m == 0) return 0;
+    if (!p->coeffs || !p->queries || !p->out) return fail("RnfSo3FourierEval: null coeffs, queries or out");
+    const size_t need = sh::records_bytes(p->lmax);
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("RnfSo3FourierEval.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_fourier_eval_workspace_bytes)",
+                    p->workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3FourierEval.workspace must be 16-byte aligned");
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    float *records = static_cast<float *>(p->workspace);
+    if (so3_harmonics_records(p->lmax, records, s)) return 1;
+    const int gb = !p->group_queries && p->G > 1 ? ks::GROUPS_PER_THREAD : 1;                // shared queries: the groups share the entries
+    const unsigned yblocks = (unsigned)((p->G + gb - 1) / gb);
+    const int block = (p->m + sh::THREADS - 1) / sh::THREADS * yblocks < ac::FEW_BLOCKS ? ac::SMALL_BLOCK : sh::THREADS;
+    const dim3 grid((unsigned)((p->m + block - 1) / block), yblocks);
+    const long long q_group = p->group_queries ? 9 * (long long)p->m : 0;
+    if (gb > 1)
+        hipLaunchKernelGGL((sh::so3_fourier_eval_kernel<ks::GROUPS_PER_THREAD>), grid, dim3(block), 0, s, p->queries, p->coeffs,
+                           (const float *)records, (long long)p->m, (int)p->lmax, (int)p->G, q_group, p->out);
+    else
+        hipLaunchKernelGGL((sh::so3_fourier_eval_kernel<1>), grid, dim3(block), 0, s, p->queries, p->coeffs, (const float *)records, (long long)p->m,
+                           (int)p->lmax, (int)p->G, q_group, p->out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

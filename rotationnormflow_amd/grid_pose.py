@@ -953,6 +953,116 @@ def grid_pose_filter(flow: Flow, features: torch.Tensor = None, kappa: float = N
     return dict(est=grid[index], index=index, log_evidence=torch.cat(evidences), posterior=post[0], grid=grid, offset=offset)
 
 
+SPECTRAL_TRUNCATION = 1e-2                          # the largest (2L+1) h_L the spectral passes accept
+
+
+def _spectral_multiplier(kappa, t, lmax: int, who: str, required: bool = True):
+    """-> (multipliers [L+1] float64 or None, truncation = (2L+1) h_L); raises where the kernel is too sharp for lmax"""
+    from .utils import harmonics
+    if kappa is not None and t is not None:
+        raise ValueError(f"{who}: both kappa and t are given; pass one of the two")
+    if kappa is None and t is None:
+        if required:
+            raise ValueError(f"{who}: one of kappa (matrix-Fisher kernel) and t (heat kernel) is required")
+        return None, float(2 * lmax + 1)
+    h = harmonics.fisher_multipliers(kappa, lmax) if kappa is not None else harmonics.heat_multipliers(t, lmax)
+    truncation = float((2 * lmax + 1) * h[lmax])
+    if truncation > SPECTRAL_TRUNCATION:
+        what = f"kappa={float(kappa)}" if kappa is not None else f"t={float(t)}"
+        raise ValueError(f"{who}: {what} is too sharp for lmax={lmax}: the first degree left out would still carry (2L+1) h_L = "
+                         f"{truncation:.3g} > {SPECTRAL_TRUNCATION}; raise lmax, or use grid_diffuse_local, which is made for sharp kernels")
+    return h, truncation
+
+
+def _spectral_density(coeffs, grid, lmax: int, h, truncation: float) -> dict:
+    from .utils import harmonics
+    density = harmonics.so3_fourier_density(coeffs, grid, lmax, multiplier=h)
+    tiny = float(np.finfo(np.float32).tiny)
+    negative = density.to(torch.float64).clamp(max=0.0).sum(dim=1) / grid.shape[0]
+    return dict(density=density, log_density=torch.log(density.clamp(min=tiny)), negative_mass=negative, truncation=truncation,
+                coefficients=coeffs)
+
+
+def _spectrum_of(coeffs, lmax: int) -> dict:
+    from .utils import harmonics
+    power = harmonics.power_spectrum(coeffs.to(torch.float64), lmax)
+    collision = power.sum(dim=-1)
+    return dict(coefficients=coeffs, power=power, collision=collision, tail=power[..., lmax] / collision)
+
+
+def grid_spectrum(logp: torch.Tensor, grid: torch.Tensor, lmax: int = 8) -> dict:
+    """The SO(3) Fourier coefficients of each image's grid posterior and their power per degree: a sharpness measure that does not
+    depend on a resolution.  ``logp`` [B,Q] log-densities on the rows of ``grid`` [Q,3,3] (any normalisation); p_b = softmax(logp_b).
+    -> dict(coefficients [B,C_L] float32 = F_b^l = sum_q p_bq D^l(R_q) (``utils.harmonics.so3_fourier``), power [B,lmax+1] float64 =
+    (2l+1) |F^l|_F^2, collision [B] = sum_l power, which tends to the integral of p^2 (1 for the uniform density), tail [B] =
+    power[lmax] / collision: a tail that is not small says that lmax is too low for this posterior).  The analysis is of the discrete
+    measure on the grid rows, so it carries the grid's quadrature error."""
+    from .utils import harmonics
+    who = "grid_spectrum"
+    _local_args(logp, grid, who)
+    _error_args(logp, grid, who)
+    return _spectrum_of(harmonics.so3_fourier(grid, lmax, log_weights=logp), lmax)
+
+
+def grid_diffuse_spectral(logp: torch.Tensor, grid: torch.Tensor, kappa: float = None, t: float = None, lmax: int = 8) -> dict:
+    """Each image's grid posterior convolved with a WIDE zonal kernel, in the harmonic domain: the isotropic matrix-Fisher kernel of
+    concentration ``kappa`` (the kernel of ``grid_diffuse``) or the heat kernel at time ``t``, evaluated on the grid rows.  The
+    counterpart of ``grid_diffuse_local``: a sharp kernel stays local, a wide one needs few degrees and costs Q C_L per image whatever
+    its width.  ``logp`` [B,Q] on the rows of ``grid`` [Q,3,3]; p_b = softmax(logp_b), F_b = ``so3_fourier`` of it,
+        density[b][i] = sum_l (2l+1) h_l <F_b^l, D^l(R_i)>.
+    -> dict(density [B,Q] float32 relative to Haar (uniform = 1), log_density = log max(density, tiny), negative_mass [B] float64 =
+    sum_q min(density, 0) / Q, truncation = (2L+1) h_L, coefficients [B,C_L] of the posterior).  Raises ValueError where the kernel is
+    so sharp that ``truncation`` exceeds 1e-3: use ``grid_diffuse_local`` there.  Unlike ``grid_diffuse`` the operator is not
+    renormalised on the grid: it differs from it by the grid's quadrature error plus the truncation.  ``log_density`` feeds
+    ``grid_modes``, ``grid_credible``, ``grid_sample`` and ``grid_filter_step``."""
+    from .utils import harmonics
+    who = "grid_diffuse_spectral"
+    _local_args(logp, grid, who)
+    _error_args(logp, grid, who)
+    lmax = harmonics._lmax(lmax, who)
+    h, truncation = _spectral_multiplier(kappa, t, lmax, who)
+    return _spectral_density(harmonics.so3_fourier(grid, lmax, log_weights=logp), grid, lmax, h, truncation)
+
+
+def grid_compose(logp_a: torch.Tensor, logp_b: torch.Tensor, grid: torch.Tensor, lmax: int = 8, invert_a: bool = False,
+                 smooth_kappa: float = None) -> dict:
+    """The density of R_a R_b (``invert_a``: of R_a^T R_b, the relative rotation) for independent R_a ~ softmax(logp_a), R_b ~
+    softmax(logp_b) on the rows of ``grid`` [Q,3,3], evaluated on the same rows: blocks F_a^l F_b^l (``utils.harmonics.compose``) in
+    place of a Q^2 gather.  ``logp_a``, ``logp_b`` [B,Q] (one may hold a single row shared by the other's images).  ``smooth_kappa``:
+    the product is also convolved with the matrix-Fisher kernel of that concentration (None: band limiting alone, which rings where
+    the product is sharper than lmax resolves; ``truncation`` is then 2 lmax + 1).  -> the dict of ``grid_diffuse_spectral``."""
+    from .utils import harmonics
+    who = "grid_compose"
+    _local_args(logp_a, grid, who, "logp_a")
+    _local_args(logp_b, grid, who, "logp_b")
+    _error_args(logp_a, grid, who)
+    _error_args(logp_b, grid, who)
+    if logp_a.shape[0] != logp_b.shape[0] and 1 not in (logp_a.shape[0], logp_b.shape[0]):
+        raise ValueError(f"{who}: logp_a holds {logp_a.shape[0]} images, logp_b {logp_b.shape[0]} (the same number, or one of them 1)")
+    lmax = harmonics._lmax(lmax, who)
+    h, truncation = _spectral_multiplier(smooth_kappa, None, lmax, who, required=False)
+    Fa, Fb = harmonics.so3_fourier(grid, lmax, log_weights=logp_a), harmonics.so3_fourier(grid, lmax, log_weights=logp_b)
+    return _spectral_density(harmonics.compose(Fa, Fb, lmax, invert_a=invert_a).contiguous(), grid, lmax, h, truncation)
+
+
+def grid_pose_spectrum(flow: Flow, feature: torch.Tensor = None, lmax: int = 8, number_queries: int = None, recursion_level: int = None,
+                       offset=None, base=None, images_per_launch: int = None) -> dict:
+    """``grid_spectrum`` of each image's density on the grid of ``grid_estimate_rotations`` (same inputs, same launches; a group's
+    coefficients do not depend on the launch that held it).  Flows with batch-coupled layers are refused as in ``grid_pose_fisher``.
+    -> the dict of ``grid_spectrum`` plus offset [3,3]."""
+    from .utils import harmonics
+    who = "grid_pose_spectrum"
+    lmax = harmonics._lmax(lmax, who)
+    _refuse_batch_coupled(flow, who, ", so an image's density would depend on the launch")
+    gf, level, offset = _grid_inputs(flow, feature, number_queries, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        parts = [harmonics.so3_fourier(grid, lmax, log_weights=lp) for b0, b1, lp in gf.images(grid, images_per_launch, who)]
+        out = _spectrum_of(parts[0] if len(parts) == 1 else torch.cat(parts), lmax)
+    out["offset"] = offset
+    return out
+
+
 def grid_pose_fit(flow: Flow, feature: torch.Tensor = None, samples: torch.Tensor = None, n_samples: int = 1 << 18, recursion_level: int = 2,
                   offset=None, base=None, images_per_launch: int = None) -> dict:
     """Samples against the flow's density, on the grid of ``grid_estimate_rotations`` (same inputs, same launches, the chunk gathering of
