@@ -64,6 +64,28 @@ static int fail(const char *fmt, ...) {
         if (e_ != hipSuccess) return fail("%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The checks that every struct entry repeats; `who` is the struct's name.  Each returns 0, or 1 with the message set.
+template <class P>
+static int check_struct(const P *p, const char *who) {
+    if (!p || p->struct_bytes != sizeof(P)) return fail("%s.struct_bytes does not match the library's %zu", who, sizeof(P));
+    return 0;
+}
+
+// p->workspace holds `need` bytes (as `fn`, the entry's *_workspace_bytes, computes) and, with align > 0, is aligned to it
+template <class P>
+static int check_workspace(const P *p, const char *who, size_t need, const char *fn, unsigned align) {
+    if (!p->workspace || p->workspace_bytes < need)
+        return fail("%s.workspace of %zu bytes is smaller than the %zu needed (%s)", who, (size_t)p->workspace_bytes, need, fn);
+    if (align && reinterpret_cast<uintptr_t>(p->workspace) % align) return fail("%s.workspace must be %u-byte aligned", who, align);
+    return 0;
+}
+
+// `what` names the one or two pointers after the struct's name (null: aligned)
+static int check_aligned16(const void *a, const void *b, const char *who, const char *what) {
+    if (reinterpret_cast<uintptr_t>(a) % 16 || reinterpret_cast<uintptr_t>(b) % 16) return fail("%s%s must be 16-byte aligned", who, what);
+    return 0;
+}
+
 // The 0/1 switches of the environment: on unless the value starts with '0' (default on), or off unless it starts with '1'.  Each is read
 // once per process (flow_switches, equalise_allowed); flow_plan.h struct Switches says what each one does.
 static bool env_flag(const char *name, bool dflt) {
@@ -831,10 +853,7 @@ extern "C" int rnf_flow_pass(const RnfFlowPass *p) {
 }
 
 extern "C" size_t rnf_flow_pass_workspace_bytes(const RnfFlowPass *p) {
-    if (!p || p->struct_bytes != sizeof(RnfFlowPass)) {
-        fail("RnfFlowPass.struct_bytes does not match the library's %zu", sizeof(RnfFlowPass));
-        return 0;
-    }
+    if (check_struct(p, "RnfFlowPass")) return 0;
     int n_slots;
     bool any_mlp;
     desc_slots(p->desc, p->n_layers, &n_slots, &any_mlp);
@@ -1424,8 +1443,7 @@ extern "C" int rnf_so3_healpix_grid(int32_t level, const float *offset, float *o
 }
 
 extern "C" int rnf_so3_grid_children(const RnfGridChildren *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridChildren))
-        return fail("RnfGridChildren.struct_bytes does not match the library's %zu", sizeof(RnfGridChildren));
+    if (check_struct(p, "RnfGridChildren")) return 1;
     if (p->level < 0 || p->level >= so3g::MAX_LEVEL)
         return fail("RnfGridChildren.level=%d outside 0..%d (children at level + 1 <= %d)", p->level, so3g::MAX_LEVEL - 1, so3g::MAX_LEVEL);
     if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridChildren.n=%lld outside 0..2^36", (long long)p->n);
@@ -1442,8 +1460,7 @@ extern "C" int rnf_so3_grid_children(const RnfGridChildren *p) {
 
 // Beam selection (csrc/grid_beam.h): passes of one-chunk-per-block sorts until one chunk per image remains.
 static int grid_beam_check(const RnfGridBeamSelect *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridBeamSelect))
-        return fail("RnfGridBeamSelect.struct_bytes does not match the library's %zu", sizeof(RnfGridBeamSelect));
+    if (check_struct(p, "RnfGridBeamSelect")) return 1;
     if (p->g < 1 || p->g > 65535) return fail("RnfGridBeamSelect.g=%d outside 1..65535", p->g);
     if (p->M < 1 || p->M > gb::ROW_MAX + 1) return fail("RnfGridBeamSelect.M=%lld outside 1..2^31 - 1", (long long)p->M);
     if (p->beam < 1 || p->beam > gb::MAX_BEAM) return fail("RnfGridBeamSelect.beam=%d outside 1..%d", p->beam, gb::MAX_BEAM);
@@ -1461,9 +1478,7 @@ extern "C" int rnf_grid_beam_select(const RnfGridBeamSelect *p) {
     if (grid_beam_check(p)) return 1;
     if (!p->logp || !p->rows_out || !p->logp_out) return fail("RnfGridBeamSelect: null logp or output pointer");
     const size_t need = rnf_grid_beam_select_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfGridBeamSelect.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_beam_select_workspace_bytes)",
-                    p->workspace_bytes, need);
+    if (check_workspace(p, "RnfGridBeamSelect", need, "rnf_grid_beam_select_workspace_bytes", 0)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
     const int dedup = p->rows != nullptr;
     unsigned long long *ws = (unsigned long long *)p->workspace;
@@ -1484,8 +1499,7 @@ extern "C" int rnf_grid_beam_select(const RnfGridBeamSelect *p) {
 
 // Top-k pose modes on the grid (csrc/grid_modes.h): k arg-max passes and one mass pass, each followed by its per-image finalise.
 static int grid_modes_check(const RnfGridModes *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridModes))
-        return fail("RnfGridModes.struct_bytes does not match the library's %zu", sizeof(RnfGridModes));
+    if (check_struct(p, "RnfGridModes")) return 1;
     if (p->g < 1 || p->g > 65535) return fail("RnfGridModes.g=%d outside 1..65535", p->g);
     if (p->Q < 1) return fail("RnfGridModes.Q=%lld must be >= 1", (long long)p->Q);
     if (p->top_k < 1 || p->top_k > gm::MAX_K) return fail("RnfGridModes.top_k=%d outside 1..%d", p->top_k, gm::MAX_K);
@@ -1503,12 +1517,11 @@ extern "C" int rnf_grid_modes(const RnfGridModes *p) {
         return fail("RnfGridModes.separation_rad=%g outside (0, pi]", p->separation_rad);
     if (!p->logp || !p->grid || !p->index_out || !p->logp_out || !p->mass_out || !p->log_norm_out)
         return fail("RnfGridModes: null logp, grid or output pointer");
-    if (reinterpret_cast<uintptr_t>(p->grid) % 16) return fail("RnfGridModes.grid must be 16-byte aligned");
+    if (check_aligned16(p->grid, nullptr, "RnfGridModes", ".grid")) return 1;
     if (p->gt && (p->n_gt < 1 || p->n_gt > gm::MAX_GT)) return fail("RnfGridModes.n_gt=%d outside 1..%d", p->n_gt, gm::MAX_GT);
     if (p->gt && !p->spread_out) return fail("RnfGridModes.gt needs spread_out");
     const size_t need = rnf_grid_modes_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfGridModes.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_modes_workspace_bytes)", p->workspace_bytes, need);
+    if (check_workspace(p, "RnfGridModes", need, "rnf_grid_modes_workspace_bytes", 0)) return 1;
     const float thr = p->separation_rad >= M_PI ? -INFINITY : (float)(1.0 + 2.0 * cos(p->separation_rad));
     const int nb = (int)gm::blocks_for(p->Q), k = p->top_k;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
@@ -1530,11 +1543,23 @@ extern "C" int rnf_grid_modes(const RnfGridModes *p) {
     return 0;
 }
 
+// The row maximum of g images of Q log-densities -> max_index[g], max_value[g]: grid_modes.h's arg-max pass for one mode (k = 1, no grid,
+// no separation) and its finalise.  The prologue of the credible sets, the histogram fit and the draws.
+static int launch_row_max(const float *logp, long long Q, int g, gm::ArgPart *max_part, long long *max_index, float *max_value, hipStream_t s) {
+    const int nbm = (int)gm::blocks_for(Q);
+    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, g), dim3(gm::THREADS), 0, s, logp, (const float *)nullptr, Q, 1, 0, 0.0f,
+                       (const long long *)max_index, (const float *)max_value, max_part);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)max_part, nbm, 1, 0, max_index,
+                       max_value);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Credible sets on the grid (csrc/grid_credible.h): the row maximum by grid_modes.h's arg-max pass, then 4 histogram passes of the radix
 // select, each followed by its finalise.
 static int grid_credible_check(const RnfGridCredible *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridCredible))
-        return fail("RnfGridCredible.struct_bytes does not match the library's %zu", sizeof(RnfGridCredible));
+    if (check_struct(p, "RnfGridCredible")) return 1;
     if (p->g < 1 || p->g > 65535) return fail("RnfGridCredible.g=%d outside 1..65535", p->g);
     if (p->Q < 1 || p->Q > gc::MAX_Q) return fail("RnfGridCredible.Q=%lld outside 1..2^26", (long long)p->Q);
     if (p->n_levels < 1 || p->n_levels > gc::MAX_LEVELS)
@@ -1563,21 +1588,13 @@ extern "C" int rnf_grid_credible(const RnfGridCredible *p) {
     if (G > 0 && (!p->queries || !p->query_mass_out || !p->query_count_out))
         return fail("RnfGridCredible: null queries, query_mass_out or query_count_out with n_queries=%d", G);
     const size_t need = rnf_grid_credible_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfGridCredible.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_credible_workspace_bytes)",
-                    p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridCredible.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfGridCredible", need, "rnf_grid_credible_workspace_bytes", 8)) return 1;
     const gc::Workspace w = gc::carve(p->workspace, p->Q, p->g, J, G);
     const long long Q = p->Q;
-    const int nbm = (int)gm::blocks_for(Q), nb = (int)gc::blocks_for(Q), S = gc::fixed_point_shift(Q);
+    const int nb = (int)gc::blocks_for(Q), S = gc::fixed_point_shift(Q);
     const double scale = ldexp(1.0, S);
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
-                       (const long long *)w.max_index, (const float *)w.max_value, w.max_part);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
-                       w.max_index, w.max_value);
-    HIP_TRY(hipGetLastError());
+    if (launch_row_max(p->logp, Q, p->g, w.max_part, w.max_index, w.max_value, s)) return 1;
     for (int pass = 0; pass < gc::PASSES; ++pass) {
         const gc::State *prev = pass ? w.state + (size_t)(pass - 1) * p->g * J : nullptr;
         gc::State *next = w.state + (size_t)pass * p->g * J;
@@ -1606,8 +1623,7 @@ extern "C" int rnf_grid_credible(const RnfGridCredible *p) {
 
 // The cell of a rotation and the histogram over the cells (csrc/grid_locate.h): one thread per rotation.
 extern "C" int rnf_so3_grid_locate(const RnfGridLocate *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridLocate))
-        return fail("RnfGridLocate.struct_bytes does not match the library's %zu", sizeof(RnfGridLocate));
+    if (check_struct(p, "RnfGridLocate")) return 1;
     if (p->level < 0 || p->level > so3g::MAX_LEVEL) return fail("RnfGridLocate.level=%d outside 0..%d", p->level, so3g::MAX_LEVEL);
     if (p->g < 1 || p->g > 65535) return fail("RnfGridLocate.g=%d outside 1..65535", p->g);
     if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridLocate.n=%lld outside 0..2^36", (long long)p->n);
@@ -1627,7 +1643,7 @@ extern "C" int rnf_so3_grid_locate(const RnfGridLocate *p) {
 
 // The fit of a histogram against a grid density (csrc/grid_locate.h): the row maximum by grid_modes.h's arg-max pass, one pass, its finalise.
 static int grid_fit_check(const RnfGridFit *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridFit)) return fail("RnfGridFit.struct_bytes does not match the library's %zu", sizeof(RnfGridFit));
+    if (check_struct(p, "RnfGridFit")) return 1;
     if (p->g < 1 || p->g > 65535) return fail("RnfGridFit.g=%d outside 1..65535", p->g);
     if (p->Q < 1 || p->Q > gl::MAX_Q) return fail("RnfGridFit.Q=%lld outside 1..2^26", (long long)p->Q);
     return 0;
@@ -1642,20 +1658,13 @@ extern "C" int rnf_grid_fit(const RnfGridFit *p) {
     if (grid_fit_check(p)) return 1;
     if (!p->logp || !p->counts || !p->stats_out) return fail("RnfGridFit: null logp, counts or stats_out");
     const size_t need = rnf_grid_fit_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfGridFit.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_fit_workspace_bytes)", p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridFit.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfGridFit", need, "rnf_grid_fit_workspace_bytes", 8)) return 1;
     static_assert(gl::N_STATS == RNF_GRID_FIT_STATS, "csrc/grid_locate.h and include/rnf_hip.h disagree on the statistics");
     const gl::Workspace w = gl::carve(p->workspace, p->Q, p->g);
     const long long Q = p->Q;
-    const int nbm = (int)gm::blocks_for(Q), nb = (int)gl::blocks_for(Q);
+    const int nb = (int)gl::blocks_for(Q);
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
-                       (const long long *)w.max_index, (const float *)w.max_value, w.max_part);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
-                       w.max_index, w.max_value);
-    HIP_TRY(hipGetLastError());
+    if (launch_row_max(p->logp, Q, p->g, w.max_part, w.max_index, w.max_value, s)) return 1;
     hipLaunchKernelGGL(gl::grid_fit_kernel, dim3(nb, p->g), dim3(gl::THREADS), 0, s, p->logp, (const int *)p->counts, Q,
                        (const float *)w.max_value, w.part);
     HIP_TRY(hipGetLastError());
@@ -1667,8 +1676,7 @@ extern "C" int rnf_grid_fit(const RnfGridFit *p) {
 
 // The chart of a grid cell (csrc/grid_sample.h): one thread per point.
 extern "C" int rnf_so3_grid_cell_points(const RnfGridCellPoints *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridCellPoints))
-        return fail("RnfGridCellPoints.struct_bytes does not match the library's %zu", sizeof(RnfGridCellPoints));
+    if (check_struct(p, "RnfGridCellPoints")) return 1;
     if (p->level < 0 || p->level > gsa::MAX_LEVEL) return fail("RnfGridCellPoints.level=%d outside 0..%d", p->level, gsa::MAX_LEVEL);
     if (p->n < 0 || p->n > (1LL << 36)) return fail("RnfGridCellPoints.n=%lld outside 0..2^36", (long long)p->n);
     if (p->n == 0) return 0;
@@ -1683,8 +1691,7 @@ extern "C" int rnf_so3_grid_cell_points(const RnfGridCellPoints *p) {
 
 // Draws from grid posteriors (csrc/grid_sample.h): the row maximum by grid_modes.h's arg-max pass, the chunk sums, their scan, the draws.
 static int grid_sample_check(const RnfGridSample *p) {
-    if (!p || p->struct_bytes != sizeof(RnfGridSample))
-        return fail("RnfGridSample.struct_bytes does not match the library's %zu", sizeof(RnfGridSample));
+    if (check_struct(p, "RnfGridSample")) return 1;
     if (p->g < 1 || p->g > 65535) return fail("RnfGridSample.g=%d outside 1..65535", p->g);
     if (p->Q < 1 || p->Q > gsa::MAX_Q) return fail("RnfGridSample.Q=%lld outside 1..2^26", (long long)p->Q);
     return 0;
@@ -1715,21 +1722,13 @@ extern "C" int rnf_grid_sample(const RnfGridSample *p) {
     if (!p->logp) return fail("RnfGridSample: null logp");
     if (p->draws > 0 && !p->index_out) return fail("RnfGridSample: null index_out");
     const size_t need = rnf_grid_sample_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfGridSample.workspace of %zu bytes is smaller than the %zu needed (rnf_grid_sample_workspace_bytes)", p->workspace_bytes,
-                    need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfGridSample.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfGridSample", need, "rnf_grid_sample_workspace_bytes", 8)) return 1;
     const long long Q = p->Q, nc = gsa::chunks_for(Q);
     const int nbm = (int)gm::blocks_for(Q), nbs = (int)gsa::sum_blocks_for(Q);
     const gsa::Workspace w = gsa::carve(p->workspace, Q, p->g, nbm);
     const double scale = ldexp(1.0, gc::fixed_point_shift(Q));
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(gm::grid_modes_argmax_kernel, dim3(nbm, p->g), dim3(gm::THREADS), 0, s, p->logp, (const float *)nullptr, Q, 1, 0, 0.0f,
-                       (const long long *)w.max_index, (const float *)w.max_value, (gm::ArgPart *)w.max_part);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(gm::grid_modes_argmax_final_kernel, dim3(p->g), dim3(gm::THREADS), 0, s, (const gm::ArgPart *)w.max_part, nbm, 1, 0,
-                       w.max_index, w.max_value);
-    HIP_TRY(hipGetLastError());
+    if (launch_row_max(p->logp, Q, p->g, (gm::ArgPart *)w.max_part, w.max_index, w.max_value, s)) return 1;
     hipLaunchKernelGGL(gsa::grid_sample_sum_kernel, dim3(nbs, p->g), dim3(gsa::THREADS), 0, s, p->logp, Q, nc, scale, (const float *)w.max_value,
                        w.prefix);
     HIP_TRY(hipGetLastError());
@@ -1746,10 +1745,20 @@ extern "C" int rnf_grid_sample(const RnfGridSample *p) {
     return 0;
 }
 
+// log Z of G rows of log-weights over n centres -> log_z[G]: so3_kernel_sum.h's weights pass and its finalise.  The prologue of the kernel
+// sums, the kernel moments, the two angle distributions and the Fourier coefficients.
+static int launch_log_z(const float *centres, const float *log_weights, int n, int G, ks::WeightPart *wpart, double *log_z, hipStream_t s) {
+    const int nchunk = (int)ks::chunks_for(n);
+    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, G), dim3(ks::THREADS), 0, s, centres, log_weights, n, wpart);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(G), dim3(64), 0, s, (const ks::WeightPart *)wpart, nchunk, log_z);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Pairwise matrix-Fisher kernel sums (csrc/so3_kernel_sum.h): the weights pass and its finalise, the pairwise pass, its finalise.
 static int so3_kernel_sum_check(const RnfSo3KernelSum *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3KernelSum))
-        return fail("RnfSo3KernelSum.struct_bytes does not match the library's %zu", sizeof(RnfSo3KernelSum));
+    if (check_struct(p, "RnfSo3KernelSum")) return 1;
     if (p->J < 1 || p->J > ks::MAX_J) return fail("RnfSo3KernelSum.J=%d outside 1..%d", p->J, ks::MAX_J);
     if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3KernelSum.G=%d outside 1..65535", p->G);
     if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3KernelSum.n=%lld outside 1..2^24", (long long)p->n);
@@ -1778,8 +1787,7 @@ extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
     for (int a = 0; a < p->J; ++a)
         if (!(p->kappas[a] >= 0.0 && p->kappas[a] <= ks::MAX_KAPPA))
             return fail("RnfSo3KernelSum.kappas[%d]=%g outside 0..1e6", a, p->kappas[a]);
-    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
-        return fail("RnfSo3KernelSum: centres and queries must be 16-byte aligned");
+    if (check_aligned16(p->centres, p->queries, "RnfSo3KernelSum", ": centres and queries")) return 1;
     const bool loo = p->leave_one_out != 0;
     if (loo && (p->m != p->n || (p->queries && p->queries != p->centres)))
         return fail("RnfSo3KernelSum.leave_one_out: the queries must be the centres (queries NULL or == centres, m == n)");
@@ -1787,10 +1795,7 @@ extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
     if (p->m == 0) return 0;
     if (!p->centres || !p->out) return fail("RnfSo3KernelSum: null centres or out");
     const size_t need = ks::carve(nullptr, p->n, p->m, p->G, p->J).bytes;
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3KernelSum.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_kernel_sum_workspace_bytes)", p->workspace_bytes,
-                    need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3KernelSum.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfSo3KernelSum", need, "rnf_so3_kernel_sum_workspace_bytes", 8)) return 1;
     const ks::Workspace w = ks::carve(p->workspace, p->n, p->m, p->G, p->J);
     ks::Scales sc;
     ks::Normalisers nm;
@@ -1798,10 +1803,7 @@ extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
     const float *Q = p->queries ? p->queries : p->centres;
     const int nchunk = (int)ks::chunks_for(p->n);
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
-    HIP_TRY(hipGetLastError());
+    if (launch_log_z(p->centres, p->log_weights, (int)p->n, p->G, w.wpart, w.log_z, s)) return 1;
 #define RNF_KS_CASE(J)                                                                 \
     case J:                                                                            \
         if (loo) so3_kernel_sum_launch<J, 1, true>(p, Q, sc, w, s);                    \
@@ -1826,8 +1828,7 @@ extern "C" int rnf_so3_kernel_sum(const RnfSo3KernelSum *p) {
 // Moments of the same kernel sum (csrc/so3_kernel_moments.h): the weights pass and its finalise, the chunk flags, the pairwise pass, its
 // finalise.
 static int so3_kernel_moments_check(const RnfSo3KernelMoments *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3KernelMoments))
-        return fail("RnfSo3KernelMoments.struct_bytes does not match the library's %zu", sizeof(RnfSo3KernelMoments));
+    if (check_struct(p, "RnfSo3KernelMoments")) return 1;
     if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3KernelMoments.G=%d outside 1..65535", p->G);
     if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3KernelMoments.n=%lld outside 1..2^24", (long long)p->n);
     if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3KernelMoments.m=%lld outside 0..2^31-1", (long long)p->m);
@@ -1845,17 +1846,13 @@ extern "C" size_t rnf_so3_kernel_moments_workspace_bytes(const RnfSo3KernelMomen
 extern "C" int rnf_so3_kernel_moments(const RnfSo3KernelMoments *p) {
     if (so3_kernel_moments_check(p)) return 1;
     if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("RnfSo3KernelMoments.kappa=%g outside 0..1e6", p->kappa);
-    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
-        return fail("RnfSo3KernelMoments: centres and queries must be 16-byte aligned");
+    if (check_aligned16(p->centres, p->queries, "RnfSo3KernelMoments", ": centres and queries")) return 1;
     if (p->step && !p->rotation) return fail("RnfSo3KernelMoments.step requires rotation");
     if (p->dlog_normaliser) *p->dlog_normaliser = km::dlog_normaliser(p->kappa);
     if (p->m == 0) return 0;
     if (!p->centres || !p->queries) return fail("RnfSo3KernelMoments: null centres or queries");
     const size_t need = km::carve(nullptr, p->n, p->m, p->G).bytes;
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3KernelMoments.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_kernel_moments_workspace_bytes)",
-                    p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3KernelMoments.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfSo3KernelMoments", need, "rnf_so3_kernel_moments_workspace_bytes", 8)) return 1;
     const km::Workspace w = km::carve(p->workspace, p->n, p->m, p->G);
     ks::Scales sc;
     ks::Normalisers nm;
@@ -1864,10 +1861,7 @@ extern "C" int rnf_so3_kernel_moments(const RnfSo3KernelMoments *p) {
     const unsigned blocks = (unsigned)((p->m + ks::THREADS - 1) / ks::THREADS);
     const long long q_group = p->group_queries ? 9 * (long long)p->m : 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
-    HIP_TRY(hipGetLastError());
+    if (launch_log_z(p->centres, p->log_weights, (int)p->n, p->G, w.wpart, w.log_z, s)) return 1;
     hipLaunchKernelGGL(km::so3_kernel_moments_flags_kernel, dim3(nchunk), dim3(ks::THREADS), 0, s, p->centres, (int)p->n, w.flags);
     HIP_TRY(hipGetLastError());
     const int block = km::block_for(p->m, nchunk, p->G);
@@ -1882,24 +1876,44 @@ extern "C" int rnf_so3_kernel_moments(const RnfSo3KernelMoments *p) {
     return 0;
 }
 
-// The distribution function of the geodesic angle (csrc/so3_angle_cdf.h): the weights pass and its finalise, the normalised weights, the
-// pairwise pass, its finalise.
-static int so3_angle_cdf_slots(const RnfSo3AngleCdf *p) { return (p->mass ? p->T : 0) + (p->mean_angle || p->mean_sq_angle ? 2 : 0); }
+// The distribution function of the geodesic angle to a query (csrc/so3_angle_cdf.h) and to the nearest member of a set
+// (csrc/so3_set_angle_cdf.h): one computation, a query being a set of one member.  launch_log_z, the normalised weights, the pairwise
+// pass of the entry (so3_angle_cdf_launch), the finalise for sets of K.  What differs between the two structs is here:
+template <class P>
+struct So3AngleCdfEntry;
+template <>
+struct So3AngleCdfEntry<RnfSo3AngleCdf> {
+    static constexpr bool sets = false;
+    static constexpr const char *who = "RnfSo3AngleCdf", *noun = "queries", *workspace_fn = "rnf_so3_angle_cdf_workspace_bytes";
+    static int K(const RnfSo3AngleCdf *) { return 1; }
+};
+template <>
+struct So3AngleCdfEntry<RnfSo3SetAngleCdf> {
+    static constexpr bool sets = true;
+    static constexpr const char *who = "RnfSo3SetAngleCdf", *noun = "sets", *workspace_fn = "rnf_so3_set_angle_cdf_workspace_bytes";
+    static int K(const RnfSo3SetAngleCdf *p) { return p->K; }
+};
 
-static int so3_angle_cdf_check(const RnfSo3AngleCdf *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3AngleCdf))
-        return fail("RnfSo3AngleCdf.struct_bytes does not match the library's %zu", sizeof(RnfSo3AngleCdf));
-    if (p->T < 0 || p->T > ac::MAX_T) return fail("RnfSo3AngleCdf.T=%d outside 0..%d", p->T, ac::MAX_T);
-    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3AngleCdf.G=%d outside 1..65535", p->G);
-    if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3AngleCdf.n=%lld outside 1..2^24", (long long)p->n);
-    if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3AngleCdf.m=%lld outside 0..2^31-1", (long long)p->m);
+template <class P>
+static int so3_angle_cdf_slots(const P *p) { return (p->mass ? p->T : 0) + (p->mean_angle || p->mean_sq_angle ? 2 : 0); }
+
+template <class P>
+static int so3_angle_cdf_check(const P *p) {
+    using E = So3AngleCdfEntry<P>;
+    if (check_struct(p, E::who)) return 1;
+    if (p->T < 0 || p->T > ac::MAX_T) return fail("%s.T=%d outside 0..%d", E::who, p->T, ac::MAX_T);
+    if (p->G < 1 || p->G > ks::MAX_G) return fail("%s.G=%d outside 1..65535", E::who, p->G);
+    if (E::sets && (E::K(p) < 1 || E::K(p) > sac::MAX_K)) return fail("%s.K=%d outside 1..%d", E::who, E::K(p), sac::MAX_K);
+    if (p->n < 1 || p->n > ks::MAX_N) return fail("%s.n=%lld outside 1..2^24", E::who, (long long)p->n);
+    if (p->m < 0 || p->m > ks::MAX_M) return fail("%s.m=%lld outside 0..2^31-1", E::who, (long long)p->m);
     if (ac::carve(nullptr, p->n, p->m, p->G, so3_angle_cdf_slots(p)).bytes == 0)
-        return fail("RnfSo3AngleCdf: the workspace of G=%d, T=%d, n=%lld, m=%lld does not fit; tile the queries", p->G, p->T, (long long)p->n,
-                    (long long)p->m);
+        return fail("%s: the workspace of G=%d, T=%d, n=%lld, m=%lld does not fit; tile the %s", E::who, p->G, p->T, (long long)p->n,
+                    (long long)p->m, E::noun);
     return 0;
 }
 
-extern "C" size_t rnf_so3_angle_cdf_workspace_bytes(const RnfSo3AngleCdf *p) {
+template <class P>
+static size_t so3_angle_cdf_workspace_bytes(const P *p) {
     if (so3_angle_cdf_check(p)) return 0;
     return ac::carve(nullptr, p->n, p->m, p->G, so3_angle_cdf_slots(p)).bytes;
 }
@@ -1922,85 +1936,8 @@ static void so3_angle_cdf_launch(const RnfSo3AngleCdf *p, int T, const ac::Taus 
 #undef RNF_AC_LAUNCH
 }
 
-extern "C" int rnf_so3_angle_cdf(const RnfSo3AngleCdf *p) {
-    if (so3_angle_cdf_check(p)) return 1;
-    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
-        return fail("RnfSo3AngleCdf: centres and queries must be 16-byte aligned");
-    const bool mom = p->mean_angle || p->mean_sq_angle;
-    if (p->T == 0 && !mom) return fail("RnfSo3AngleCdf.T=0 requires mean_angle or mean_sq_angle");
-    if (p->T == 0 && (p->thresholds || p->query_tau)) return fail("RnfSo3AngleCdf.T=0 with thresholds or query_tau");
-    if (p->T > 0 && p->thresholds && p->query_tau) return fail("RnfSo3AngleCdf: both thresholds and query_tau are given; exactly one of the two");
-    if (p->T > 0 && !p->thresholds && !p->query_tau) return fail("RnfSo3AngleCdf: neither thresholds nor query_tau is given for T=%d", p->T);
-    ac::Taus taus;
-    for (int t = 0; t < ac::MAX_T; ++t) taus.t[t] = -1.f;
-    if (p->T > 0 && p->thresholds)
-        for (int t = 0; t < p->T; ++t) {
-            if (!(p->thresholds[t] >= 0.0 && p->thresholds[t] <= ac::PI))
-                return fail("RnfSo3AngleCdf.thresholds[%d]=%g outside 0..pi", t, p->thresholds[t]);
-            taus.t[t] = ac::tau_of(p->thresholds[t]);
-        }
-    if (p->m == 0) return 0;
-    if (!p->centres || !p->queries) return fail("RnfSo3AngleCdf: null centres or queries");
-    const int T = p->mass ? p->T : 0;              // masses nobody takes are not computed
-    if (T == 0 && !mom) return 0;
-    const size_t need = ac::carve(nullptr, p->n, p->m, p->G, so3_angle_cdf_slots(p)).bytes;
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3AngleCdf.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_angle_cdf_workspace_bytes)", p->workspace_bytes,
-                    need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3AngleCdf.workspace must be 8-byte aligned");
-    const ac::Workspace w = ac::carve(p->workspace, p->n, p->m, p->G, so3_angle_cdf_slots(p));
-    const int nchunk = (int)ks::chunks_for(p->n);
-    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ac::so3_angle_cdf_weights_kernel, dim3((unsigned)((p->n + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
-                       p->log_weights, (const double *)w.log_z, (int)p->n, w.wn);
-    HIP_TRY(hipGetLastError());
-#define RNF_AC_CASE(TT)                                                    \
-    case TT:                                                               \
-        if (mom) so3_angle_cdf_launch<TT, true>(p, T, taus, w, s);         \
-        else so3_angle_cdf_launch<TT, false>(p, T, taus, w, s);            \
-        break;
-    switch (ac::slots_for(T)) {
-        case 0: so3_angle_cdf_launch<0, true>(p, T, taus, w, s); break;
-        RNF_AC_CASE(1) RNF_AC_CASE(2) RNF_AC_CASE(4) RNF_AC_CASE(8)
-    }
-#undef RNF_AC_CASE
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ac::so3_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
-                       (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m : 0LL, (int)p->m, nchunk, T, (int)mom, taus,
-                       T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The distribution function of the angle to the nearest member of a set (csrc/so3_set_angle_cdf.h): rnf_so3_angle_cdf's five launches
-// with the set kernels in place of the pairwise pass and its finalise.
-static int so3_set_angle_cdf_slots(const RnfSo3SetAngleCdf *p) { return (p->mass ? p->T : 0) + (p->mean_angle || p->mean_sq_angle ? 2 : 0); }
-
-static int so3_set_angle_cdf_check(const RnfSo3SetAngleCdf *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3SetAngleCdf))
-        return fail("RnfSo3SetAngleCdf.struct_bytes does not match the library's %zu", sizeof(RnfSo3SetAngleCdf));
-    if (p->T < 0 || p->T > sac::MAX_T) return fail("RnfSo3SetAngleCdf.T=%d outside 0..%d", p->T, sac::MAX_T);
-    if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3SetAngleCdf.G=%d outside 1..65535", p->G);
-    if (p->K < 1 || p->K > sac::MAX_K) return fail("RnfSo3SetAngleCdf.K=%d outside 1..%d", p->K, sac::MAX_K);
-    if (p->n < 1 || p->n > ks::MAX_N) return fail("RnfSo3SetAngleCdf.n=%lld outside 1..2^24", (long long)p->n);
-    if (p->m < 0 || p->m > ks::MAX_M) return fail("RnfSo3SetAngleCdf.m=%lld outside 0..2^31-1", (long long)p->m);
-    if (ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes == 0)
-        return fail("RnfSo3SetAngleCdf: the workspace of G=%d, T=%d, n=%lld, m=%lld does not fit; tile the sets", p->G, p->T, (long long)p->n,
-                    (long long)p->m);
-    return 0;
-}
-
-extern "C" size_t rnf_so3_set_angle_cdf_workspace_bytes(const RnfSo3SetAngleCdf *p) {
-    if (so3_set_angle_cdf_check(p)) return 0;
-    return ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes;
-}
-
 template <int TT, bool MOM>
-static void so3_set_angle_cdf_launch(const RnfSo3SetAngleCdf *p, int T, const ac::Taus &taus, const ac::Workspace &w, hipStream_t s) {
+static void so3_angle_cdf_launch(const RnfSo3SetAngleCdf *p, int T, const ac::Taus &taus, const ac::Workspace &w, hipStream_t s) {
     constexpr int GBS = sac::groups_for(TT + (MOM ? 2 : 0));
     const int nchunk = (int)ks::chunks_for(p->n);
     const long long q_group = p->group_queries ? 9 * (long long)p->m * p->K : 0;
@@ -2028,60 +1965,59 @@ static void so3_set_angle_cdf_launch(const RnfSo3SetAngleCdf *p, int T, const ac
 #undef RNF_SAC_LAUNCH
 }
 
-extern "C" int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *p) {
-    if (so3_set_angle_cdf_check(p)) return 1;
-    if (reinterpret_cast<uintptr_t>(p->centres) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
-        return fail("RnfSo3SetAngleCdf: centres and queries must be 16-byte aligned");
+template <class P>
+static int so3_angle_cdf_run(const P *p) {
+    using E = So3AngleCdfEntry<P>;
+    if (so3_angle_cdf_check(p)) return 1;
+    if (check_aligned16(p->centres, p->queries, E::who, ": centres and queries")) return 1;
     const bool mom = p->mean_angle || p->mean_sq_angle;
-    if (p->T == 0 && !mom) return fail("RnfSo3SetAngleCdf.T=0 requires mean_angle or mean_sq_angle");
-    if (p->T == 0 && (p->thresholds || p->query_tau)) return fail("RnfSo3SetAngleCdf.T=0 with thresholds or query_tau");
-    if (p->T > 0 && p->thresholds && p->query_tau)
-        return fail("RnfSo3SetAngleCdf: both thresholds and query_tau are given; exactly one of the two");
-    if (p->T > 0 && !p->thresholds && !p->query_tau) return fail("RnfSo3SetAngleCdf: neither thresholds nor query_tau is given for T=%d", p->T);
+    if (p->T == 0 && !mom) return fail("%s.T=0 requires mean_angle or mean_sq_angle", E::who);
+    if (p->T == 0 && (p->thresholds || p->query_tau)) return fail("%s.T=0 with thresholds or query_tau", E::who);
+    if (p->T > 0 && p->thresholds && p->query_tau) return fail("%s: both thresholds and query_tau are given; exactly one of the two", E::who);
+    if (p->T > 0 && !p->thresholds && !p->query_tau) return fail("%s: neither thresholds nor query_tau is given for T=%d", E::who, p->T);
     ac::Taus taus;
     for (int t = 0; t < ac::MAX_T; ++t) taus.t[t] = -1.f;
     if (p->T > 0 && p->thresholds)
         for (int t = 0; t < p->T; ++t) {
             if (!(p->thresholds[t] >= 0.0 && p->thresholds[t] <= ac::PI))
-                return fail("RnfSo3SetAngleCdf.thresholds[%d]=%g outside 0..pi", t, p->thresholds[t]);
+                return fail("%s.thresholds[%d]=%g outside 0..pi", E::who, t, p->thresholds[t]);
             taus.t[t] = ac::tau_of(p->thresholds[t]);
         }
     if (p->m == 0) return 0;
-    if (!p->centres || !p->queries) return fail("RnfSo3SetAngleCdf: null centres or queries");
+    if (!p->centres || !p->queries) return fail("%s: null centres or queries", E::who);
     const int T = p->mass ? p->T : 0;              // masses nobody takes are not computed
     if (T == 0 && !mom) return 0;
-    const size_t need = ac::carve(nullptr, p->n, p->m, p->G, so3_set_angle_cdf_slots(p)).bytes;
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3SetAngleCdf.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_set_angle_cdf_workspace_bytes)",
-                    p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfSo3SetAngleCdf.workspace must be 8-byte aligned");
-    const ac::Workspace w = ac::carve(p->workspace, p->n, p->m, p->G, so3_set_angle_cdf_slots(p));
-    const int nchunk = (int)ks::chunks_for(p->n);
+    const size_t need = ac::carve(nullptr, p->n, p->m, p->G, so3_angle_cdf_slots(p)).bytes;
+    if (check_workspace(p, E::who, need, E::workspace_fn, 8)) return 1;
+    const ac::Workspace w = ac::carve(p->workspace, p->n, p->m, p->G, so3_angle_cdf_slots(p));
+    const int nchunk = (int)ks::chunks_for(p->n), K = E::K(p);
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
-    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, p->G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, (int)p->n, w.wpart);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(p->G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
-    HIP_TRY(hipGetLastError());
+    if (launch_log_z(p->centres, p->log_weights, (int)p->n, p->G, w.wpart, w.log_z, s)) return 1;
     hipLaunchKernelGGL(ac::so3_angle_cdf_weights_kernel, dim3((unsigned)((p->n + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
                        p->log_weights, (const double *)w.log_z, (int)p->n, w.wn);
     HIP_TRY(hipGetLastError());
-#define RNF_SAC_CASE(TT)                                                       \
-    case TT:                                                                   \
-        if (mom) so3_set_angle_cdf_launch<TT, true>(p, T, taus, w, s);         \
-        else so3_set_angle_cdf_launch<TT, false>(p, T, taus, w, s);            \
+#define RNF_AC_CASE(TT)                                                    \
+    case TT:                                                               \
+        if (mom) so3_angle_cdf_launch<TT, true>(p, T, taus, w, s);         \
+        else so3_angle_cdf_launch<TT, false>(p, T, taus, w, s);            \
         break;
     switch (ac::slots_for(T)) {
-        case 0: so3_set_angle_cdf_launch<0, true>(p, T, taus, w, s); break;
-        RNF_SAC_CASE(1) RNF_SAC_CASE(2) RNF_SAC_CASE(4) RNF_SAC_CASE(8)
+        case 0: so3_angle_cdf_launch<0, true>(p, T, taus, w, s); break;
+        RNF_AC_CASE(1) RNF_AC_CASE(2) RNF_AC_CASE(4) RNF_AC_CASE(8)
     }
-#undef RNF_SAC_CASE
+#undef RNF_AC_CASE
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sac::so3_set_angle_cdf_final_kernel, dim3((unsigned)((p->m + ks::THREADS - 1) / ks::THREADS), p->G), dim3(ks::THREADS), 0, s,
-                       (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m * p->K : 0LL, (int)p->m, (int)p->K, nchunk, T,
-                       (int)mom, taus, T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
+                       (const double *)w.psum, p->queries, p->group_queries ? 9 * (long long)p->m * K : 0LL, (int)p->m, K, nchunk, T, (int)mom, taus,
+                       T > 0 ? p->query_tau : (const float *)nullptr, p->mass, p->mean_angle, p->mean_sq_angle);
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+extern "C" size_t rnf_so3_angle_cdf_workspace_bytes(const RnfSo3AngleCdf *p) { return so3_angle_cdf_workspace_bytes(p); }
+extern "C" int rnf_so3_angle_cdf(const RnfSo3AngleCdf *p) { return so3_angle_cdf_run(p); }
+extern "C" size_t rnf_so3_set_angle_cdf_workspace_bytes(const RnfSo3SetAngleCdf *p) { return so3_angle_cdf_workspace_bytes(p); }
+extern "C" int rnf_so3_set_angle_cdf(const RnfSo3SetAngleCdf *p) { return so3_angle_cdf_run(p); }
 
 // Harmonic analysis on SO(3) (csrc/so3_harmonics.h).  Every entry first writes the entry records into its workspace.
 static int so3_harmonics_records(int L, float *records, hipStream_t s) {
@@ -2092,7 +2028,7 @@ static int so3_harmonics_records(int L, float *records, hipStream_t s) {
 }
 
 static int so3_wigner_check(const RnfSo3Wigner *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3Wigner)) return fail("RnfSo3Wigner.struct_bytes does not match the library's %zu", sizeof(RnfSo3Wigner));
+    if (check_struct(p, "RnfSo3Wigner")) return 1;
     if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3Wigner.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
     if (p->n < 0 || p->n > sh::MAX_N) return fail("RnfSo3Wigner.n=%lld outside 0..2^24", (long long)p->n);
     return 0;
@@ -2105,9 +2041,7 @@ extern "C" int rnf_so3_wigner(const RnfSo3Wigner *p) {
     if (p->n == 0) return 0;
     if (!p->rotations || !p->out) return fail("RnfSo3Wigner: null rotations or out");
     const size_t need = sh::records_bytes(p->lmax);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3Wigner.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_wigner_workspace_bytes)", p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3Wigner.workspace must be 16-byte aligned");
+    if (check_workspace(p, "RnfSo3Wigner", need, "rnf_so3_wigner_workspace_bytes", 16)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
     float *records = static_cast<float *>(p->workspace);
     if (so3_harmonics_records(p->lmax, records, s)) return 1;
@@ -2118,7 +2052,7 @@ extern "C" int rnf_so3_wigner(const RnfSo3Wigner *p) {
 }
 
 static int so3_fourier_check(const RnfSo3Fourier *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3Fourier)) return fail("RnfSo3Fourier.struct_bytes does not match the library's %zu", sizeof(RnfSo3Fourier));
+    if (check_struct(p, "RnfSo3Fourier")) return 1;
     if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3Fourier.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
     if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3Fourier.G=%d outside 1..65535", p->G);
     if (p->n < 1 || p->n > sh::MAX_N) return fail("RnfSo3Fourier.n=%lld outside 1..2^24", (long long)p->n);
@@ -2133,17 +2067,12 @@ extern "C" int rnf_so3_fourier(const RnfSo3Fourier *p) {
     if (so3_fourier_check(p)) return 1;
     if (!p->centres || !p->out) return fail("RnfSo3Fourier: null centres or out");
     const size_t need = sh::carve(nullptr, p->n, p->G, p->lmax).bytes;
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3Fourier.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_fourier_workspace_bytes)", p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3Fourier.workspace must be 16-byte aligned");
+    if (check_workspace(p, "RnfSo3Fourier", need, "rnf_so3_fourier_workspace_bytes", 16)) return 1;
     const sh::Workspace w = sh::carve(p->workspace, p->n, p->G, p->lmax);
     const int nchunk = (int)ks::chunks_for(p->n), L = p->lmax, n = (int)p->n, G = p->G, CL = sh::coefficient_count(L);
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
     if (so3_harmonics_records(L, w.records, s)) return 1;
-    hipLaunchKernelGGL(ks::so3_kernel_weights_kernel, dim3(nchunk, G), dim3(ks::THREADS), 0, s, p->centres, p->log_weights, n, w.wpart);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ks::so3_kernel_weights_final_kernel, dim3(G), dim3(64), 0, s, (const ks::WeightPart *)w.wpart, nchunk, w.log_z);
-    HIP_TRY(hipGetLastError());
+    if (launch_log_z(p->centres, p->log_weights, n, G, w.wpart, w.log_z, s)) return 1;
     hipLaunchKernelGGL(ac::so3_angle_cdf_weights_kernel, dim3((unsigned)((n + ks::THREADS - 1) / ks::THREADS), G), dim3(ks::THREADS), 0, s,
                        p->log_weights, (const double *)w.log_z, n, w.wn);
     HIP_TRY(hipGetLastError());
@@ -2166,8 +2095,7 @@ extern "C" int rnf_so3_fourier(const RnfSo3Fourier *p) {
 }
 
 static int so3_fourier_eval_check(const RnfSo3FourierEval *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3FourierEval))
-        return fail("RnfSo3FourierEval.struct_bytes does not match the library's %zu", sizeof(RnfSo3FourierEval));
+    if (check_struct(p, "RnfSo3FourierEval")) return 1;
     if (p->lmax < 0 || p->lmax > sh::MAX_DEGREE) return fail("RnfSo3FourierEval.lmax=%d outside 0..%d", p->lmax, sh::MAX_DEGREE);
     if (p->G < 1 || p->G > ks::MAX_G) return fail("RnfSo3FourierEval.G=%d outside 1..65535", p->G);
     if (p->m < 0 || p->m > sh::MAX_M) return fail("RnfSo3FourierEval.m=%lld outside 0..2^31-1", (long long)p->m);
@@ -2183,10 +2111,7 @@ extern "C" int rnf_so3_fourier_eval(const RnfSo3FourierEval *p) {
     if (p->m == 0) return 0;
     if (!p->coeffs || !p->queries || !p->out) return fail("RnfSo3FourierEval: null coeffs, queries or out");
     const size_t need = sh::records_bytes(p->lmax);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfSo3FourierEval.workspace of %zu bytes is smaller than the %zu needed (rnf_so3_fourier_eval_workspace_bytes)",
-                    p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 16) return fail("RnfSo3FourierEval.workspace must be 16-byte aligned");
+    if (check_workspace(p, "RnfSo3FourierEval", need, "rnf_so3_fourier_eval_workspace_bytes", 16)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
     float *records = static_cast<float *>(p->workspace);
     if (so3_harmonics_records(p->lmax, records, s)) return 1;
@@ -2214,15 +2139,13 @@ static void so3_grid_local_launch(const RnfSo3GridLocalSum *p, const sgl::Geomet
 }
 
 extern "C" int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *p) {
-    if (!p || p->struct_bytes != sizeof(RnfSo3GridLocalSum))
-        return fail("RnfSo3GridLocalSum.struct_bytes does not match the library's %zu", sizeof(RnfSo3GridLocalSum));
+    if (check_struct(p, "RnfSo3GridLocalSum")) return 1;
     if (p->level < 0 || p->level > sgl::MAX_LEVEL) return fail("RnfSo3GridLocalSum.level=%d outside 0..%d", p->level, sgl::MAX_LEVEL);
     if (p->G < 1 || p->G > sgl::MAX_G) return fail("RnfSo3GridLocalSum.G=%d outside 1..65535", p->G);
     if (p->m < 0 || p->m > sgl::MAX_M) return fail("RnfSo3GridLocalSum.m=%lld outside 0..2^31-1", (long long)p->m);
     if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("RnfSo3GridLocalSum.kappa=%g outside 0..1e6", p->kappa);
     if (!(p->d2_cut >= 0.0 && p->d2_cut <= sgl::MAX_D2)) return fail("RnfSo3GridLocalSum.d2_cut=%g outside 0..8", p->d2_cut);
-    if (reinterpret_cast<uintptr_t>(p->grid) % 16 || reinterpret_cast<uintptr_t>(p->queries) % 16)
-        return fail("RnfSo3GridLocalSum: grid and queries must be 16-byte aligned");
+    if (check_aligned16(p->grid, p->queries, "RnfSo3GridLocalSum", ": grid and queries")) return 1;
     if (reinterpret_cast<uintptr_t>(p->offset) % 4 || reinterpret_cast<uintptr_t>(p->log_weights) % 4 || reinterpret_cast<uintptr_t>(p->out) % 4 ||
         reinterpret_cast<uintptr_t>(p->count) % 4)
         return fail("RnfSo3GridLocalSum: offset, log_weights, out and count must be 4-byte aligned");
@@ -2410,7 +2333,7 @@ __global__ __launch_bounds__(256) void fisher_fit_kernel(const double *moments, 
 }
 
 extern "C" int rnf_fisher_fit(const RnfFisherFit *p) {
-    if (!p || p->struct_bytes != sizeof(RnfFisherFit)) return fail("RnfFisherFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherFit));
+    if (check_struct(p, "RnfFisherFit")) return 1;
     if (p->B < 0) return fail("RnfFisherFit.B=%lld", (long long)p->B);
     if (!(p->max_concentration > 0.0 && p->max_concentration <= 3e4))
         return fail("RnfFisherFit.max_concentration=%g outside (0, 3e4]", p->max_concentration);
@@ -2518,8 +2441,7 @@ __global__ __launch_bounds__(64) void rotation_moments_final_kernel(const double
 }  // namespace rmom
 
 static int rotation_moments_check(const RnfRotationMoments *p) {
-    if (!p || p->struct_bytes != sizeof(RnfRotationMoments))
-        return fail("RnfRotationMoments.struct_bytes does not match the library's %zu", sizeof(RnfRotationMoments));
+    if (check_struct(p, "RnfRotationMoments")) return 1;
     if (p->G < 1) return fail("RnfRotationMoments.G=%lld must be >= 1", (long long)p->G);
     if (p->n < 1 || p->n > (1LL << 40)) return fail("RnfRotationMoments.n=%lld outside 1..2^40", (long long)p->n);
     if ((double)p->G * (double)rmom::chunks_for(p->n) > 2147483647.0)
@@ -2537,10 +2459,7 @@ extern "C" int rnf_rotation_moments(const RnfRotationMoments *p) {
     if (!p->rotations || !p->moments_out) return fail("RnfRotationMoments: null rotations or moments_out");
     if (p->shared_rotations && !p->log_weights) return fail("RnfRotationMoments.shared_rotations needs log_weights (every group would get the same moment)");
     const size_t need = rnf_rotation_moments_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfRotationMoments.workspace of %zu bytes is smaller than the %zu needed (rnf_rotation_moments_workspace_bytes)", p->workspace_bytes,
-                    need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfRotationMoments.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfRotationMoments", need, "rnf_rotation_moments_workspace_bytes", 8)) return 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
     const long long nchunk = rmom::chunks_for(p->n);
     const unsigned blocks = (unsigned)(p->G * nchunk);
@@ -2798,8 +2717,7 @@ static inline long long chunks_for(long long n) { return (n + kMixChunk - 1) / k
     }
 
 static int fisher_mixture_check(const RnfFisherMixtureFit *p) {
-    if (!p || p->struct_bytes != sizeof(RnfFisherMixtureFit))
-        return fail("RnfFisherMixtureFit.struct_bytes does not match the library's %zu", sizeof(RnfFisherMixtureFit));
+    if (check_struct(p, "RnfFisherMixtureFit")) return 1;
     if (p->G < 1 || p->G > 0x7fffffffLL) return fail("RnfFisherMixtureFit.G=%lld outside 1..2^31-1", (long long)p->G);
     if (p->n < 1 || p->n > (1LL << 40)) return fail("RnfFisherMixtureFit.n=%lld outside 1..2^40", (long long)p->n);
     if (p->K < 1 || p->K > kMixMaxK) return fail("RnfFisherMixtureFit.K=%d outside 1..%d", (int)p->K, kMixMaxK);
@@ -2827,10 +2745,7 @@ extern "C" int rnf_fisher_mixture_fit(const RnfFisherMixtureFit *p) {
     if (!(p->max_concentration > 0.0 && p->max_concentration <= 3e4))
         return fail("RnfFisherMixtureFit.max_concentration=%g outside (0, 3e4]", p->max_concentration);
     const size_t need = rnf_fisher_mixture_fit_workspace_bytes(p);
-    if (!p->workspace || p->workspace_bytes < need)
-        return fail("RnfFisherMixtureFit.workspace of %zu bytes is smaller than the %zu needed (rnf_fisher_mixture_fit_workspace_bytes)",
-                    p->workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(p->workspace) % 8) return fail("RnfFisherMixtureFit.workspace must be 8-byte aligned");
+    if (check_workspace(p, "RnfFisherMixtureFit", need, "rnf_fisher_mixture_fit_workspace_bytes", 8)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(p->stream);
     const int K = p->K, T = p->iterations;
     const long long G = p->G, n = p->n, nchunk = rmix::chunks_for(n);

@@ -137,6 +137,40 @@ RNF_FM_HD float finish_mass(double S, bool q_ok, float tau) {
 }
 RNF_FM_HD float finish_moment(double S, bool q_ok) { return q_ok ? (float)S : NAN; }
 
+}  // namespace ac
+namespace sac {                                    // so3_set_angle_cdf.h: a query is a set of K = 1
+// whether any of the K members of a set is live
+RNF_FM_HD bool any_live(const float *Qs, int K) {
+    bool live = false;
+    for (int s = 0; s < K; ++s) live = live || ks::finite9(Qs + 9LL * s);
+    return live;
+}
+
+#if defined(__HIPCC__) && !defined(RNF_AC_HOST_ONLY)       // the host builds of the tests define it: no device code to link
+// The finalise of both entries, grid (ceil(m / THREADS), G): the outputs of (g, i) for sets of K members, Q [m][K][9]; null outputs
+// are not written
+__global__ __launch_bounds__(ks::THREADS) void so3_set_angle_cdf_final_kernel(const double *__restrict__ psum, const float *__restrict__ Q,
+                                                                              long long q_group, int m, int K, int nchunk, int T, int mom,
+                                                                              ac::Taus taus, const float *__restrict__ query_tau,
+                                                                              float *__restrict__ mass, float *__restrict__ mean_angle,
+                                                                              float *__restrict__ mean_sq_angle) {
+    const long long i = (long long)blockIdx.x * ks::THREADS + threadIdx.x;
+    if (i >= m) return;
+    const int g = blockIdx.y, nsw = T + (mom ? 2 : 0);
+    const bool q_ok = any_live(Q + (long long)g * q_group + 9LL * K * i, K);
+    const double *p = psum + (long long)g * nsw * nchunk * m + i;
+    const long long plane = (long long)nchunk * m;
+    for (int t = 0; t < T; ++t) {
+        const long long at = ((long long)g * T + t) * m + i;
+        mass[at] = ac::finish_mass(ac::chunk_sum(p + t * plane, m, nchunk), q_ok, query_tau ? query_tau[at] : taus.t[t]);
+    }
+    if (mean_angle) mean_angle[(long long)g * m + i] = ac::finish_moment(ac::chunk_sum(p + T * plane, m, nchunk), q_ok);
+    if (mean_sq_angle) mean_sq_angle[(long long)g * m + i] = ac::finish_moment(ac::chunk_sum(p + (T + 1) * plane, m, nchunk), q_ok);
+}
+#endif
+}  // namespace sac
+namespace ac {
+
 #if defined(__HIPCC__) && !defined(RNF_AC_HOST_ONLY)       // the host builds of the tests define it: no device code to link
 // grid (ceil(n / THREADS), G): wn[g][j]
 __global__ __launch_bounds__(THREADS) void so3_angle_cdf_weights_kernel(const float *__restrict__ lw, const double *__restrict__ log_z, int n,
@@ -186,24 +220,6 @@ __global__ __launch_bounds__(THREADS) void so3_angle_cdf_kernel(const float *__r
     }
 }
 
-// grid (ceil(m / THREADS), G): the outputs of (g, i); null outputs are not written
-__global__ __launch_bounds__(THREADS) void so3_angle_cdf_final_kernel(const double *__restrict__ psum, const float *__restrict__ Q,
-                                                                      long long q_group, int m, int nchunk, int T, int mom, Taus taus,
-                                                                      const float *__restrict__ query_tau, float *__restrict__ mass,
-                                                                      float *__restrict__ mean_angle, float *__restrict__ mean_sq_angle) {
-    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (i >= m) return;
-    const int g = blockIdx.y, nsw = T + (mom ? 2 : 0);
-    const bool q_ok = ks::finite9(Q + (long long)g * q_group + 9 * i);
-    const double *p = psum + (long long)g * nsw * nchunk * m + i;
-    const long long plane = (long long)nchunk * m;
-    for (int t = 0; t < T; ++t) {
-        const long long at = ((long long)g * T + t) * m + i;
-        mass[at] = finish_mass(chunk_sum(p + t * plane, m, nchunk), q_ok, query_tau ? query_tau[at] : taus.t[t]);
-    }
-    if (mean_angle) mean_angle[(long long)g * m + i] = finish_moment(chunk_sum(p + T * plane, m, nchunk), q_ok);
-    if (mean_sq_angle) mean_sq_angle[(long long)g * m + i] = finish_moment(chunk_sum(p + (T + 1) * plane, m, nchunk), q_ok);
-}
 #endif  // __HIPCC__ && !RNF_AC_HOST_ONLY
 
 // The workspace of one call, carved in this order (the parts of 8-byte elements first); slots = T + 2 (with a moment output) or T
@@ -233,9 +249,21 @@ inline Workspace carve(void *base, long long n, long long m, int G, int slots) {
 
 // ---- the host evaluator: the same row functions in the same order (the host's libm in place of the device's) --------------------------
 
-template <int TT, bool MOM>
-inline void host_query(const float *C, const float *wn, long long n, const float *q, const float *tau, int T, float *mass, long long mass_stride,
-                       float *mean_angle, float *mean_sq_angle) {
+// A row of the outputs is one query here and one set in so3_set_angle_cdf.h: where it lies in Q, its chunk function, whether it counts
+struct QueryRow {
+    const float *q;
+    static long long floats(int) { return 9; }
+    QueryRow(const float *q_, int) : q(q_) {}
+    bool ok() const { return ks::finite9(q); }
+    template <int TT, bool MOM>
+    void chunk(const float *C, const float *wn, long long n, int j0, int j1, const float *tau, double *S) const {
+        cdf_chunk<TT, MOM, 1>(C, wn, n, j0, j1, 0, 1, q, tau, S);
+    }
+};
+
+template <int TT, bool MOM, class Row>
+inline void host_row(const float *C, const float *wn, long long n, const Row &row, const float *tau, int T, float *mass, long long mass_stride,
+                     float *mean_angle, float *mean_sq_angle) {
     constexpr int NS = TT + (MOM ? 2 : 0);
     const int nchunk = (int)ks::chunks_for(n);
     std::vector<double> psum((size_t)(NS > 0 ? NS : 1) * nchunk);
@@ -244,20 +272,21 @@ inline void host_query(const float *C, const float *wn, long long n, const float
     for (int chunk = 0; chunk < nchunk; ++chunk) {
         const int j0 = chunk * CHUNK, j1 = j0 + CHUNK < n ? j0 + CHUNK : (int)n;
         double S[NS > 0 ? NS : 1];
-        cdf_chunk<TT, MOM, 1>(C, wn, n, j0, j1, 0, 1, q, tt, S);
+        row.template chunk<TT, MOM>(C, wn, n, j0, j1, tt, S);
         for (int s = 0; s < NS; ++s) psum[(size_t)s * nchunk + chunk] = S[s];
     }
-    const bool q_ok = ks::finite9(q);
+    const bool q_ok = row.ok();
     if (mass)
         for (int t = 0; t < T; ++t) mass[t * mass_stride] = finish_mass(chunk_sum(psum.data() + (size_t)t * nchunk, 1, nchunk), q_ok, tau[t]);
     if (MOM && mean_angle) *mean_angle = finish_moment(chunk_sum(psum.data() + (size_t)TT * nchunk, 1, nchunk), q_ok);
     if (MOM && mean_sq_angle) *mean_sq_angle = finish_moment(chunk_sum(psum.data() + (size_t)(TT + 1) * nchunk, 1, nchunk), q_ok);
 }
 
-// Q [m][9], or [G][m][9] with group_queries; lw [G][n] or null; thresholds: HOST double[T] angles, or null with query_tau [G][T][m];
-// mass [G][T][m], mean_angle and mean_sq_angle [G][m] may each be null; arguments are not checked
-inline void host_angle_cdf(const float *C, const float *Q, const float *lw, long long n, long long m, int G, bool group_queries, int T,
-                           const double *thresholds, const float *query_tau, float *mass, float *mean_angle, float *mean_sq_angle) {
+// Q [m] rows of Row::floats(K) floats, or [G][m] with group_queries; lw [G][n] or null; thresholds: HOST double[T] angles, or null with
+// query_tau [G][T][m]; mass [G][T][m], mean_angle and mean_sq_angle [G][m] may each be null; arguments are not checked
+template <class Row>
+inline void host_cdf(const float *C, const float *Q, int K, const float *lw, long long n, long long m, int G, bool group_queries, int T,
+                     const double *thresholds, const float *query_tau, float *mass, float *mean_angle, float *mean_sq_angle) {
     const bool mom = mean_angle || mean_sq_angle;
     if (!mass) T = 0;
     std::vector<float> wn((size_t)n);
@@ -265,25 +294,31 @@ inline void host_angle_cdf(const float *C, const float *Q, const float *lw, long
         const double log_z = ks::host_log_z(C, lw, g, n);
         for (long long j = 0; j < n; ++j) wn[(size_t)j] = weight_norm(lw ? lw[(long long)g * n + j] : 0.f, log_z);
         for (long long i = 0; i < m; ++i) {
-            const float *q = Q + ((group_queries ? (long long)g * m : 0) + i) * 9;
+            const Row row(Q + ((group_queries ? (long long)g * m : 0) + i) * Row::floats(K), K);
             float tau[MAX_T];
             for (int t = 0; t < T; ++t) tau[t] = thresholds ? tau_of(thresholds[t]) : query_tau[((long long)g * T + t) * m + i];
             float *ms = mass ? mass + (long long)g * T * m + i : nullptr;
             float *ma = mean_angle ? mean_angle + (long long)g * m + i : nullptr, *m2 = mean_sq_angle ? mean_sq_angle + (long long)g * m + i : nullptr;
 #define RNF_AC_HOST_CASE(TT)                                                                 \
     case TT:                                                                                 \
-        if (mom) host_query<TT, true>(C, wn.data(), n, q, tau, T, ms, m, ma, m2);            \
-        else host_query<TT, false>(C, wn.data(), n, q, tau, T, ms, m, ma, m2);               \
+        if (mom) host_row<TT, true>(C, wn.data(), n, row, tau, T, ms, m, ma, m2);            \
+        else host_row<TT, false>(C, wn.data(), n, row, tau, T, ms, m, ma, m2);               \
         break;
             switch (slots_for(T)) {
                 case 0:
-                    if (mom) host_query<0, true>(C, wn.data(), n, q, tau, T, ms, m, ma, m2);
+                    if (mom) host_row<0, true>(C, wn.data(), n, row, tau, T, ms, m, ma, m2);
                     break;
                 RNF_AC_HOST_CASE(1) RNF_AC_HOST_CASE(2) RNF_AC_HOST_CASE(4) RNF_AC_HOST_CASE(8)
             }
 #undef RNF_AC_HOST_CASE
         }
     }
+}
+
+// Q [m][9], or [G][m][9] with group_queries
+inline void host_angle_cdf(const float *C, const float *Q, const float *lw, long long n, long long m, int G, bool group_queries, int T,
+                           const double *thresholds, const float *query_tau, float *mass, float *mean_angle, float *mean_sq_angle) {
+    host_cdf<QueryRow>(C, Q, 1, lw, n, m, G, group_queries, T, thresholds, query_tau, mass, mean_angle, mean_sq_angle);
 }
 
 }  // namespace ac

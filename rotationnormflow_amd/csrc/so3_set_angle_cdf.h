@@ -51,13 +51,6 @@ constexpr int WAVE_MIN_K = 8;
 constexpr long long WAVE_MAX_WAVES = 4096;
 inline bool wave_per_set(long long m, long long nchunk, long long G, int K) { return K >= WAVE_MIN_K && m * nchunk * G <= WAVE_MAX_WAVES; }
 
-// whether any of the K members of a set is live
-RNF_FM_HD bool any_live(const float *Qs, int K) {
-    bool live = false;
-    for (int s = 0; s < K; ++s) live = live || ks::finite9(Qs + 9LL * s);
-    return live;
-}
-
 // The tile's centres are the same for every member, and the compiler would lift their 576 scalar loads out of the member loop and
 // spill them; an offset it cannot see through keeps the loads inside the loop, where they stream through a few scalar registers.
 RNF_FM_HD int opaque_zero() {
@@ -282,81 +275,29 @@ __global__ __launch_bounds__(64) void so3_set_angle_cdf_wave_kernel(const float 
     }
 }
 
-// grid (ceil(m / THREADS), G): the outputs of (g, i); null outputs are not written
-__global__ __launch_bounds__(THREADS) void so3_set_angle_cdf_final_kernel(const double *__restrict__ psum, const float *__restrict__ Q,
-                                                                          long long q_group, int m, int K, int nchunk, int T, int mom, Taus taus,
-                                                                          const float *__restrict__ query_tau, float *__restrict__ mass,
-                                                                          float *__restrict__ mean_angle, float *__restrict__ mean_sq_angle) {
-    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
-    if (i >= m) return;
-    const int g = blockIdx.y, nsw = T + (mom ? 2 : 0);
-    const bool q_ok = any_live(Q + (long long)g * q_group + 9LL * K * i, K);
-    const double *p = psum + (long long)g * nsw * nchunk * m + i;
-    const long long plane = (long long)nchunk * m;
-    for (int t = 0; t < T; ++t) {
-        const long long at = ((long long)g * T + t) * m + i;
-        mass[at] = ac::finish_mass(ac::chunk_sum(p + t * plane, m, nchunk), q_ok, query_tau ? query_tau[at] : taus.t[t]);
-    }
-    if (mean_angle) mean_angle[(long long)g * m + i] = ac::finish_moment(ac::chunk_sum(p + T * plane, m, nchunk), q_ok);
-    if (mean_sq_angle) mean_sq_angle[(long long)g * m + i] = ac::finish_moment(ac::chunk_sum(p + (T + 1) * plane, m, nchunk), q_ok);
-}
+// The finalise, so3_set_angle_cdf_final_kernel, is in so3_angle_cdf.h: rnf_so3_angle_cdf launches it with K = 1.
 #endif  // __HIPCC__ && !RNF_SAC_HOST_ONLY
 
 // The workspace is ac::carve's for m sets: it does not grow with K.
 
-// ---- the host evaluator: the same row functions in the same order (the host's libm in place of the device's) --------------------------
+// ---- the host evaluator: ac::host_cdf on sets ------------------------------------------------------------------------------------------
 
-template <int TT, bool MOM>
-inline void host_set(const float *C, const float *wn, long long n, const float *Qs, int K, const float *tau, int T, float *mass,
-                     long long mass_stride, float *mean_angle, float *mean_sq_angle) {
-    constexpr int NS = TT + (MOM ? 2 : 0);
-    const int nchunk = (int)ks::chunks_for(n);
-    std::vector<double> psum((size_t)(NS > 0 ? NS : 1) * nchunk);
-    float tt[TT > 0 ? TT : 1];
-    for (int t = 0; t < TT; ++t) tt[t] = t < T ? tau[t] : -1.f;
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        const int j0 = chunk * CHUNK, j1 = j0 + CHUNK < n ? j0 + CHUNK : (int)n;
-        double S[NS > 0 ? NS : 1];
-        set_chunk<TT, MOM, 1>(C, wn, n, j0, j1, 0, 1, Qs, K, tt, S);
-        for (int s = 0; s < NS; ++s) psum[(size_t)s * nchunk + chunk] = S[s];
+struct SetRow {
+    const float *Qs;
+    int K;
+    static long long floats(int K) { return 9LL * K; }
+    SetRow(const float *Qs_, int K_) : Qs(Qs_), K(K_) {}
+    bool ok() const { return any_live(Qs, K); }
+    template <int TT, bool MOM>
+    void chunk(const float *C, const float *wn, long long n, int j0, int j1, const float *tau, double *S) const {
+        set_chunk<TT, MOM, 1>(C, wn, n, j0, j1, 0, 1, Qs, K, tau, S);
     }
-    const bool q_ok = any_live(Qs, K);
-    if (mass)
-        for (int t = 0; t < T; ++t)
-            mass[t * mass_stride] = ac::finish_mass(ac::chunk_sum(psum.data() + (size_t)t * nchunk, 1, nchunk), q_ok, tau[t]);
-    if (MOM && mean_angle) *mean_angle = ac::finish_moment(ac::chunk_sum(psum.data() + (size_t)TT * nchunk, 1, nchunk), q_ok);
-    if (MOM && mean_sq_angle) *mean_sq_angle = ac::finish_moment(ac::chunk_sum(psum.data() + (size_t)(TT + 1) * nchunk, 1, nchunk), q_ok);
-}
+};
 
 // Q [m][K][9], or [G][m][K][9] with group_queries; the other arguments as ac::host_angle_cdf; arguments are not checked
 inline void host_set_angle_cdf(const float *C, const float *Q, const float *lw, long long n, long long m, int K, int G, bool group_queries, int T,
                                const double *thresholds, const float *query_tau, float *mass, float *mean_angle, float *mean_sq_angle) {
-    const bool mom = mean_angle || mean_sq_angle;
-    if (!mass) T = 0;
-    std::vector<float> wn((size_t)n);
-    for (int g = 0; g < G; ++g) {
-        const double log_z = ks::host_log_z(C, lw, g, n);
-        for (long long j = 0; j < n; ++j) wn[(size_t)j] = ac::weight_norm(lw ? lw[(long long)g * n + j] : 0.f, log_z);
-        for (long long i = 0; i < m; ++i) {
-            const float *Qs = Q + ((group_queries ? (long long)g * m : 0) + i) * K * 9;
-            float tau[MAX_T];
-            for (int t = 0; t < T; ++t) tau[t] = thresholds ? ac::tau_of(thresholds[t]) : query_tau[((long long)g * T + t) * m + i];
-            float *ms = mass ? mass + (long long)g * T * m + i : nullptr;
-            float *ma = mean_angle ? mean_angle + (long long)g * m + i : nullptr, *m2 = mean_sq_angle ? mean_sq_angle + (long long)g * m + i : nullptr;
-#define RNF_SAC_HOST_CASE(TT)                                                                \
-    case TT:                                                                                 \
-        if (mom) host_set<TT, true>(C, wn.data(), n, Qs, K, tau, T, ms, m, ma, m2);          \
-        else host_set<TT, false>(C, wn.data(), n, Qs, K, tau, T, ms, m, ma, m2);             \
-        break;
-            switch (ac::slots_for(T)) {
-                case 0:
-                    if (mom) host_set<0, true>(C, wn.data(), n, Qs, K, tau, T, ms, m, ma, m2);
-                    break;
-                RNF_SAC_HOST_CASE(1) RNF_SAC_HOST_CASE(2) RNF_SAC_HOST_CASE(4) RNF_SAC_HOST_CASE(8)
-            }
-#undef RNF_SAC_HOST_CASE
-        }
-    }
+    ac::host_cdf<SetRow>(C, Q, K, lw, n, m, G, group_queries, T, thresholds, query_tau, mass, mean_angle, mean_sq_angle);
 }
 
 }  // namespace sac

@@ -54,6 +54,71 @@ def _inputs(centres, queries, log_weights, group_queries, who: str):
     return Cn, Qr, lw, G, grouped
 
 
+def _angle_cdf(who, one, many, Cn, Qr, lw, G, grouped, K, thresholds, query_tau, group_queries, moments, workspace_cap):
+    """``so3_angle_cdf`` (``K`` None: the rows of ``Qr`` are queries) and ``so3_set_angle_cdf`` (sets of ``K`` members) after their input
+    checks: the thresholds, the outputs, the tiling under ``workspace_cap`` and the copy-back.  ``who`` names the public function and the
+    library's entry, ``one`` and ``many`` a row of ``Qr`` in the messages."""
+    struct, members = (_lib.So3AngleCdf, {}) if K is None else (_lib.So3SetAngleCdf, {"K": K})
+    n, dev, m = Cn.shape[0], Cn.device, Qr.shape[-3 if K is None else -4]
+    if thresholds is not None and query_tau is not None:
+        raise ValueError(f"{who}: both thresholds and query_tau are given; pass one of the two")
+    th, tau, T = None, None, 0
+    if thresholds is not None:
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().reshape(-1).tolist()
+        th = [float(thresholds)] if not isinstance(thresholds, (list, tuple)) else [float(t) for t in thresholds]
+        T = len(th)
+        for t in th:
+            if not (math.isfinite(t) and 0.0 <= t <= math.pi):
+                raise ValueError(f"{who}: threshold {t} outside 0..pi radians")
+    elif query_tau is not None:
+        want = "[G,T,m]" if grouped else "[T,m]"
+        if not isinstance(query_tau, torch.Tensor) or query_tau.dim() != (3 if grouped else 2) or query_tau.shape[-1] != m or (
+                grouped and query_tau.shape[0] != G):
+            raise ValueError(f"{who}: query_tau {tuple(getattr(query_tau, 'shape', ()))} for {G} groups of {m} {many}, expected {want}")
+        if not query_tau.is_cuda:
+            raise ValueError(f"{who}: query_tau is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+        tau = query_tau.detach().to(device=dev, dtype=torch.float32).reshape(G, -1, m).contiguous()
+        T = tau.shape[1]
+    if T > MAX_THRESHOLDS or (T == 0 and (th is not None or tau is not None)):
+        raise ValueError(f"{who}: {T} thresholds (1 to {MAX_THRESHOLDS})")
+    if T == 0 and not moments:
+        raise ValueError(f"{who}: no thresholds, no query_tau and no moments: nothing to compute")
+    cap = WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
+    out = {"mass": torch.empty(G, T, m, dtype=torch.float32, device=dev)}
+    if moments:
+        out["mean_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
+        out["mean_sq_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
+    per_row = SLOT_BYTES * (T + (2 if moments else 0)) * ((n + CHUNK - 1) // CHUNK)        # bytes per query (set) and group
+    if per_row > cap:
+        raise ValueError(f"{who}: one {one}'s partial sums take {per_row} bytes, above workspace_cap={cap}; pass a larger workspace_cap")
+    host = (C.c_double * T)(*th) if th is not None else None
+    if m > 0:
+        g_tile = max(1, min(G, cap // (per_row * min(m, 256))))
+        m_tile = max(1, min(m, cap // (per_row * g_tile)))
+        m_tile = m_tile if m_tile < 4 or m_tile == m else m_tile // 4 * 4          # rows of 36 (K) bytes: every fourth is 16-byte aligned
+        for g0 in range(0, G, g_tile):
+            g1 = min(G, g0 + g_tile)
+            for i0 in range(0, m, m_tile):
+                i1 = min(m, i0 + m_tile)
+                tile = _aligned(Qr[g0:g1, i0:i1].contiguous() if group_queries else Qr[i0:i1])
+                part = {name: v[g0:g1, ..., i0:i1] for name, v in out.items() if name != "mass" or T > 0}
+                dst = {name: v if v.is_contiguous() else torch.empty(v.shape, dtype=torch.float32, device=dev) for name, v in part.items()}
+                tau_tile = tau[g0:g1, :, i0:i1].contiguous() if tau is not None else None
+                args = struct(centres=Cn.data_ptr(), queries=tile.data_ptr(), log_weights=lw[g0:g1].data_ptr() if lw is not None else None,
+                              n=n, m=i1 - i0, G=g1 - g0, group_queries=int(bool(group_queries)), T=T,
+                              thresholds=C.cast(host, C.c_void_p) if host is not None else None,
+                              query_tau=tau_tile.data_ptr() if tau_tile is not None else None, **members,
+                              **{name: v.data_ptr() for name, v in dst.items()})
+                _lib.call(who, args, dev)
+                for name, v in part.items():
+                    if dst[name] is not v:
+                        v.copy_(dst[name])
+    if moments:
+        out["rms_angle"] = torch.sqrt(out["mean_sq_angle"])
+    return out if grouped else {name: v[0] for name, v in out.items()}
+
+
 def so3_angle_cdf(centres, queries, thresholds=None, query_tau=None, log_weights=None, group_queries: bool = False, moments: bool = True,
                   workspace_cap: int = None) -> dict:
     """The distribution function of the geodesic angle on the device (``rnf_so3_angle_cdf``): with w = softmax(``log_weights``) (uniform
@@ -72,64 +137,7 @@ def so3_angle_cdf(centres, queries, thresholds=None, query_tau=None, log_weights
     below one query's partial sums raises ValueError.  Stream-ordered, no host synchronisation, no gradient."""
     who = "so3_angle_cdf"
     Cn, Qr, lw, G, grouped = _inputs(centres, queries, log_weights, bool(group_queries), who)
-    n, dev, m = Cn.shape[0], Cn.device, Qr.shape[-3]
-    if thresholds is not None and query_tau is not None:
-        raise ValueError(f"{who}: both thresholds and query_tau are given; pass one of the two")
-    th, tau, T = None, None, 0
-    if thresholds is not None:
-        if isinstance(thresholds, torch.Tensor):
-            thresholds = thresholds.detach().cpu().reshape(-1).tolist()
-        th = [float(thresholds)] if not isinstance(thresholds, (list, tuple)) else [float(t) for t in thresholds]
-        T = len(th)
-        for t in th:
-            if not (math.isfinite(t) and 0.0 <= t <= math.pi):
-                raise ValueError(f"{who}: threshold {t} outside 0..pi radians")
-    elif query_tau is not None:
-        want = "[G,T,m]" if grouped else "[T,m]"
-        if not isinstance(query_tau, torch.Tensor) or query_tau.dim() != (3 if grouped else 2) or query_tau.shape[-1] != m or (
-                grouped and query_tau.shape[0] != G):
-            raise ValueError(f"{who}: query_tau {tuple(getattr(query_tau, 'shape', ()))} for {G} groups of {m} queries, expected {want}")
-        if not query_tau.is_cuda:
-            raise ValueError(f"{who}: query_tau is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
-        tau = query_tau.detach().to(device=dev, dtype=torch.float32).reshape(G, -1, m).contiguous()
-        T = tau.shape[1]
-    if T > MAX_THRESHOLDS or (T == 0 and (th is not None or tau is not None)):
-        raise ValueError(f"{who}: {T} thresholds (1 to {MAX_THRESHOLDS})")
-    if T == 0 and not moments:
-        raise ValueError(f"{who}: no thresholds, no query_tau and no moments: nothing to compute")
-    cap = WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
-    out = {"mass": torch.empty(G, T, m, dtype=torch.float32, device=dev)}
-    if moments:
-        out["mean_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
-        out["mean_sq_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
-    per_query = SLOT_BYTES * (T + (2 if moments else 0)) * ((n + CHUNK - 1) // CHUNK)      # bytes per query and group
-    if per_query > cap:
-        raise ValueError(f"{who}: one query's partial sums take {per_query} bytes, above workspace_cap={cap}; pass a larger workspace_cap")
-    host = (C.c_double * T)(*th) if th is not None else None
-    if m > 0:
-        g_tile = max(1, min(G, cap // (per_query * min(m, 256))))
-        m_tile = max(1, min(m, cap // (per_query * g_tile)))
-        m_tile = m_tile if m_tile < 4 or m_tile == m else m_tile // 4 * 4          # rows of 36 bytes: every fourth is 16-byte aligned
-        for g0 in range(0, G, g_tile):
-            g1 = min(G, g0 + g_tile)
-            for i0 in range(0, m, m_tile):
-                i1 = min(m, i0 + m_tile)
-                tile = _aligned(Qr[g0:g1, i0:i1].contiguous() if group_queries else Qr[i0:i1])
-                part = {name: v[g0:g1, ..., i0:i1] for name, v in out.items() if name != "mass" or T > 0}
-                dst = {name: v if v.is_contiguous() else torch.empty(v.shape, dtype=torch.float32, device=dev) for name, v in part.items()}
-                tau_tile = tau[g0:g1, :, i0:i1].contiguous() if tau is not None else None
-                args = _lib.So3AngleCdf(centres=Cn.data_ptr(), queries=tile.data_ptr(),
-                                        log_weights=lw[g0:g1].data_ptr() if lw is not None else None, n=n, m=i1 - i0, G=g1 - g0,
-                                        group_queries=int(bool(group_queries)), T=T, thresholds=C.cast(host, C.c_void_p) if host is not None else None,
-                                        query_tau=tau_tile.data_ptr() if tau_tile is not None else None,
-                                        **{name: v.data_ptr() for name, v in dst.items()})
-                _lib.call("so3_angle_cdf", args, dev)
-                for name, v in part.items():
-                    if dst[name] is not v:
-                        v.copy_(dst[name])
-    if moments:
-        out["rms_angle"] = torch.sqrt(out["mean_sq_angle"])
-    return out if grouped else {name: v[0] for name, v in out.items()}
+    return _angle_cdf(who, "query", "queries", Cn, Qr, lw, G, grouped, None, thresholds, query_tau, group_queries, moments, workspace_cap)
 
 
 def _tau(theta):
@@ -169,6 +177,35 @@ def _quantile_search(cdf, G, m, lv, passes, dev):
     return {key: v.reshape(G, L, m) for key, v in res.items()}
 
 
+def _angle_quantile(who, cdf_fn, rows, Cn, Qr, lw, G, grouped, levels, group_queries, tol, workspace_cap):
+    """``so3_angle_quantile`` and ``so3_set_angle_quantile`` after their input checks: the levels, ``tol`` and the bracket search on
+    ``cdf_fn`` (``so3_angle_cdf`` or ``so3_set_angle_cdf``); ``rows``: the axis of ``Qr`` that counts the queries (sets)"""
+    if isinstance(levels, torch.Tensor):
+        levels = levels.detach().cpu().reshape(-1).tolist()
+    lv = [float(levels)] if not isinstance(levels, (list, tuple)) else [float(a) for a in levels]
+    if not lv:
+        raise ValueError(f"{who}: levels is empty")
+    for a in lv:
+        if not 0.0 < a < 1.0:
+            raise ValueError(f"{who}: level {a} outside (0, 1)")
+    if not (math.isfinite(float(tol)) and 0.0 < float(tol) <= math.pi):
+        raise ValueError(f"{who}: tol={tol} outside (0, pi] radians")
+    dev, m = Cn.device, Qr.shape[rows]
+    passes = max(1, math.ceil(math.log(math.pi / float(tol)) / math.log(9.0) - 1e-12))
+    kw = dict(log_weights=lw, group_queries=group_queries, moments=False, workspace_cap=workspace_cap)
+    lead = lw is not None or group_queries                                # lw is [G,n] here: the calls below carry a G whenever it is given
+    Qrep = torch.cat([Qr] * len(lv), dim=rows) if len(lv) > 1 else Qr     # level-major: one call per pass serves every level
+
+    def cdf(thresholds=None, query_tau=None):
+        if query_tau is not None and not lead:
+            query_tau = query_tau[0]
+        out = cdf_fn(Cn, Qrep, thresholds, query_tau, **kw)["mass"].to(torch.float64)
+        return out if lead else out[None]                                 # [G,T,L*m]
+
+    out = _quantile_search(cdf, G, m, lv, passes, dev)                    # [G,L,m]
+    return out if grouped else {key: v[0] for key, v in out.items()}
+
+
 def so3_angle_quantile(centres, queries, levels, log_weights=None, group_queries: bool = False, tol: float = 1e-3,
                        workspace_cap: int = None) -> dict:
     """The error radii of the queries: for each level alpha in (0, 1) the angle at which the ball about query i reaches mass alpha
@@ -184,31 +221,7 @@ def so3_angle_quantile(centres, queries, levels, log_weights=None, group_queries
     at a hi still pi); a leading G as ``so3_angle_cdf``."""
     who = "so3_angle_quantile"
     Cn, Qr, lw, G, grouped = _inputs(centres, queries, log_weights, bool(group_queries), who)
-    if isinstance(levels, torch.Tensor):
-        levels = levels.detach().cpu().reshape(-1).tolist()
-    lv = [float(levels)] if not isinstance(levels, (list, tuple)) else [float(a) for a in levels]
-    if not lv:
-        raise ValueError(f"{who}: levels is empty")
-    for a in lv:
-        if not 0.0 < a < 1.0:
-            raise ValueError(f"{who}: level {a} outside (0, 1)")
-    if not (math.isfinite(float(tol)) and 0.0 < float(tol) <= math.pi):
-        raise ValueError(f"{who}: tol={tol} outside (0, pi] radians")
-    dev, m = Cn.device, Qr.shape[-3]
-    passes = max(1, math.ceil(math.log(math.pi / float(tol)) / math.log(9.0) - 1e-12))
-    kw = dict(log_weights=lw, group_queries=bool(group_queries), moments=False, workspace_cap=workspace_cap)
-    lead = lw is not None or bool(group_queries)                          # lw is [G,n] here: the calls below carry a G whenever it is given
-
-    Qrep = torch.cat([Qr] * len(lv), dim=-3) if len(lv) > 1 else Qr      # level-major: one call per pass serves every level
-
-    def cdf(thresholds=None, query_tau=None):
-        if query_tau is not None and not lead:
-            query_tau = query_tau[0]
-        out = so3_angle_cdf(Cn, Qrep, thresholds, query_tau, **kw)["mass"].to(torch.float64)
-        return out if lead else out[None]                                 # [G,T,L*m]
-
-    out = _quantile_search(cdf, G, m, lv, passes, dev)                    # [G,L,m]
-    return out if grouped else {key: v[0] for key, v in out.items()}
+    return _angle_quantile(who, so3_angle_cdf, -3, Cn, Qr, lw, G, grouped, levels, bool(group_queries), tol, workspace_cap)
 
 
 MAX_MEMBERS = 4096                                  # K of rnf_so3_set_angle_cdf (include/rnf_hip.h)
@@ -243,65 +256,7 @@ def so3_set_angle_cdf(centres, query_sets, thresholds=None, query_tau=None, log_
     no host synchronisation, no gradient."""
     who = "so3_set_angle_cdf"
     Cn, Qr, lw, G, grouped = _set_inputs(centres, query_sets, log_weights, bool(group_queries), who)
-    n, dev, m, K = Cn.shape[0], Cn.device, Qr.shape[-4], Qr.shape[-3]
-    if thresholds is not None and query_tau is not None:
-        raise ValueError(f"{who}: both thresholds and query_tau are given; pass one of the two")
-    th, tau, T = None, None, 0
-    if thresholds is not None:
-        if isinstance(thresholds, torch.Tensor):
-            thresholds = thresholds.detach().cpu().reshape(-1).tolist()
-        th = [float(thresholds)] if not isinstance(thresholds, (list, tuple)) else [float(t) for t in thresholds]
-        T = len(th)
-        for t in th:
-            if not (math.isfinite(t) and 0.0 <= t <= math.pi):
-                raise ValueError(f"{who}: threshold {t} outside 0..pi radians")
-    elif query_tau is not None:
-        want = "[G,T,m]" if grouped else "[T,m]"
-        if not isinstance(query_tau, torch.Tensor) or query_tau.dim() != (3 if grouped else 2) or query_tau.shape[-1] != m or (
-                grouped and query_tau.shape[0] != G):
-            raise ValueError(f"{who}: query_tau {tuple(getattr(query_tau, 'shape', ()))} for {G} groups of {m} sets, expected {want}")
-        if not query_tau.is_cuda:
-            raise ValueError(f"{who}: query_tau is on the CPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
-        tau = query_tau.detach().to(device=dev, dtype=torch.float32).reshape(G, -1, m).contiguous()
-        T = tau.shape[1]
-    if T > MAX_THRESHOLDS or (T == 0 and (th is not None or tau is not None)):
-        raise ValueError(f"{who}: {T} thresholds (1 to {MAX_THRESHOLDS})")
-    if T == 0 and not moments:
-        raise ValueError(f"{who}: no thresholds, no query_tau and no moments: nothing to compute")
-    cap = WORKSPACE_CAP if workspace_cap is None else int(workspace_cap)
-    out = {"mass": torch.empty(G, T, m, dtype=torch.float32, device=dev)}
-    if moments:
-        out["mean_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
-        out["mean_sq_angle"] = torch.empty(G, m, dtype=torch.float32, device=dev)
-    per_set = SLOT_BYTES * (T + (2 if moments else 0)) * ((n + CHUNK - 1) // CHUNK)        # bytes per set and group
-    if per_set > cap:
-        raise ValueError(f"{who}: one set's partial sums take {per_set} bytes, above workspace_cap={cap}; pass a larger workspace_cap")
-    host = (C.c_double * T)(*th) if th is not None else None
-    if m > 0:
-        g_tile = max(1, min(G, cap // (per_set * min(m, 256))))
-        m_tile = max(1, min(m, cap // (per_set * g_tile)))
-        m_tile = m_tile if m_tile < 4 or m_tile == m else m_tile // 4 * 4          # sets of 36 K bytes: every fourth is 16-byte aligned
-        for g0 in range(0, G, g_tile):
-            g1 = min(G, g0 + g_tile)
-            for i0 in range(0, m, m_tile):
-                i1 = min(m, i0 + m_tile)
-                tile = _aligned(Qr[g0:g1, i0:i1].contiguous() if group_queries else Qr[i0:i1])
-                part = {name: v[g0:g1, ..., i0:i1] for name, v in out.items() if name != "mass" or T > 0}
-                dst = {name: v if v.is_contiguous() else torch.empty(v.shape, dtype=torch.float32, device=dev) for name, v in part.items()}
-                tau_tile = tau[g0:g1, :, i0:i1].contiguous() if tau is not None else None
-                args = _lib.So3SetAngleCdf(centres=Cn.data_ptr(), queries=tile.data_ptr(),
-                                           log_weights=lw[g0:g1].data_ptr() if lw is not None else None, n=n, m=i1 - i0, K=K, G=g1 - g0,
-                                           group_queries=int(bool(group_queries)), T=T,
-                                           thresholds=C.cast(host, C.c_void_p) if host is not None else None,
-                                           query_tau=tau_tile.data_ptr() if tau_tile is not None else None,
-                                           **{name: v.data_ptr() for name, v in dst.items()})
-                _lib.call("so3_set_angle_cdf", args, dev)
-                for name, v in part.items():
-                    if dst[name] is not v:
-                        v.copy_(dst[name])
-    if moments:
-        out["rms_angle"] = torch.sqrt(out["mean_sq_angle"])
-    return out if grouped else {name: v[0] for name, v in out.items()}
+    return _angle_cdf(who, "set", "sets", Cn, Qr, lw, G, grouped, Qr.shape[-3], thresholds, query_tau, group_queries, moments, workspace_cap)
 
 
 def so3_set_angle_quantile(centres, query_sets, levels, log_weights=None, group_queries: bool = False, tol: float = 1e-3,
@@ -311,27 +266,4 @@ def so3_set_angle_quantile(centres, query_sets, levels, log_weights=None, group_
     other arguments and the result ([L,m], a leading G) as ``so3_angle_quantile``.  Bit-identical however the call is tiled."""
     who = "so3_set_angle_quantile"
     Cn, Qr, lw, G, grouped = _set_inputs(centres, query_sets, log_weights, bool(group_queries), who)
-    if isinstance(levels, torch.Tensor):
-        levels = levels.detach().cpu().reshape(-1).tolist()
-    lv = [float(levels)] if not isinstance(levels, (list, tuple)) else [float(a) for a in levels]
-    if not lv:
-        raise ValueError(f"{who}: levels is empty")
-    for a in lv:
-        if not 0.0 < a < 1.0:
-            raise ValueError(f"{who}: level {a} outside (0, 1)")
-    if not (math.isfinite(float(tol)) and 0.0 < float(tol) <= math.pi):
-        raise ValueError(f"{who}: tol={tol} outside (0, pi] radians")
-    dev, m = Cn.device, Qr.shape[-4]
-    passes = max(1, math.ceil(math.log(math.pi / float(tol)) / math.log(9.0) - 1e-12))
-    kw = dict(log_weights=lw, group_queries=bool(group_queries), moments=False, workspace_cap=workspace_cap)
-    lead = lw is not None or bool(group_queries)
-    Qrep = torch.cat([Qr] * len(lv), dim=-4) if len(lv) > 1 else Qr      # level-major: one call per pass serves every level
-
-    def cdf(thresholds=None, query_tau=None):
-        if query_tau is not None and not lead:
-            query_tau = query_tau[0]
-        out = so3_set_angle_cdf(Cn, Qrep, thresholds, query_tau, **kw)["mass"].to(torch.float64)
-        return out if lead else out[None]                                 # [G,T,L*m]
-
-    out = _quantile_search(cdf, G, m, lv, passes, dev)                    # [G,L,m]
-    return out if grouped else {key: v[0] for key, v in out.items()}
+    return _angle_quantile(who, so3_set_angle_cdf, -4, Cn, Qr, lw, G, grouped, levels, bool(group_queries), tol, workspace_cap)

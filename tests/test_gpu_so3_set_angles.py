@@ -83,6 +83,30 @@ def test_bit_identities():
                 assert same(a, gpu_single_angle_cdf(Cn, sets[:, 0], lw, False, thresholds=th, moments=mom)), (th, lw is None, mom)
 
 
+@pytest.mark.parametrize("per_query", [False, True], ids=["shared-thresholds", "query-tau"])
+def test_sets_of_one_member_are_the_queries_bit_for_bit_through_the_shared_tiling(per_query):
+    """so3_set_angle_cdf on [m,1,3,3] against so3_angle_cdf on [m,3,3], which share the thresholds, the tiling and the copy-back of
+    utils/angles.py: n = 4097 is two chunks, the second a single ragged tile; [G,n] log-weights, T = 3, the moments.  Under the default cap
+    (one call) and under a cap of two queries' partial sums (8 bytes x 5 slots x 2 chunks each), which tiles the queries in twos and the
+    groups in ones and copies every tile back."""
+    n, m, G, T = 4097, 5, 3, 3
+    Cn, sets, lw = hs.make_set_case(n, m, 1, G)
+    Cn, sets, lw = dev(Cn), dev(sets), dev(lw)
+    th = [float(t) for t in np.deg2rad([15.0, 30.0, 120.0])]
+    tau = dev(np.broadcast_to(ha.tau_of(np.asarray(th))[None, :, None], (G, T, m)).copy()) * torch.linspace(0.5, 1.5, m, device=DEV)
+    kw = dict(query_tau=tau) if per_query else dict(thresholds=th)
+    per_query_bytes = angles.SLOT_BYTES * (T + 2) * 2
+    outs = []
+    for cap in (None, 2 * per_query_bytes):
+        a = angles.so3_set_angle_cdf(Cn, sets, log_weights=lw, workspace_cap=cap, **kw)
+        b = angles.so3_angle_cdf(Cn, sets[:, 0], log_weights=lw, workspace_cap=cap, **kw)
+        assert a.keys() == b.keys() == {"mass", "mean_angle", "mean_sq_angle", "rms_angle"} and tuple(a["mass"].shape) == (G, T, m)
+        assert all(torch.equal(a[k], b[k]) and torch.isfinite(a[k]).all() for k in a), (per_query, cap)
+        outs.append(a)
+    assert all(torch.equal(outs[0][k], outs[1][k]) for k in outs[0])
+    assert (outs[0]["mass"][:, 1:] >= outs[0]["mass"][:, :-1]).all()     # the thresholds of a query increase with the slot
+
+
 def test_edge_cases():
     hs.check_set_edge_cases(gpu_set_angle_cdf)
     Cn = dev(ha.draw("uniform", 5, 1))
