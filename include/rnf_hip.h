@@ -843,6 +843,36 @@ typedef struct RnfSo3GridLocalSum {
 } RnfSo3GridLocalSum;
 int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *sum);
 
+/* The max-plus pass over the same neighbourhoods (csrc/so3_grid_local.h): the step of a Viterbi recursion on the grid, which the sum
+ * cannot express (a log-sum has no arg-max).  With the rows, queries, kappa, d2_cut and log-weights of rnf_so3_grid_local_sum,
+ *   out[g][i] = max_{j : d^2(G_j, Q_i) <= d2_cut} (log_weights[g][j] - (kappa/2) d^2(G_j, Q_i)) - l(kappa),
+ *   arg[g][i] = the smallest row index j attaining that maximum,     count[i] = the number of such j.
+ * The enumeration and the membership are the sum's own, bit for bit.  The maximum and the tie are decided on the sum's fp32 term
+ * t = fma(-h, d^2, lw log2 e); the tie goes to the smallest row, compared explicitly (members arrive by ring, pixel and tilt, not by
+ * row).  One sweep, no exp2.
+ * Edge cases: an empty neighbourhood, or one whose members all have log-weight -inf, gives -inf and arg -1; a NaN log-weight inside a
+ * query's neighbourhood gives NaN and arg -1; a query with a non-finite entry gives NaN, arg -1 and count 0.  m = 0 is a no-op.
+ * Deterministic: one thread per query; a result is bit-identical from run to run and whatever m, G, the query's position and the
+ * group's position are: queries and groups may be tiled over calls.
+ * One launch, no workspace.  Stream-ordered, no host synchronisation, capturable in a HIP graph. */
+typedef struct RnfSo3GridLocalMax {
+    size_t struct_bytes;        /* sizeof(RnfSo3GridLocalMax); any other value is refused (header and library differ) */
+    int32_t level;              /* 0..6: Q = 72 * 8^level grid rows */
+    const float *offset;        /* dev float[9], the grid's offset O (row-major, a rotation), or NULL (the identity) */
+    const float *grid;          /* dev float[Q][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9] row-major, 16-byte aligned, or NULL: the grid rows (then m must be Q) */
+    const float *log_weights;   /* dev float[G][Q], or NULL (zeros) */
+    int64_t m;                  /* queries, 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    double kappa;               /* finite, 0..1e6 */
+    double d2_cut;              /* finite, 0..8; 8 (180 degrees) covers every row */
+    float *out;                 /* dev float[G][m] */
+    int32_t *arg;               /* dev int32[G][m], required */
+    int32_t *count;             /* dev int32[m], or NULL */
+    void *stream;
+} RnfSo3GridLocalMax;
+int rnf_so3_grid_local_max(const RnfSo3GridLocalMax *max);
+
 /* Harmonic analysis on SO(3) (csrc/so3_harmonics.h).  Y_l(x) is the vector of the 2l+1 orthonormal real spherical harmonics of degree
  * l, m = -l..l: sqrt2 (-1)^m Re Y_l^m for m > 0, sqrt2 (-1)^m Im Y_l^|m| for m < 0, Y_l^0 for m = 0 (for l = 1: y, z, x).  The Wigner
  * matrix D^l(R) is the real orthogonal (2l+1) x (2l+1) matrix with Y_l(R x) = D^l(R) Y_l(x): D^l(R1 R2) = D^l(R1) D^l(R2), D^0 = 1,

@@ -128,6 +128,13 @@ class So3GridLocalSum(_Pass):
                 ("out", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class So3GridLocalMax(_Pass):
+    """RnfSo3GridLocalMax (include/rnf_hip.h): the max-plus pass with its arg-max over the same neighbourhoods."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("offset", C.c_void_p), ("grid", C.c_void_p), ("queries", C.c_void_p),
+                ("log_weights", C.c_void_p), ("m", C.c_int64), ("G", C.c_int32), ("kappa", C.c_double), ("d2_cut", C.c_double),
+                ("out", C.c_void_p), ("arg", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class So3Wigner(_Pass):
     """RnfSo3Wigner (include/rnf_hip.h): the real Wigner matrices of rotations, degrees 0..lmax."""
     _fields_ = [("struct_bytes", C.c_size_t), ("rotations", C.c_void_p), ("n", C.c_int64), ("lmax", C.c_int32), ("out", C.c_void_p),
@@ -255,6 +262,7 @@ _SIGNATURES = {
     "rnf_so3_set_angle_cdf": (C.c_int, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_set_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_grid_local_sum": (C.c_int, [C.POINTER(So3GridLocalSum)]),
+    "rnf_so3_grid_local_max": (C.c_int, [C.POINTER(So3GridLocalMax)]),
     "rnf_so3_wigner": (C.c_int, [C.POINTER(So3Wigner)]),
     "rnf_so3_wigner_workspace_bytes": (C.c_size_t, [C.POINTER(So3Wigner)]),
     "rnf_so3_fourier": (C.c_int, [C.POINTER(So3Fourier)]),

@@ -2138,21 +2138,27 @@ static void so3_grid_local_launch(const RnfSo3GridLocalSum *p, const sgl::Geomet
                        sgl::rows_of(p->level), (int)p->m, (int)p->G, l_kappa, p->out, p->count);
 }
 
-extern "C" int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *p) {
-    if (check_struct(p, "RnfSo3GridLocalSum")) return 1;
-    if (p->level < 0 || p->level > sgl::MAX_LEVEL) return fail("RnfSo3GridLocalSum.level=%d outside 0..%d", p->level, sgl::MAX_LEVEL);
-    if (p->G < 1 || p->G > sgl::MAX_G) return fail("RnfSo3GridLocalSum.G=%d outside 1..65535", p->G);
-    if (p->m < 0 || p->m > sgl::MAX_M) return fail("RnfSo3GridLocalSum.m=%lld outside 0..2^31-1", (long long)p->m);
-    if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("RnfSo3GridLocalSum.kappa=%g outside 0..1e6", p->kappa);
-    if (!(p->d2_cut >= 0.0 && p->d2_cut <= sgl::MAX_D2)) return fail("RnfSo3GridLocalSum.d2_cut=%g outside 0..8", p->d2_cut);
-    if (check_aligned16(p->grid, p->queries, "RnfSo3GridLocalSum", ": grid and queries")) return 1;
+// the refusals rnf_so3_grid_local_sum and rnf_so3_grid_local_max share; 1: refused, -1: nothing to do (m = 0), 0: go on
+template <class P>
+static int so3_grid_local_check(const P *p, const char *who, const void *arg, const char *arg_name) {
+    if (p->level < 0 || p->level > sgl::MAX_LEVEL) return fail("%s.level=%d outside 0..%d", who, p->level, sgl::MAX_LEVEL);
+    if (p->G < 1 || p->G > sgl::MAX_G) return fail("%s.G=%d outside 1..65535", who, p->G);
+    if (p->m < 0 || p->m > sgl::MAX_M) return fail("%s.m=%lld outside 0..2^31-1", who, (long long)p->m);
+    if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("%s.kappa=%g outside 0..1e6", who, p->kappa);
+    if (!(p->d2_cut >= 0.0 && p->d2_cut <= sgl::MAX_D2)) return fail("%s.d2_cut=%g outside 0..8", who, p->d2_cut);
+    if (check_aligned16(p->grid, p->queries, who, ": grid and queries")) return 1;
     if (reinterpret_cast<uintptr_t>(p->offset) % 4 || reinterpret_cast<uintptr_t>(p->log_weights) % 4 || reinterpret_cast<uintptr_t>(p->out) % 4 ||
-        reinterpret_cast<uintptr_t>(p->count) % 4)
-        return fail("RnfSo3GridLocalSum: offset, log_weights, out and count must be 4-byte aligned");
+        reinterpret_cast<uintptr_t>(arg) % 4 || reinterpret_cast<uintptr_t>(p->count) % 4)
+        return fail("%s: offset, log_weights, out%s and count must be 4-byte aligned", who, arg_name);
     const long long Q = sgl::rows_of(p->level);
     if (!p->queries && p->m != Q)
-        return fail("RnfSo3GridLocalSum: null queries stand for the grid rows, but m=%lld and level %d has %lld", (long long)p->m, p->level, Q);
-    if (p->m == 0) return 0;
+        return fail("%s: null queries stand for the grid rows, but m=%lld and level %d has %lld", who, (long long)p->m, p->level, Q);
+    return p->m == 0 ? -1 : 0;
+}
+
+extern "C" int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *p) {
+    if (check_struct(p, "RnfSo3GridLocalSum")) return 1;
+    if (const int r = so3_grid_local_check(p, "RnfSo3GridLocalSum", nullptr, "")) return r > 0;
     if (!p->grid || !p->out) return fail("RnfSo3GridLocalSum: null grid or out");
     const sgl::Geometry ge = sgl::geometry_of(p->level, p->kappa, p->d2_cut);
     const double l_kappa = ks::log_normaliser(p->kappa);
@@ -2164,6 +2170,32 @@ extern "C" int rnf_so3_grid_local_sum(const RnfSo3GridLocalSum *p) {
         so3_grid_local_launch<1, true>(p, ge, queries, l_kappa, s);
     else
         so3_grid_local_launch<sgl::GROUPS_PER_THREAD, true>(p, ge, queries, l_kappa, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The max-plus pass over the same neighbourhoods (csrc/so3_grid_local.h, SWEEP_ARGMAX): one launch of the sum's shape, no workspace.
+template <int GB, bool W>
+static void so3_grid_local_max_launch(const RnfSo3GridLocalMax *p, const sgl::Geometry &ge, const float *Q, double l_kappa, hipStream_t s) {
+    const dim3 grid((unsigned)((p->m + sgl::THREADS - 1) / sgl::THREADS), (unsigned)((p->G + GB - 1) / GB));
+    hipLaunchKernelGGL((sgl::so3_grid_local_max_kernel<GB, W>), grid, dim3(sgl::THREADS), 0, s, ge, p->offset, p->grid, Q, p->log_weights,
+                       sgl::rows_of(p->level), (int)p->m, (int)p->G, l_kappa, p->out, p->arg, p->count);
+}
+
+extern "C" int rnf_so3_grid_local_max(const RnfSo3GridLocalMax *p) {
+    if (check_struct(p, "RnfSo3GridLocalMax")) return 1;
+    if (const int r = so3_grid_local_check(p, "RnfSo3GridLocalMax", p->arg, ", arg")) return r > 0;
+    if (!p->grid || !p->out || !p->arg) return fail("RnfSo3GridLocalMax: null grid, out or arg");
+    const sgl::Geometry ge = sgl::geometry_of(p->level, p->kappa, p->d2_cut);
+    const double l_kappa = ks::log_normaliser(p->kappa);
+    const float *queries = p->queries ? p->queries : p->grid;
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    if (!p->log_weights)
+        so3_grid_local_max_launch<1, false>(p, ge, queries, l_kappa, s);
+    else if (p->G == 1)
+        so3_grid_local_max_launch<1, true>(p, ge, queries, l_kappa, s);
+    else
+        so3_grid_local_max_launch<sgl::GROUPS_PER_THREAD, true>(p, ge, queries, l_kappa, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

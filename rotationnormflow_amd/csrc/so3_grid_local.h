@@ -37,6 +37,12 @@
 // counts).  A NaN log-weight inside a query's neighbourhood makes that output NaN.  A query with a non-finite entry gives NaN and
 // count 0; a finite query with |Q|_F^2 > 25 is further than the largest cut from every rotation: -inf and count 0.  A grid row with a
 // non-finite entry is at distance FLT_MAX: no member.
+//
+// The max-plus pass (rnf_so3_grid_local_max) is a third mode of the same sweep: over the same members, on the same fp32 term t,
+//     out[g][i] = max_j (lw[g][j] - (kappa/2) d^2(G_j, Q_i)) - l(kappa) = (float)((double)M ln 2 - l(kappa)),     arg[g][i] = the smallest row with t == M.
+// One sweep, no exp2.  The tie goes to the smallest ROW, compared explicitly: members arrive by (ring, pixel, tilt).  No live member
+// (none, or all at -inf): -inf and -1; a NaN log-weight inside the neighbourhood (fmaxf would drop it: a flag carries it): NaN and -1;
+// a non-finite query: NaN, -1, count 0.  The Viterbi recursion of grid_pose.grid_viterbi runs on it.
 #pragma once
 #if defined(RNF_SGL_HOST_ONLY) && !defined(RNF_KS_HOST_ONLY)
 #define RNF_KS_HOST_ONLY
@@ -198,10 +204,12 @@ RNF_FM_HD void cyclic_window(float x0, float w, int n, int &lo, int &count) {
 }
 
 // One sweep of a query's enumeration for the GB groups g0 .. (clamped at G - 1).
-//   SUM = false: M[gb] = max t, count = the members, visited = the rows looked at;   SUM = true: S[gb] = sum exp2(t - M[gb]) (M: finite).
-template <int GB, bool W, bool SUM>
+//   SWEEP_MAX: M[gb] = max t, count = the members, visited = the rows looked at;   SWEEP_SUM: S[gb] = sum exp2(t - M[gb]) (M: finite);
+//   SWEEP_ARGMAX: SWEEP_MAX, and A[gb] = the smallest row whose t is M[gb] (-1: none above -inf), bit gb of nans set where a member's t is NaN.
+enum Mode { SWEEP_MAX = 0, SWEEP_SUM = 1, SWEEP_ARGMAX = 2 };
+template <int GB, bool W, int MODE>
 RNF_FM_HD void sweep(const Geometry &ge, const Frame &fr, const float *__restrict__ grid, const float *__restrict__ lw, long long Q, int g0, int G,
-                     const float q[9], float *M, double *S, int &count, int &visited) {
+                     const float q[9], float *M, double *S, int *A, unsigned &nans, int &count, int &visited) {
     const float *lwg[GB];
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) lwg[gb] = W ? lw + (long long)(g0 + gb < G ? g0 + gb : G - 1) * Q : nullptr;
@@ -241,21 +249,27 @@ RNF_FM_HD void sweep(const Geometry &ge, const Frame &fr, const float *__restric
                     for (int t = ta; t < tb; ++t) {
                         const int r = t * ge.npix + first + j;                              // < 72 * 8^level <= 2^31 / 9
                         const float d2 = ks::dist2(grid + 9 * r, q);
-                        if (!SUM) ++visited;                                                // dead code where the caller drops it
+                        if (MODE != SWEEP_SUM) ++visited;                                   // dead code where the caller drops it
                         if (!(d2 <= ge.cut)) continue;
-                        if (!SUM) ++count;
+                        if (MODE != SWEEP_SUM) ++count;
 #pragma unroll
                         for (int gb = 0; gb < GB; ++gb) {
                             const float l2 = W ? lwg[gb][r] * (float)ks::LOG2E : 0.f;
                             const float tt = fmaf(-ge.h, d2, l2);
-                            if (SUM)
+                            if (MODE == SWEEP_SUM)
                                 part[gb] += exp2_soft(tt - M[gb]);
-                            else
+                            else if (MODE == SWEEP_MAX)
                                 M[gb] = fmaxf(M[gb], tt);
+                            else if (tt != tt)
+                                nans |= 1u << gb;
+                            else if (tt > M[gb] || (tt == M[gb] && r < A[gb])) {                // members come by (ring, pixel, tilt), not by row
+                                M[gb] = tt;
+                                A[gb] = r;
+                            }
                         }
                     }
                 }
-                if (SUM) {
+                if (MODE == SWEEP_SUM) {
 #pragma unroll
                     for (int gb = 0; gb < GB; ++gb) S[gb] += (double)part[gb];
                 }
@@ -278,12 +292,13 @@ RNF_FM_HD void query_local(const Geometry &ge, const float *offset, const float 
         S[gb] = 0.0;
     }
     count = visited = 0;
-    sweep<GB, W, false>(ge, fr, grid, lw, Q, g0, G, q, M, S, count, visited);
+    unsigned none = 0;
+    sweep<GB, W, SWEEP_MAX>(ge, fr, grid, lw, Q, g0, G, q, M, S, nullptr, none, count, visited);
     float Mu[GB];                                  // no live member: M = -inf, every term exp2(-inf - 0) = 0 (a NaN log-weight stays NaN)
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) Mu[gb] = M[gb] == -INFINITY ? 0.f : M[gb];
     int unused = 0;
-    sweep<GB, W, true>(ge, fr, grid, lw, Q, g0, G, q, Mu, S, unused, unused);
+    sweep<GB, W, SWEEP_SUM>(ge, fr, grid, lw, Q, g0, G, q, Mu, S, nullptr, none, unused, unused);
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) {
         const double s = S[gb];
@@ -295,6 +310,31 @@ RNF_FM_HD void query_local(const Geometry &ge, const float *offset, const float 
         else
             r = (float)(((double)M[gb] + log2(s)) * ks::LN2 - l_kappa);
         out[gb] = r;
+    }
+}
+
+// One query, GB groups of rnf_so3_grid_local_max: out[gb] = max_j (lw[g][j] - (kappa/2) d^2) - l(kappa) over the members, arg[gb] the
+// smallest row attaining it.  ONE sweep: the maximum and the tie are decided on the sum's own fp32 term t, no exp2.
+template <int GB, bool W>
+RNF_FM_HD void query_local_max(const Geometry &ge, const float *offset, const float *__restrict__ grid, const float *__restrict__ lw, long long Q,
+                               int g0, int G, const float q[9], double l_kappa, float *out, int *arg, int &count, int &visited) {
+#pragma clang fp contract(off)                     // the last expression below: the host build rounds it the same way
+    const Frame fr = frame_of(ge, offset, q);
+    float M[GB];
+    int A[GB];
+#pragma unroll
+    for (int gb = 0; gb < GB; ++gb) {
+        M[gb] = -INFINITY;
+        A[gb] = -1;
+    }
+    count = visited = 0;
+    unsigned nans = 0;
+    sweep<GB, W, SWEEP_ARGMAX>(ge, fr, grid, lw, Q, g0, G, q, M, nullptr, A, nans, count, visited);
+#pragma unroll
+    for (int gb = 0; gb < GB; ++gb) {
+        const bool bad = !fr.finite || ((nans >> gb) & 1u);
+        out[gb] = bad ? NAN : A[gb] < 0 ? -INFINITY : (float)((double)M[gb] * ks::LN2 - l_kappa);
+        arg[gb] = bad ? -1 : A[gb];
     }
 }
 
@@ -318,6 +358,30 @@ __global__ __launch_bounds__(THREADS) void so3_grid_local_kernel(Geometry ge, co
         if (g0 + gb < G) out[(long long)(g0 + gb) * m + i] = res[gb];
     if (count && g0 == 0) count[i] = cnt;
 }
+
+// the same launch shape for rnf_so3_grid_local_max: out[g][i], arg[g][i], count[i]
+template <int GB, bool W>
+__global__ __launch_bounds__(THREADS) void so3_grid_local_max_kernel(Geometry ge, const float *__restrict__ offset, const float *__restrict__ grid,
+                                                                     const float *__restrict__ queries, const float *__restrict__ lw, long long Q,
+                                                                     int m, int G, double l_kappa, float *__restrict__ out, int *__restrict__ arg,
+                                                                     int *__restrict__ count) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= m) return;
+    const int g0 = blockIdx.y * GB;
+    float q[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) q[k] = queries[9 * i + k];
+    float res[GB];
+    int at[GB], cnt, visited;
+    query_local_max<GB, W>(ge, offset, grid, lw, Q, g0, G, q, l_kappa, res, at, cnt, visited);
+#pragma unroll
+    for (int gb = 0; gb < GB; ++gb)
+        if (g0 + gb < G) {
+            out[(long long)(g0 + gb) * m + i] = res[gb];
+            arg[(long long)(g0 + gb) * m + i] = at[gb];
+        }
+    if (count && g0 == 0) count[i] = cnt;
+}
 #endif  // __HIPCC__ && !RNF_SGL_HOST_ONLY
 
 // out [G][m] and count [m] (or null) of rnf_so3_grid_local_sum on the host, with the kernel's row functions in the kernel's order
@@ -338,6 +402,28 @@ inline void host_grid_local_sum(int level, const float *offset, const float *gri
             else
                 query_local<1, false>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, cnt, vis);
             out[(long long)g * m + i] = r;
+            if (count && g == 0) count[i] = cnt;
+            if (visited && g == 0) visited[i] = vis;
+        }
+}
+
+// out [G][m], arg [G][m] and count [m] (or null) of rnf_so3_grid_local_max on the host, as host_grid_local_sum
+inline void host_grid_local_max(int level, const float *offset, const float *grid, const float *queries, const float *lw, long long m, int G,
+                                double kappa, double d2_cut, float *out, int *arg, int *count, int *visited = nullptr) {
+    const Geometry ge = geometry_of(level, kappa, d2_cut);
+    const long long Q = rows_of(level);
+    const double l_kappa = ks::log_normaliser(kappa);
+    if (!queries) queries = grid;
+    for (long long i = 0; i < m; ++i)
+        for (int g = 0; g < G; ++g) {
+            float r;
+            int at, cnt, vis;
+            if (lw)
+                query_local_max<1, true>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
+            else
+                query_local_max<1, false>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
+            out[(long long)g * m + i] = r;
+            arg[(long long)g * m + i] = at;
             if (count && g == 0) count[i] = cnt;
             if (visited && g == 0) visited[i] = vis;
         }

@@ -953,7 +953,154 @@ def grid_pose_filter(flow: Flow, features: torch.Tensor = None, kappa: float = N
     return dict(est=grid[index], index=index, log_evidence=torch.cat(evidences), posterior=post[0], grid=grid, offset=offset)
 
 
-SPECTRAL_TRUNCATION = 1e-2                          # the largest (2L+1) h_L the spectral passes accept
+def _sequence_args(log_likelihood, grid, level, log_prior, who: str):
+    """-> (log-likelihoods [B,T,Q] float32, whether the caller gave the B axis, log_prior [B,Q] float32 or None)"""
+    ll = log_likelihood
+    if not isinstance(ll, torch.Tensor) or ll.dim() not in (2, 3):
+        raise ValueError(f"{who}: log_likelihood {tuple(getattr(ll, 'shape', ()))} (want [T,Q] or [B,T,Q])")
+    batched = ll.dim() == 3
+    ll = ll if batched else ll[None]
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape) != (ll.shape[2], 3, 3):
+        raise ValueError(f"{who}: grid {tuple(getattr(grid, 'shape', ()))} for log_likelihood {tuple(log_likelihood.shape)} (want [Q,3,3])")
+    if grid.shape[0] != 72 * 8 ** int(level):
+        raise ValueError(f"{who}: grid holds {grid.shape[0]} rows, level {level} has {72 * 8 ** int(level)}")
+    B, T, Q = ll.shape
+    if T < 1 or not 1 <= B <= 65535:
+        raise ValueError(f"{who}: log_likelihood holds {B} sequences of {T} frames (1 to 65535 sequences, at least one frame)")
+    if not ll.is_cuda or not grid.is_cuda:
+        raise ValueError(f"{who}: log_likelihood and grid must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
+    prior = None
+    if log_prior is not None:
+        if not isinstance(log_prior, torch.Tensor) or tuple(log_prior.shape) not in ((Q,), (B, Q)):
+            raise ValueError(f"{who}: log_prior {tuple(getattr(log_prior, 'shape', ()))}, expected [{Q}] or [{B},{Q}]")
+        prior = log_prior.detach().to(device=ll.device, dtype=torch.float32).reshape(-1, Q).expand(B, Q).contiguous()
+    return ll.detach().to(torch.float32), batched, prior
+
+
+def _recentre(delta):
+    """delta [B,Q] float64 -> (delta - its row maximum as float32, the maxima [B] float64; 0 where a row holds no finite number)"""
+    top = delta.max(dim=1).values
+    top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))
+    return (delta - top[:, None]).to(torch.float32), top
+
+
+def grid_viterbi(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None,
+                 log_prior: torch.Tensor = None) -> dict:
+    """The most probable JOINT sequence of grid rows under the model ``grid_pose_filter`` implies (Viterbi): per-frame arg-maxes are not
+    a path -- on a symmetric object they hop between equivalent modes -- this is one.  ``log_likelihood`` [T,Q] or [B,T,Q]: each frame's
+    log-likelihood on the rows of ``grid`` [Q,3,3] of ``level`` and ``offset``.  The model: a step j -> i has the mass
+    k(R_j, R_i) / (Z_j Q) on the neighbourhood N(j) of ``grid_diffuse_local`` (``kappa``, ``radius_deg``, its per-row Z_j); the initial
+    density pi_0 is uniform (``log_prior`` None) or ``grid_diffuse_local(log_prior)`` ([Q] or [B,Q]), the filter's predicted density of
+    frame 0; p(x, y) = pi_0(x_0)/Q  prod_t k(x_{t-1}, x_t) / (Z Q)  prod_t l_t(x_t).  The recursion
+        delta_0(i) = log pi_0(i) - log Q + l_0(i),    delta_t(i) = l_t(i) + max_{j in N(i)} [delta_{t-1}(j) - log Z_j + log k(R_j, R_i)] - log Q
+    runs on the max-plus pass ``utils.kde.so3_grid_local_log_max`` with the B sequences as its groups (neighbourhoods are symmetric, so
+    the backward operator is the forward one).  Its log-weights delta - log Z are formed in fp64 and rounded once; delta is re-centred on
+    its maximum every frame and the offsets are summed in fp64.  Ties go to the smallest row.  The back-pointers are kept as int32
+    [T,B,Q] -- 4 T B Q bytes, 9.4 MB per frame and sequence at level 5 -- and followed by T device-side gathers: no host synchronisation.
+    -> dict(index [B,T] int64 the path's rows, est [B,T,3,3] its rotations, log_joint [B] float64 = log p(path, y)); without the B
+    axis where ``log_likelihood`` came without it.  T = 1 gives the arg-max of pi_0 l_0."""
+    from .utils.kde import so3_grid_local_log_max, so3_grid_local_log_sum
+    who = "grid_viterbi"
+    ll, batched, prior = _sequence_args(log_likelihood, grid, level, log_prior, who)
+    B, T, Q = ll.shape
+    log_q = float(np.log(Q))
+    with torch.no_grad():
+        delta = ll[:, 0].to(torch.float64) - log_q
+        if prior is not None:
+            delta = delta + grid_diffuse_local(prior, grid, level, kappa, radius_deg, offset).to(torch.float64)
+        delta, log_joint = _recentre(delta)
+        back = torch.empty(T, B, Q, dtype=torch.int32, device=ll.device)
+        if T > 1:
+            lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64) - log_q    # log Z_j
+        for t in range(1, T):
+            lw = (delta.to(torch.float64) - lz).to(torch.float32)
+            best, arg = so3_grid_local_log_max(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
+            back[t] = arg
+            delta, top = _recentre(ll[:, t].to(torch.float64) + best.to(torch.float64) - log_q)
+            log_joint = log_joint + top
+        index = torch.empty(B, T, dtype=torch.int64, device=ll.device)
+        index[:, T - 1] = torch.argmax(delta, dim=1)
+        log_joint = log_joint + delta.max(dim=1).values.to(torch.float64)        # 0 after re-centring, -inf where no path has mass
+        for t in range(T - 1, 0, -1):
+            index[:, t - 1] = back[t].gather(1, index[:, t, None])[:, 0].to(torch.int64).clamp_min(0)    # -1: no predecessor with mass
+        est = grid[index]
+    if not batched:
+        index, est, log_joint = index[0], est[0], log_joint[0]
+    return dict(index=index, est=est, log_joint=log_joint)
+
+
+def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None,
+                log_prior: torch.Tensor = None) -> dict:
+    """Fixed-interval smoothing on the SO(3) grid: every frame of a recorded sequence judged with all of it, p(x_t | y_0..T-1), by the
+    forward-backward recursion on the model of ``grid_viterbi`` (same arguments).  Forward: the ``grid_filter_step`` chain itself, frame 0
+    from ``log_prior`` (None: uniform, and as in ``grid_pose_filter`` nothing is diffused before it: its posterior is its normalised
+    likelihood).  Backward, with b_{T-1} = 0 and the existing neighbour-limited sum (the neighbourhoods and the kernel are symmetric, so
+    the backward operator is the forward one, scaled by the per-row Z_j of ``grid_diffuse_local``):
+        b_t(j) = log sum_{i in N(j)} k(R_j, R_i) l_{t+1}(i) exp b_{t+1}(i) - log Z_j - log Q - log_evidence_{t+1},
+    log-weights and result formed in fp64 and rounded once.  smoothed_t = filtered_t + b_t, renormalised in fp64 (the last frame, where
+    b = 0 exactly, is the filtered one bit for bit).
+    -> dict(smoothed [B,T,Q] and filtered [B,T,Q] float32 log-densities with sum exp / Q = 1, log_evidence [B,T] float64 as
+    ``grid_filter_step``'s, backward [B,T,Q] float32 the b_t, index [B,T] and est [B,T,3,3] the smoothed arg-max); without the B axis
+    where ``log_likelihood`` came without it.  Three [B,T,Q] float32 arrays are kept."""
+    from .utils.kde import so3_grid_local_log_sum
+    who = "grid_smooth"
+    ll, batched, prior = _sequence_args(log_likelihood, grid, level, log_prior, who)
+    B, T, Q = ll.shape
+    log_q = float(np.log(Q))
+    with torch.no_grad():
+        filtered = torch.empty(B, T, Q, dtype=torch.float32, device=ll.device)
+        evidence = torch.empty(B, T, dtype=torch.float64, device=ll.device)
+        post = prior
+        for t in range(T):
+            if post is None:                                                # a uniform prior: nothing to diffuse
+                ll64 = ll[:, 0].to(torch.float64)
+                ev = torch.logsumexp(ll64, dim=1) - log_q
+                post = (ll64 - ev[:, None]).to(torch.float32)
+            else:
+                step = grid_filter_step(post, ll[:, t], grid, level, kappa, radius_deg, offset)
+                post, ev = step["posterior"], step["log_evidence"]
+            filtered[:, t], evidence[:, t] = post, ev
+        backward = torch.zeros(B, T, Q, dtype=torch.float32, device=ll.device)
+        smoothed = torch.empty_like(filtered)
+        smoothed[:, T - 1] = filtered[:, T - 1]
+        if T > 1:
+            lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64)    # log Z_j + log Q
+        for t in range(T - 2, -1, -1):
+            lw = (ll[:, t + 1].to(torch.float64) + backward[:, t + 1].to(torch.float64)).to(torch.float32)
+            s = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
+            backward[:, t] = (s.to(torch.float64) - lz - evidence[:, t + 1, None]).to(torch.float32)
+            both = filtered[:, t].to(torch.float64) + backward[:, t].to(torch.float64)
+            smoothed[:, t] = (both - (torch.logsumexp(both, dim=1, keepdim=True) - log_q)).to(torch.float32)
+        index = torch.argmax(smoothed, dim=2)
+        est = grid[index]
+    res = dict(smoothed=smoothed, filtered=filtered, log_evidence=evidence, backward=backward, index=index, est=est)
+    return res if batched else {k: v[0] for k, v in res.items()}
+
+
+def grid_pose_smooth(flow: Flow, features: torch.Tensor = None, kappa: float = None, recursion_level: int = 4, radius_deg: float = None, offset=None,
+                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None) -> dict:
+    """``grid_pose_filter`` for a RECORDED sequence: the frames' grid log-densities -- collected on the launches of
+    ``grid_estimate_rotations``, one row per frame of ``features`` [T,F] -- are judged together, by ``grid_smooth`` (each frame's marginal
+    given the whole clip) and by ``grid_viterbi`` (the most probable joint path; on a symmetric object it stays on one branch where the
+    per-frame arg-max hops).  Arguments as ``grid_pose_filter``; ``log_prior`` [Q] or None.  T Q floats are kept for the likelihoods, and
+    what the two recursions keep.  Flows with batch-coupled layers are refused.
+    -> dict(est_smoothed [T,3,3], index_smoothed [T], est_path [T,3,3], index_path [T], log_evidence [T] float64, log_joint float64 [],
+    smoothed [T,Q], grid [Q,3,3], offset [3,3])."""
+    who = "grid_pose_smooth"
+    if kappa is None:
+        raise ValueError(f"{who}: kappa is required")
+    _refuse_batch_coupled(flow, who, ", so a frame's likelihood would depend on the frames that share its launch")
+    gf, level, offset = _grid_inputs(flow, features, None, recursion_level, offset, base, who)
+    with torch.no_grad():
+        grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
+        ll = torch.cat([lp.to(torch.float32).clone() for _, _, lp in gf.images(grid, images_per_launch, who)])
+        smooth = grid_smooth(ll, grid, level, kappa, radius_deg, offset, log_prior)
+        path = grid_viterbi(ll, grid, level, kappa, radius_deg, offset, log_prior)
+    return dict(est_smoothed=smooth["est"], index_smoothed=smooth["index"], est_path=path["est"], index_path=path["index"],
+                log_evidence=smooth["log_evidence"], log_joint=path["log_joint"], smoothed=smooth["smoothed"], grid=grid, offset=offset)
+
+
+SPECTRAL_TRUNCATION = 1e-2                        # the largest (2L+1) h_L the spectral passes accept
 
 
 def _spectral_multiplier(kappa, t, lmax: int, who: str, required: bool = True):

@@ -33,9 +33,10 @@ from .grid_pose import (grid_ball_estimate, grid_beam_estimate_rotations, grid_b
                         grid_pose_error, grid_pose_fisher, grid_pose_fit, grid_pose_mixture, grid_pose_modes, grid_pose_modes_refined)
 from .grid_pose import grid_error_symmetric, grid_pose_error_symmetric, grid_set_error  # noqa: F401
 from .grid_pose import grid_diffuse_local, grid_filter_step, grid_pose_filter  # noqa: F401
+from .grid_pose import grid_pose_smooth, grid_smooth, grid_viterbi  # noqa: F401
 from .grid_pose import grid_pose_sample, grid_sample  # noqa: F401
 from .grid_pose import grid_compose, grid_diffuse_spectral, grid_pose_spectrum, grid_spectrum  # noqa: F401
-from .utils.kde import so3_grid_local_log_sum  # noqa: F401
+from .utils.kde import so3_grid_local_log_max, so3_grid_local_log_sum  # noqa: F401
 
 
 def load_reference_checkpoint(path, map_location="cpu") -> dict:

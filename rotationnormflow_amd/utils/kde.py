@@ -162,7 +162,24 @@ def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = N
     a row with log-weight -inf drops out, a NaN log-weight inside a query's neighbourhood gives NaN, a non-finite query NaN and count 0.
     A result is bit-identical from run to run and however the call is tiled, so the tiling of queries and groups is invisible.
     Stream-ordered, no host synchronisation, no workspace, no gradient."""
-    who = "so3_grid_local_log_sum"
+    return _grid_local_pass("so3_grid_local_log_sum", False, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count)
+
+
+def so3_grid_local_log_max(grid, level: int, kappa: float, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
+                           offset=None, return_count: bool = False):
+    """The max-plus pass over the neighbourhoods of ``so3_grid_local_log_sum`` on the device (``rnf_so3_grid_local_max``,
+    csrc/so3_grid_local.h): out[g][i] = max_{j: d^2(G_j, Q_i) <= cut} (log_weights[g][j] - (kappa/2) d^2(G_j, Q_i)) - l(kappa), the largest
+    TERM of that sum, and arg[g][i] = the smallest grid row j attaining it -- the step of a Viterbi recursion (``grid_pose.grid_viterbi``).
+    Arguments, cut, membership and tiling are those of ``so3_grid_local_log_sum``.
+    -> (float32 [m] or [G,m], int64 of the same shape) (with ``return_count`` also int32 [m]).  An empty neighbourhood, or one whose rows
+    all have log-weight -inf, gives -inf and arg -1; a NaN log-weight inside a query's neighbourhood gives NaN and -1, a non-finite query
+    NaN, -1 and count 0.  The maximum and the tie are decided on the kernel's fp32 term.  A result is bit-identical from run to run and
+    however the call is tiled.  Stream-ordered, no host synchronisation, no workspace, no gradient."""
+    return _grid_local_pass("so3_grid_local_log_max", True, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count)
+
+
+def _grid_local_pass(who: str, with_arg: bool, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count):
+    """The argument checks and the tiling the two neighbour-limited passes share; ``with_arg``: the max pass, -> (out, arg int64[, count])"""
     if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape[-2:]) != (3, 3):
         raise ValueError(f"{who}: grid {tuple(getattr(grid, 'shape', ()))}, expected [Q,3,3]")
     level = int(level)
@@ -203,6 +220,7 @@ def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = N
     if offset is not None:
         off = offset.detach().reshape(9).to(device=dev, dtype=torch.float32).contiguous()
     out = torch.empty(G, m, dtype=torch.float32, device=dev)
+    arg = torch.empty(G, m, dtype=torch.int32, device=dev) if with_arg else None
     count = torch.empty(m, dtype=torch.int32, device=dev) if return_count else None
     m_tile = max(4, int(LOCAL_QUERY_TILE) // 4 * 4)
     g_tile = max(1, min(int(LOCAL_GROUP_TILE), MAX_GROUPS))
@@ -215,14 +233,23 @@ def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = N
             dst = part if whole else torch.empty(g1 - g0, i1 - i0, dtype=torch.float32, device=dev)
             all_rows = Qr is Gr and i0 == 0 and i1 == m                      # a null pointer stands for the grid rows
             tile = None if all_rows else _aligned(Qr[i0:i1])
-            args = _lib.So3GridLocalSum(level=level, offset=None if off is None else off.data_ptr(), grid=Gr.data_ptr(),
-                                        queries=None if all_rows else tile.data_ptr(), log_weights=lw[g0:g1].data_ptr() if lw is not None else None,
-                                        m=i1 - i0, G=g1 - g0, kappa=k, d2_cut=cut, out=dst.data_ptr(),
-                                        count=count[i0:i1].data_ptr() if return_count and g0 == 0 else None)
-            _lib.call("so3_grid_local_sum", args, dev)
+            common = dict(level=level, offset=None if off is None else off.data_ptr(), grid=Gr.data_ptr(),
+                          queries=None if all_rows else tile.data_ptr(), log_weights=lw[g0:g1].data_ptr() if lw is not None else None,
+                          m=i1 - i0, G=g1 - g0, kappa=k, d2_cut=cut, out=dst.data_ptr(),
+                          count=count[i0:i1].data_ptr() if return_count and g0 == 0 else None)
+            if with_arg:
+                adst = arg[g0:g1, i0:i1] if whole else torch.empty(g1 - g0, i1 - i0, dtype=torch.int32, device=dev)
+                _lib.call("so3_grid_local_max", _lib.So3GridLocalMax(arg=adst.data_ptr(), **common), dev)
+                if not whole:
+                    arg[g0:g1, i0:i1].copy_(adst)
+            else:
+                _lib.call("so3_grid_local_sum", _lib.So3GridLocalSum(**common), dev)
             if not whole:
                 part.copy_(dst)
     out = out if grouped else out[0]
+    if with_arg:
+        arg = arg.to(torch.int64)
+        return (out, arg if grouped else arg[0]) + ((count,) if return_count else ())
     return (out, count) if return_count else out
 
 
