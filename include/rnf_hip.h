@@ -873,6 +873,40 @@ typedef struct RnfSo3GridLocalMax {
 } RnfSo3GridLocalMax;
 int rnf_so3_grid_local_max(const RnfSo3GridLocalMax *max);
 
+/* The two passes above on an ANISOTROPIC matrix-Fisher kernel (csrc/so3_grid_local.h): the transition of a grid filter whose motion
+ * x' = x E, E ~ MF(A), drifts and is tighter about some body axes than others.  With the proper SVD A = U diag(s) V^T, the drift
+ * Delta = U V^T and the symmetric concentration K = V diag(s) V^T (A = Delta K), the density of the step from Q to G is
+ *   k_K(C, G) = exp(-1/2 tr((G - C) K (G - C)^T) - l(K)),   C = Q Delta,   l(K) = c(K) - tr K,
+ * c the exact log-normaliser of rnf_fisher_exact (computed here on the host in fp64).  The drift is the CALLER's: this entry takes K
+ * alone and evaluates k_K between the stored rows and the queries, so a drifting model passes the shifted rows C = G Delta (the rows of
+ * the grid with offset O Delta) on one side.  With arg NULL it is rnf_so3_grid_local_sum,
+ *   out[g][i] = log sum_{j : d^2(G_j, Q_i) <= d2_cut} exp(log_weights[g][j]) k_K(G_j, Q_i),
+ * with arg non-NULL rnf_so3_grid_local_max (the largest term, and the smallest row attaining it).  Membership is the isotropic
+ * passes' -- the fp32 |G_j - Q_i|_F^2 <= d2_cut on the stored rows, a ball -- and so are the enumeration, the order of the terms, the
+ * edge cases, the determinism and the tiling: a result is bit-identical from run to run and whatever m, G, the query's position and
+ * the group's position are.  The term is symmetric bit for bit in (row, query).  The exponent is bounded by -(s2 + s3)/4 d^2.  K = kappa I
+ * is the isotropic kernel of concentration kappa (to rounding; the log-weights are NOT normalised here either).
+ * Refused before any launch: a non-finite K; a K that is not symmetric to 1e-9 |K|_F; eigenvalues with a pair sum below -1e-9 |K|_F
+ * (K is then not the symmetric factor of a proper SVD); a largest |eigenvalue| above 3e4 (the range rnf_fisher_exact is tested on);
+ * and everything rnf_so3_grid_local_sum / _max refuse.  One launch, no workspace.  Stream-ordered, no host synchronisation, capturable. */
+typedef struct RnfSo3GridLocalFisher {
+    size_t struct_bytes;        /* sizeof(RnfSo3GridLocalFisher); any other value is refused (header and library differ) */
+    int32_t level;              /* 0..6: Q = 72 * 8^level grid rows */
+    const float *offset;        /* dev float[9], the offset of the rows in grid (row-major, a rotation), or NULL (the identity) */
+    const float *grid;          /* dev float[Q][9] row-major, 16-byte aligned */
+    const float *queries;       /* dev float[m][9] row-major, 16-byte aligned, or NULL: the grid rows (then m must be Q) */
+    const float *log_weights;   /* dev float[G][Q], or NULL (zeros) */
+    int64_t m;                  /* queries, 0..2^31 - 1 */
+    int32_t G;                  /* groups (rows of log-weights), 1..65535 */
+    double concentration[9];    /* K row-major: symmetric, finite, eigenvalue pair sums >= 0, |eigenvalues| <= 3e4 */
+    double d2_cut;              /* finite, 0..8; 8 (180 degrees) covers every row */
+    float *out;                 /* dev float[G][m] */
+    int32_t *arg;               /* dev int32[G][m], or NULL: the sum; non-NULL: the max-plus pass */
+    int32_t *count;             /* dev int32[m], or NULL */
+    void *stream;
+} RnfSo3GridLocalFisher;
+int rnf_so3_grid_local_fisher(const RnfSo3GridLocalFisher *fisher);
+
 /* Harmonic analysis on SO(3) (csrc/so3_harmonics.h).  Y_l(x) is the vector of the 2l+1 orthonormal real spherical harmonics of degree
  * l, m = -l..l: sqrt2 (-1)^m Re Y_l^m for m > 0, sqrt2 (-1)^m Im Y_l^|m| for m < 0, Y_l^0 for m = 0 (for l = 1: y, z, x).  The Wigner
  * matrix D^l(R) is the real orthogonal (2l+1) x (2l+1) matrix with Y_l(R x) = D^l(R) Y_l(x): D^l(R1 R2) = D^l(R1) D^l(R2), D^0 = 1,

@@ -135,6 +135,13 @@ class So3GridLocalMax(_Pass):
                 ("out", C.c_void_p), ("arg", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class So3GridLocalFisher(_Pass):
+    """RnfSo3GridLocalFisher (include/rnf_hip.h): the two neighbour-limited passes on an anisotropic matrix-Fisher kernel."""
+    _fields_ = [("struct_bytes", C.c_size_t), ("level", C.c_int32), ("offset", C.c_void_p), ("grid", C.c_void_p), ("queries", C.c_void_p),
+                ("log_weights", C.c_void_p), ("m", C.c_int64), ("G", C.c_int32), ("concentration", C.c_double * 9), ("d2_cut", C.c_double),
+                ("out", C.c_void_p), ("arg", C.c_void_p), ("count", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class So3Wigner(_Pass):
     """RnfSo3Wigner (include/rnf_hip.h): the real Wigner matrices of rotations, degrees 0..lmax."""
     _fields_ = [("struct_bytes", C.c_size_t), ("rotations", C.c_void_p), ("n", C.c_int64), ("lmax", C.c_int32), ("out", C.c_void_p),
@@ -263,6 +270,7 @@ _SIGNATURES = {
     "rnf_so3_set_angle_cdf_workspace_bytes": (C.c_size_t, [C.POINTER(So3SetAngleCdf)]),
     "rnf_so3_grid_local_sum": (C.c_int, [C.POINTER(So3GridLocalSum)]),
     "rnf_so3_grid_local_max": (C.c_int, [C.POINTER(So3GridLocalMax)]),
+    "rnf_so3_grid_local_fisher": (C.c_int, [C.POINTER(So3GridLocalFisher)]),
     "rnf_so3_wigner": (C.c_int, [C.POINTER(So3Wigner)]),
     "rnf_so3_wigner_workspace_bytes": (C.c_size_t, [C.POINTER(So3Wigner)]),
     "rnf_so3_fourier": (C.c_int, [C.POINTER(So3Fourier)]),

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -2144,7 +2145,9 @@ static int so3_grid_local_check(const P *p, const char *who, const void *arg, co
     if (p->level < 0 || p->level > sgl::MAX_LEVEL) return fail("%s.level=%d outside 0..%d", who, p->level, sgl::MAX_LEVEL);
     if (p->G < 1 || p->G > sgl::MAX_G) return fail("%s.G=%d outside 1..65535", who, p->G);
     if (p->m < 0 || p->m > sgl::MAX_M) return fail("%s.m=%lld outside 0..2^31-1", who, (long long)p->m);
-    if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("%s.kappa=%g outside 0..1e6", who, p->kappa);
+    if constexpr (!std::is_same<P, RnfSo3GridLocalFisher>::value) {                          // the anisotropic entry checks its K itself
+        if (!(p->kappa >= 0.0 && p->kappa <= ks::MAX_KAPPA)) return fail("%s.kappa=%g outside 0..1e6", who, p->kappa);
+    }
     if (!(p->d2_cut >= 0.0 && p->d2_cut <= sgl::MAX_D2)) return fail("%s.d2_cut=%g outside 0..8", who, p->d2_cut);
     if (check_aligned16(p->grid, p->queries, who, ": grid and queries")) return 1;
     if (reinterpret_cast<uintptr_t>(p->offset) % 4 || reinterpret_cast<uintptr_t>(p->log_weights) % 4 || reinterpret_cast<uintptr_t>(p->out) % 4 ||
@@ -2196,6 +2199,51 @@ extern "C" int rnf_so3_grid_local_max(const RnfSo3GridLocalMax *p) {
         so3_grid_local_max_launch<1, true>(p, ge, queries, l_kappa, s);
     else
         so3_grid_local_max_launch<sgl::GROUPS_PER_THREAD, true>(p, ge, queries, l_kappa, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The anisotropic term on the same two passes (csrc/so3_grid_local.h, F): arg selects the max-plus pass.  One launch, no workspace.
+template <int GB, bool W, bool MAX>
+static void so3_grid_local_fisher_launch(const RnfSo3GridLocalFisher *p, const sgl::Geometry &ge, const sgl::Quad &kq, const float *Q, double l_k,
+                                         hipStream_t s) {
+    const dim3 grid((unsigned)((p->m + sgl::THREADS - 1) / sgl::THREADS), (unsigned)((p->G + GB - 1) / GB));
+    hipLaunchKernelGGL((sgl::so3_grid_local_fisher_kernel<GB, W, MAX>), grid, dim3(sgl::THREADS), 0, s, ge, kq, p->offset, p->grid, Q,
+                       p->log_weights, sgl::rows_of(p->level), (int)p->m, (int)p->G, l_k, p->out, p->arg, p->count);
+}
+
+template <bool MAX>
+static void so3_grid_local_fisher_pick(const RnfSo3GridLocalFisher *p, const sgl::Geometry &ge, const sgl::Quad &kq, const float *Q, double l_k,
+                                       hipStream_t s) {
+    if (!p->log_weights)
+        so3_grid_local_fisher_launch<1, false, MAX>(p, ge, kq, Q, l_k, s);
+    else if (p->G == 1)
+        so3_grid_local_fisher_launch<1, true, MAX>(p, ge, kq, Q, l_k, s);
+    else
+        so3_grid_local_fisher_launch<sgl::GROUPS_PER_THREAD, true, MAX>(p, ge, kq, Q, l_k, s);
+}
+
+extern "C" int rnf_so3_grid_local_fisher(const RnfSo3GridLocalFisher *p) {
+    const char *who = "RnfSo3GridLocalFisher";
+    if (check_struct(p, who)) return 1;
+    switch (sgl::concentration_defect(p->concentration)) {
+        case 1: return fail("%s.concentration holds a non-finite entry", who);
+        case 2: return fail("%s.concentration is not symmetric to 1e-9 of its norm", who);
+        case 3: return fail("%s.concentration has two eigenvalues with a negative sum: not the symmetric factor of a proper SVD", who);
+        case 4: return fail("%s.concentration has an eigenvalue beyond 3e4 in magnitude", who);
+        default: break;
+    }
+    if (const int r = so3_grid_local_check(p, who, p->arg, ", arg")) return r > 0;
+    if (!p->grid || !p->out) return fail("%s: null grid or out", who);
+    const sgl::Geometry ge = sgl::geometry_of(p->level, 0.0, p->d2_cut);
+    const sgl::Quad kq = sgl::quad_of(p->concentration);
+    const double l_k = sgl::log_normaliser_fisher(p->concentration);
+    const float *queries = p->queries ? p->queries : p->grid;
+    hipStream_t s = reinterpret_cast<hipStream_t>(p->stream);
+    if (p->arg)
+        so3_grid_local_fisher_pick<true>(p, ge, kq, queries, l_k, s);
+    else
+        so3_grid_local_fisher_pick<false>(p, ge, kq, queries, l_k, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

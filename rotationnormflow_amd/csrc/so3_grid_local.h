@@ -43,6 +43,19 @@
 // One sweep, no exp2.  The tie goes to the smallest ROW, compared explicitly: members arrive by (ring, pixel, tilt).  No live member
 // (none, or all at -inf): -inf and -1; a NaN log-weight inside the neighbourhood (fmaxf would drop it: a flag carries it): NaN and -1;
 // a non-finite query: NaN, -1, count 0.  The Viterbi recursion of grid_pose.grid_viterbi runs on it.
+//
+// The anisotropic variant (rnf_so3_grid_local_fisher; template parameter F of sweep, query_local and query_local_max, and
+// so3_grid_local_fisher_kernel for both passes).  A general matrix-Fisher step x' = x E, E ~ MF(A), A = Delta K with the drift Delta = U V^T and the symmetric concentration
+// K = V diag(s) V^T of the proper SVD, has for rotations Q, G with C = Q Delta and W = G - C
+//     tr(A^T Q^T G) - (s1 + s2 + s3) = -1/2 tr(W K W^T) = -1/2 sum_r w_r K w_r^T        (w_r the rows of W),
+// the difference form ks::dist2 gives the isotropic kernel (K = kappa I: -(kappa/2) |G - C|^2).  The drift needs nothing here: the
+// caller passes the shifted rows C.  A member's term is  t = lw log2(e) - quad,  quad = sum_r w_r Kh w_r^T  on the SAME nine
+// differences q[k] - c[k] the distance is taken from, Kh = (K / 2) log2(e) in fp32, six entries by value (Quad: the off-diagonal ones
+// doubled), in a fixed order of fmaf under fp contract(off) (fisher_term).  Every product holds two differences, so the term of
+// (query a, row b) is the term of (query b, row a) bit for bit.  Membership stays ks::dist2 <= cut; the enumeration, the sweep order,
+// max-then-sum, the fp32 / fp64 split, exp2_soft, the tie rule and the edge cases are the isotropic pass's.  The log-normaliser is
+// l(K) = c(K) - tr K with the exact c of fisher_exact.h, fp64 on the host (K = kappa I: ks::log_normaliser(kappa)).  The exponent is
+// bounded by -(s2 + s3)/4 |G - C|^2 (equality for rotations about the loosest axis): the ball of the loosest axis is the neighbourhood.
 #pragma once
 #if defined(RNF_SGL_HOST_ONLY) && !defined(RNF_KS_HOST_ONLY)
 #define RNF_KS_HOST_ONLY
@@ -80,6 +93,115 @@ inline Geometry geometry_of(int level, double kappa, double d2_cut) {
     ge.h = (float)(0.5 * kappa * ks::LOG2E);
     ge.cell = 1.1f / (float)ge.nside;
     return ge;
+}
+
+// The anisotropic variant's (K / 2) log2(e) in fp32: k[0..2] the diagonal, k[3..5] TWICE the entries 01, 02, 12; passed by value
+struct Quad { float k[6]; };
+
+inline Quad quad_of(const double K[9]) {
+    const double h = 0.5 * ks::LOG2E;
+    Quad qd;
+    qd.k[0] = (float)(h * K[0]);
+    qd.k[1] = (float)(h * K[4]);
+    qd.k[2] = (float)(h * K[8]);
+    qd.k[3] = (float)(h * (K[1] + K[3]));          // the symmetric part: 2 * (K01 + K10) / 2
+    qd.k[4] = (float)(h * (K[2] + K[6]));
+    qd.k[5] = (float)(h * (K[5] + K[7]));
+    return qd;
+}
+
+// The eigenvalues of the symmetric part of K by cyclic Jacobi in fp64, in decreasing order
+inline void sym_eigenvalues3(const double K[9], double ev[3]) {
+    double a[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) a[i][j] = 0.5 * (K[3 * i + j] + K[3 * j + i]);
+    for (int it = 0; it < 64; ++it) {
+        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+        const double diag = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2];
+        if (!(off > 1e-34 * diag)) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (a[p][q] == 0.0) continue;
+                const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {                                             // A <- A J
+                    const double akp = a[k][p], akq = a[k][q];
+                    a[k][p] = c * akp - s * akq;
+                    a[k][q] = s * akp + c * akq;
+                }
+                for (int k = 0; k < 3; ++k) {                                             // A <- J^T A
+                    const double apk = a[p][k], aqk = a[q][k];
+                    a[p][k] = c * apk - s * aqk;
+                    a[q][k] = s * apk + c * aqk;
+                }
+            }
+    }
+    ev[0] = a[0][0];
+    ev[1] = a[1][1];
+    ev[2] = a[2][2];
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2 - i; ++j)
+            if (ev[j] < ev[j + 1]) {
+                const double t = ev[j];
+                ev[j] = ev[j + 1];
+                ev[j + 1] = t;
+            }
+}
+
+constexpr double MAX_CONCENTRATION = 3e4;          // the largest |eigenvalue| of K: the range fisher_exact is tested on
+constexpr double SYMMETRY_TOL = 1e-9;              // |K - K^T|_F and a negative pair sum of eigenvalues, relative to |K|_F
+
+// What rnf_so3_grid_local_fisher refuses of a concentration: 0 fine, 1 non-finite, 2 not symmetric, 3 a negative pair sum of
+// eigenvalues (not the symmetric factor of a proper SVD), 4 an eigenvalue beyond MAX_CONCENTRATION
+inline int concentration_defect(const double K[9]) {
+    double n2 = 0.0, a2 = 0.0;
+    for (int k = 0; k < 9; ++k) {
+        if (!(fabs(K[k]) < INFINITY)) return 1;
+        n2 += K[k] * K[k];
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) a2 += (K[3 * i + j] - K[3 * j + i]) * (K[3 * i + j] - K[3 * j + i]);
+    const double norm = sqrt(n2);
+    if (!(n2 < INFINITY)) return 4;
+    if (sqrt(a2) > SYMMETRY_TOL * norm) return 2;
+    double ev[3];
+    sym_eigenvalues3(K, ev);
+    if (ev[1] + ev[2] < -SYMMETRY_TOL * norm) return 3;
+    if (fmax(fabs(ev[0]), fabs(ev[2])) > MAX_CONCENTRATION) return 4;
+    return 0;
+}
+
+// l(K) = c(K) - tr K with the exact log-normaliser c (fisher_exact.h, relative error 1e-10 of c), fp64 on the host; an exact
+// K = kappa I takes ks::log_normaliser(kappa), the same number in closed form
+inline double log_normaliser_fisher(const double K[9]) {
+    double S[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) S[3 * i + j] = 0.5 * (K[3 * i + j] + K[3 * j + i]);
+    double U[9], s[3], V[9], c, m[3], h;
+    proper_svd3(S, U, s, V);
+    if (s[0] == s[1] && s[1] == s[2]) return ks::log_normaliser(s[0]);                       // kappa I (0 included): the isotropic pass's own
+    fisher_exact_from_s(s, c, m, h);
+    return c - (s[0] + s[1] + s[2]);
+}
+
+// t = l2 - sum_r w_r Kh w_r^T on the rows w_r = (q - c)[3r..3r+2], the nine differences ks::dist2 takes (the same subtraction: the same
+// bits): each row is w0 (k00 w0 + k01' w1 + k02' w2) + w1 (k11 w1 + k12' w2) +
+// w2 (k22 w2), the rows added in order.  Negating every d leaves every rounding where it was: symmetric in (q, c) bit for bit.
+RNF_FM_HD float fisher_term(const Quad &kq, const float *c, const float *q, float l2) {
+#pragma clang fp contract(off)                     // the products and the difference below are not to be fused: the host build's bits
+    float quad = 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float w0 = q[3 * r] - c[3 * r], w1 = q[3 * r + 1] - c[3 * r + 1], w2 = q[3 * r + 2] - c[3 * r + 2];
+        const float u0 = fmaf(kq.k[4], w2, fmaf(kq.k[3], w1, kq.k[0] * w0));
+        const float u1 = fmaf(kq.k[5], w2, kq.k[1] * w1);
+        const float u2 = kq.k[2] * w2;
+        quad = fmaf(u0, w0, quad);
+        quad = fmaf(u1, w1, quad);
+        quad = fmaf(u2, w2, quad);
+    }
+    return l2 - quad;
 }
 
 // 2^x for x <= 0 (NaN: NaN; below -125: 0, so that no result is subnormal): the same bits on the host and on the device
@@ -206,9 +328,10 @@ RNF_FM_HD void cyclic_window(float x0, float w, int n, int &lo, int &count) {
 // One sweep of a query's enumeration for the GB groups g0 .. (clamped at G - 1).
 //   SWEEP_MAX: M[gb] = max t, count = the members, visited = the rows looked at;   SWEEP_SUM: S[gb] = sum exp2(t - M[gb]) (M: finite);
 //   SWEEP_ARGMAX: SWEEP_MAX, and A[gb] = the smallest row whose t is M[gb] (-1: none above -inf), bit gb of nans set where a member's t is NaN.
+//   F: the anisotropic variant -- a member's term is fisher_term(kq, row, q, ..) on the distance's own differences; kq is not read otherwise.
 enum Mode { SWEEP_MAX = 0, SWEEP_SUM = 1, SWEEP_ARGMAX = 2 };
-template <int GB, bool W, int MODE>
-RNF_FM_HD void sweep(const Geometry &ge, const Frame &fr, const float *__restrict__ grid, const float *__restrict__ lw, long long Q, int g0, int G,
+template <int GB, bool W, int MODE, bool F = false>
+RNF_FM_HD void sweep(const Geometry &ge, const Quad &kq, const Frame &fr, const float *__restrict__ grid, const float *__restrict__ lw, long long Q, int g0, int G,
                      const float q[9], float *M, double *S, int *A, unsigned &nans, int &count, int &visited) {
     const float *lwg[GB];
 #pragma unroll
@@ -255,7 +378,7 @@ RNF_FM_HD void sweep(const Geometry &ge, const Frame &fr, const float *__restric
 #pragma unroll
                         for (int gb = 0; gb < GB; ++gb) {
                             const float l2 = W ? lwg[gb][r] * (float)ks::LOG2E : 0.f;
-                            const float tt = fmaf(-ge.h, d2, l2);
+                            const float tt = F ? fisher_term(kq, grid + 9 * r, q, l2) : fmaf(-ge.h, d2, l2);
                             if (MODE == SWEEP_SUM)
                                 part[gb] += exp2_soft(tt - M[gb]);
                             else if (MODE == SWEEP_MAX)
@@ -279,8 +402,8 @@ RNF_FM_HD void sweep(const Geometry &ge, const Frame &fr, const float *__restric
 }
 
 // One query, GB groups: out[gb], the count, and the rows the enumeration looked at (the host build reports them)
-template <int GB, bool W>
-RNF_FM_HD void query_local(const Geometry &ge, const float *offset, const float *__restrict__ grid, const float *__restrict__ lw, long long Q,
+template <int GB, bool W, bool F = false>
+RNF_FM_HD void query_local(const Geometry &ge, const Quad &kq, const float *offset, const float *__restrict__ grid, const float *__restrict__ lw, long long Q,
                            int g0, int G, const float q[9], double l_kappa, float *out, int &count, int &visited) {
 #pragma clang fp contract(off)                     // the last expression below: the host build rounds it the same way
     const Frame fr = frame_of(ge, offset, q);
@@ -293,12 +416,12 @@ RNF_FM_HD void query_local(const Geometry &ge, const float *offset, const float 
     }
     count = visited = 0;
     unsigned none = 0;
-    sweep<GB, W, SWEEP_MAX>(ge, fr, grid, lw, Q, g0, G, q, M, S, nullptr, none, count, visited);
+    sweep<GB, W, SWEEP_MAX, F>(ge, kq, fr, grid, lw, Q, g0, G, q, M, S, nullptr, none, count, visited);
     float Mu[GB];                                  // no live member: M = -inf, every term exp2(-inf - 0) = 0 (a NaN log-weight stays NaN)
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) Mu[gb] = M[gb] == -INFINITY ? 0.f : M[gb];
     int unused = 0;
-    sweep<GB, W, SWEEP_SUM>(ge, fr, grid, lw, Q, g0, G, q, Mu, S, nullptr, none, unused, unused);
+    sweep<GB, W, SWEEP_SUM, F>(ge, kq, fr, grid, lw, Q, g0, G, q, Mu, S, nullptr, none, unused, unused);
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) {
         const double s = S[gb];
@@ -315,8 +438,8 @@ RNF_FM_HD void query_local(const Geometry &ge, const float *offset, const float 
 
 // One query, GB groups of rnf_so3_grid_local_max: out[gb] = max_j (lw[g][j] - (kappa/2) d^2) - l(kappa) over the members, arg[gb] the
 // smallest row attaining it.  ONE sweep: the maximum and the tie are decided on the sum's own fp32 term t, no exp2.
-template <int GB, bool W>
-RNF_FM_HD void query_local_max(const Geometry &ge, const float *offset, const float *__restrict__ grid, const float *__restrict__ lw, long long Q,
+template <int GB, bool W, bool F = false>
+RNF_FM_HD void query_local_max(const Geometry &ge, const Quad &kq, const float *offset, const float *__restrict__ grid, const float *__restrict__ lw, long long Q,
                                int g0, int G, const float q[9], double l_kappa, float *out, int *arg, int &count, int &visited) {
 #pragma clang fp contract(off)                     // the last expression below: the host build rounds it the same way
     const Frame fr = frame_of(ge, offset, q);
@@ -329,7 +452,7 @@ RNF_FM_HD void query_local_max(const Geometry &ge, const float *offset, const fl
     }
     count = visited = 0;
     unsigned nans = 0;
-    sweep<GB, W, SWEEP_ARGMAX>(ge, fr, grid, lw, Q, g0, G, q, M, nullptr, A, nans, count, visited);
+    sweep<GB, W, SWEEP_ARGMAX, F>(ge, kq, fr, grid, lw, Q, g0, G, q, M, nullptr, A, nans, count, visited);
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb) {
         const bool bad = !fr.finite || ((nans >> gb) & 1u);
@@ -352,7 +475,7 @@ __global__ __launch_bounds__(THREADS) void so3_grid_local_kernel(Geometry ge, co
     for (int k = 0; k < 9; ++k) q[k] = queries[9 * i + k];
     float res[GB];
     int cnt, visited;
-    query_local<GB, W>(ge, offset, grid, lw, Q, g0, G, q, l_kappa, res, cnt, visited);
+    query_local<GB, W>(ge, Quad{}, offset, grid, lw, Q, g0, G, q, l_kappa, res, cnt, visited);
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb)
         if (g0 + gb < G) out[(long long)(g0 + gb) * m + i] = res[gb];
@@ -373,12 +496,39 @@ __global__ __launch_bounds__(THREADS) void so3_grid_local_max_kernel(Geometry ge
     for (int k = 0; k < 9; ++k) q[k] = queries[9 * i + k];
     float res[GB];
     int at[GB], cnt, visited;
-    query_local_max<GB, W>(ge, offset, grid, lw, Q, g0, G, q, l_kappa, res, at, cnt, visited);
+    query_local_max<GB, W>(ge, Quad{}, offset, grid, lw, Q, g0, G, q, l_kappa, res, at, cnt, visited);
 #pragma unroll
     for (int gb = 0; gb < GB; ++gb)
         if (g0 + gb < G) {
             out[(long long)(g0 + gb) * m + i] = res[gb];
             arg[(long long)(g0 + gb) * m + i] = at[gb];
+        }
+    if (count && g0 == 0) count[i] = cnt;
+}
+
+// rnf_so3_grid_local_fisher: the launch shape and the stores of the two kernels above on the anisotropic term; MAX: the max-plus pass
+template <int GB, bool W, bool MAX>
+__global__ __launch_bounds__(THREADS) void so3_grid_local_fisher_kernel(Geometry ge, Quad kq, const float *__restrict__ offset,
+                                                                        const float *__restrict__ grid, const float *__restrict__ queries,
+                                                                        const float *__restrict__ lw, long long Q, int m, int G, double l_k,
+                                                                        float *__restrict__ out, int *__restrict__ arg, int *__restrict__ count) {
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= m) return;
+    const int g0 = blockIdx.y * GB;
+    float q[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) q[k] = queries[9 * i + k];
+    float res[GB];
+    int at[GB], cnt, visited;
+    if (MAX)
+        query_local_max<GB, W, true>(ge, kq, offset, grid, lw, Q, g0, G, q, l_k, res, at, cnt, visited);
+    else
+        query_local<GB, W, true>(ge, kq, offset, grid, lw, Q, g0, G, q, l_k, res, cnt, visited);
+#pragma unroll
+    for (int gb = 0; gb < GB; ++gb)
+        if (g0 + gb < G) {
+            out[(long long)(g0 + gb) * m + i] = res[gb];
+            if (MAX) arg[(long long)(g0 + gb) * m + i] = at[gb];
         }
     if (count && g0 == 0) count[i] = cnt;
 }
@@ -398,9 +548,9 @@ inline void host_grid_local_sum(int level, const float *offset, const float *gri
             float r;
             int cnt, vis;
             if (lw)
-                query_local<1, true>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, cnt, vis);
+                query_local<1, true>(ge, Quad{}, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, cnt, vis);
             else
-                query_local<1, false>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, cnt, vis);
+                query_local<1, false>(ge, Quad{}, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, cnt, vis);
             out[(long long)g * m + i] = r;
             if (count && g == 0) count[i] = cnt;
             if (visited && g == 0) visited[i] = vis;
@@ -419,11 +569,38 @@ inline void host_grid_local_max(int level, const float *offset, const float *gri
             float r;
             int at, cnt, vis;
             if (lw)
-                query_local_max<1, true>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
+                query_local_max<1, true>(ge, Quad{}, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
             else
-                query_local_max<1, false>(ge, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
+                query_local_max<1, false>(ge, Quad{}, offset, grid, lw, Q, g, G, queries + 9 * i, l_kappa, &r, &at, cnt, vis);
             out[(long long)g * m + i] = r;
             arg[(long long)g * m + i] = at;
+            if (count && g == 0) count[i] = cnt;
+            if (visited && g == 0) visited[i] = vis;
+        }
+}
+
+// host_grid_local_sum / host_grid_local_max on the anisotropic term: K [9] row-major, arg null: the sum, else the max-plus pass
+inline void host_grid_local_fisher(int level, const float *offset, const float *grid, const float *queries, const float *lw, long long m, int G,
+                                   const double K[9], double d2_cut, float *out, int *arg, int *count, int *visited = nullptr) {
+    const Geometry ge = geometry_of(level, 0.0, d2_cut);
+    const Quad kq = quad_of(K);
+    const long long Q = rows_of(level);
+    const double l_k = log_normaliser_fisher(K);
+    if (!queries) queries = grid;
+    for (long long i = 0; i < m; ++i)
+        for (int g = 0; g < G; ++g) {
+            float r;
+            int at = -1, cnt, vis;
+            if (arg && lw)
+                query_local_max<1, true, true>(ge, kq, offset, grid, lw, Q, g, G, queries + 9 * i, l_k, &r, &at, cnt, vis);
+            else if (arg)
+                query_local_max<1, false, true>(ge, kq, offset, grid, lw, Q, g, G, queries + 9 * i, l_k, &r, &at, cnt, vis);
+            else if (lw)
+                query_local<1, true, true>(ge, kq, offset, grid, lw, Q, g, G, queries + 9 * i, l_k, &r, cnt, vis);
+            else
+                query_local<1, false, true>(ge, kq, offset, grid, lw, Q, g, G, queries + 9 * i, l_k, &r, cnt, vis);
+            out[(long long)g * m + i] = r;
+            if (arg) arg[(long long)g * m + i] = at;
             if (count && g == 0) count[i] = cnt;
             if (visited && g == 0) visited[i] = vis;
         }

@@ -873,7 +873,145 @@ def _local_args(logp, grid, who: str, name: str = "logp"):
         raise ValueError(f"{who}: {name} and grid must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
 
 
-def grid_diffuse_local(logp: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None) -> torch.Tensor:
+def _right_multiply(x: torch.Tensor, D) -> torch.Tensor:
+    """x [...,3,3] @ D for a host matrix D [3,3] in x's precision, from Python scalars: no host-to-device copy, so it can be captured"""
+    return torch.stack([x[..., 0] * float(D[0, c]) + x[..., 1] * float(D[1, c]) + x[..., 2] * float(D[2, c]) for c in range(3)], dim=-1)
+
+
+def _isotropic(A):
+    """kappa where the host matrix A [3,3] is exactly kappa I with kappa >= 0 (the isotropic model, no drift), else None"""
+    k = float(A[0, 0])
+    return k if k >= 0.0 and np.array_equal(A, k * np.eye(3)) else None
+
+
+DRIFT_RESOLUTION = 1e-7                             # a drift closer to the identity than fp32 resolves in a rotation's entries is none
+
+
+def _motion_cut(A, level, radius_deg, who):
+    """The host side of one motion matrix, from the arguments alone (no device work): -> (drift, K, whether the fp32 drift differs from
+    the identity, the cut).  Refuses what the entry point would refuse of K, and an explicit radius under the floor of a drifting model."""
+    from .utils import kde
+    drift, K, sv = kde.motion_factors(A)
+    kde._concentration(K, who)
+    drifting = bool(np.abs(drift - np.eye(3)).max() > DRIFT_RESOLUTION)
+    if radius_deg is None:
+        return drift, K, drifting, kde.local_default_d2_cut_fisher(sv, level, drifting)
+    cut = kde.local_radius_to_d2_cut(radius_deg)
+    if drifting and cut < kde.local_floor_d2_cut(level):
+        raise ValueError(f"{who}: radius_deg={radius_deg} is below {kde.LOCAL_FLOOR_SPACINGS} grid spacings of level {level} "
+                         f"({kde.LOCAL_FLOOR_SPACINGS * 360.0 / (6 * 2 ** int(level)):.3f} degrees): a drifted row may find no neighbour")
+    return drift, K, drifting, cut
+
+
+class _MotionStep:
+    """One matrix-Fisher motion model A = Delta K on one grid: the shifted rows C = grid Delta in fp32, formed once,
+    their offset O Delta, the cut, and the four passes.  ``rows`` is ``grid`` itself where the fp32 drift is the identity."""
+
+    def __init__(self, A, grid, level, radius_deg, offset, who):
+        self.A = A
+        drift, self.K, self.drifting, self.cut = _motion_cut(A, level, radius_deg, who)
+        self.level, self.grid = int(level), grid
+        self.offset = offset
+        self.rows, self.rows_offset = grid, offset
+        if self.drifting:
+            g32 = grid.detach().to(torch.float32)
+            self.rows = _right_multiply(g32, drift).contiguous()
+            off = torch.eye(3, dtype=torch.float64, device=grid.device) if offset is None else offset.detach().to(
+                device=grid.device, dtype=torch.float64).reshape(3, 3)
+            self.rows_offset = _right_multiply(off, drift).to(torch.float32)
+        self._lzq = None
+
+    def _queries(self, side):
+        return None if not self.drifting else side
+
+    def log_zq(self):
+        """log Z_j + log Q, float64 [Q]: rows G, queries C_j; -inf where the neighbourhood of C_j is empty"""
+        from .utils.kde import so3_grid_local_log_sum
+        if self._lzq is None:
+            self._lzq = so3_grid_local_log_sum(self.grid, self.level, concentration=self.K, d2_cut=self.cut, queries=self._queries(self.rows),
+                                               offset=self.offset).to(torch.float64)
+        return self._lzq
+
+    def minus_log_z(self, x64, log_q: float):
+        """x - log Z_j in fp64 rounded once; -inf where Z_j = 0: such a source row's mass is dropped"""
+        lzq = self.log_zq()
+        return torch.where(torch.isneginf(lzq), torch.full_like(x64, -float("inf")), x64 - (lzq - log_q)).to(torch.float32)
+
+    def predict(self, lw):
+        """log sum_j exp(lw_j) k(C_j, G_i): rows C (offset O Delta), queries G"""
+        from .utils.kde import so3_grid_local_log_sum
+        return so3_grid_local_log_sum(self.rows, self.level, concentration=self.K, d2_cut=self.cut, queries=self._queries(self.grid),
+                                      log_weights=lw, offset=self.rows_offset)
+
+    def best(self, lw):
+        """max_j and arg max_j of lw_j + log k(C_j, G_i): the max-plus pass in the predict orientation; arg is the source row j"""
+        from .utils.kde import so3_grid_local_log_max
+        return so3_grid_local_log_max(self.rows, self.level, concentration=self.K, d2_cut=self.cut, queries=self._queries(self.grid),
+                                      log_weights=lw, offset=self.rows_offset)
+
+    def backward(self, lw):
+        """log sum_i exp(lw_i) k(C_j, G_i): rows G (offset O), queries C"""
+        from .utils.kde import so3_grid_local_log_sum
+        return so3_grid_local_log_sum(self.grid, self.level, concentration=self.K, d2_cut=self.cut, queries=self._queries(self.rows),
+                                      log_weights=lw, offset=self.offset)
+
+
+class _Motions:
+    """The motion models of one call: one matrix, or one per step; a step whose matrix equals the one built last reuses it (its rows C
+    and its Z).  Only the last one built is kept."""
+
+    def __init__(self, A, steps, grid, level, radius_deg, offset, who, built=None):
+        self.A, self.args, self.last, self.last_A = A, (grid, level, radius_deg, offset, who), built, None if built is None else built.A
+
+    def step(self, t):
+        """the model of the step t -> t + 1 (t = 0: also the one a ``log_prior`` is taken through)"""
+        a = self.A if self.A.ndim == 2 else self.A[t]
+        if self.last is None or not np.array_equal(a, self.last_A):
+            self.last, self.last_A = _MotionStep(a, *self.args), a
+        return self.last
+
+
+def _motion_host(kappa, motion, steps, level, radius_deg, who):
+    """The checks of ``kappa`` / ``motion`` that need no device, first in every function that takes them: exactly one of the two; the
+    shape ([3,3]; with ``steps`` not None also [steps,3,3], one matrix per step); finite entries; each matrix's concentration and, for an
+    explicit radius, the floor.  -> (kappa, None) on the isotropic path (``motion`` exactly kappa I in every step IS that path: the same
+    bits), else (None, A float64 numpy) -- or the _MotionStep / _Motions a caller hands down."""
+    if (kappa is None) == (motion is None):
+        raise ValueError(f"{who}: give exactly one of kappa and motion")
+    if motion is None or isinstance(motion, (_MotionStep, _Motions)):
+        return kappa, motion
+    if isinstance(motion, torch.Tensor):
+        motion = motion.detach().cpu().to(torch.float64).numpy()               # a GPU tensor is read back
+    A = np.asarray(motion, dtype=np.float64)
+    if A.shape != (3, 3) and (steps is None or A.shape != (steps, 3, 3)):
+        want = "[3,3]" if steps is None else f"[3,3] or [{steps},3,3] (one matrix per step)"
+        raise ValueError(f"{who}: motion {tuple(A.shape)}, expected {want}")
+    if not np.isfinite(A).all():
+        raise ValueError(f"{who}: motion holds a non-finite entry")
+    flat = A.reshape(-1, 3, 3)
+    if len(flat) and all(np.array_equal(a, flat[0]) for a in flat) and _isotropic(flat[0]) is not None:
+        return _isotropic(flat[0]), None
+    for t, a in enumerate(flat):
+        if t == 0 or not np.array_equal(a, flat[t - 1]):
+            _motion_cut(a, level, radius_deg, who)
+    return None, A
+
+
+def _motion_plan(A, grid, level, radius_deg, offset, who):
+    """The device side of ``_motion_host``'s second result, once the other arguments are checked"""
+    if A is None or isinstance(A, (_MotionStep, _Motions)):
+        return A
+    return _MotionStep(A, grid, level, radius_deg, offset, who) if A.ndim == 2 else _Motions(A, len(A), grid, level, radius_deg, offset, who)
+
+
+def _steps_of(log_likelihood):
+    """T - 1 of a [T,Q] or [B,T,Q] tensor (else 0: the shape is refused further on)"""
+    ok = isinstance(log_likelihood, torch.Tensor) and log_likelihood.dim() in (2, 3)
+    return max(int(log_likelihood.shape[-2]) - 1, 0) if ok else 0
+
+
+def grid_diffuse_local(logp: torch.Tensor, grid: torch.Tensor, level: int, kappa: float = None, radius_deg: float = None, offset=None,
+                       motion=None) -> torch.Tensor:
     """``grid_diffuse``'s operator on the TRUNCATED motion kernel, for the levels where Q^2 pairs cannot run: each image's grid posterior
     diffused by the isotropic matrix-Fisher kernel of concentration ``kappa`` cut off at ``radius_deg`` (default: where (kappa/2) d^2 = 18
     nats, capped at 180 degrees; ``utils.kde.so3_grid_local_log_sum``).  ``logp`` [B,Q] on the rows of ``grid`` [Q,3,3] =
@@ -883,54 +1021,78 @@ def grid_diffuse_local(logp: torch.Tensor, grid: torch.Tensor, level: int, kappa
     The neighbourhoods are symmetric (membership is one bit-symmetric fp32 distance), so this is a Markov kernel on the grid:
     sum_i exp(out[b][i]) / Q = 1 whatever kappa and radius.  Two calls of the neighbour-limited sum: Z without weights, then the sum with
     the log-weights log_softmax(logp) - log Z, formed in fp64 and rounded once.  The cost is Q |N| terms per image, not Q^2.
-    -> float32 [B,Q], a log-density w.r.t. Haar on the grid rows.  At radius 180 it is ``grid_diffuse`` (which stays the dense form)."""
+    -> float32 [B,Q], a log-density w.r.t. Haar on the grid rows.  At radius 180 it is ``grid_diffuse`` (which stays the dense form).
+    ``motion`` [3,3] in place of ``kappa`` (exactly one of the two): a general matrix-Fisher step x' = x E, E ~ MF(A), A = Delta K
+    (``utils.kde.motion_factors``, ``utils.kde.motion_matrix``): the drift Delta shifts the source rows to C_j = R_j Delta (formed once in
+    fp32; they are the grid of offset O Delta), the symmetric K is a per-axis concentration, and k(C_j, R_i) = exp(-1/2 tr((R_i - C_j) K
+    (R_i - C_j)^T) - l(K)) (``rnf_so3_grid_local_fisher``).  N(j) is the ball of ``radius_deg`` about C_j -- by default where the loosest
+    axis reaches 18 nats, and with a drift not below 1.25 grid spacings: a smaller explicit radius is refused -- Z_j sums over it, and
+    the same stored C serves both orientations, so membership and term are bit-symmetric and the operator stays a Markov kernel.  A
+    source row whose neighbourhood is nevertheless empty (Z_j = 0) gets the log-weight -inf: its mass is dropped.  ``motion`` = kappa I
+    gives the bits of ``kappa``."""
     from .utils.kde import so3_grid_local_log_sum
     who = "grid_diffuse_local"
+    kappa, mo = _motion_host(kappa, motion, None, level, radius_deg, who)
     _local_args(logp, grid, who)
     Q = grid.shape[0]
+    mo = _motion_plan(mo, grid, level, radius_deg, offset, who)
+    if mo is not None:
+        return mo.predict(mo.minus_log_z(torch.log_softmax(logp.detach().to(torch.float64), dim=1), float(np.log(Q))))
     lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64) - float(np.log(Q))   # log Z_j
     lw = (torch.log_softmax(logp.detach().to(torch.float64), dim=1) - lz).to(torch.float32)
     return so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
 
 
-def grid_filter_step(log_prior: torch.Tensor, log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float,
-                     radius_deg: float = None, offset=None) -> dict:
+def grid_filter_step(log_prior: torch.Tensor, log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float = None,
+                     radius_deg: float = None, offset=None, motion=None) -> dict:
     """One step of a Bayes filter on the SO(3) grid: predict with ``grid_diffuse_local`` (motion kernel ``kappa``, ``radius_deg``), multiply
     by the likelihood, normalise.  ``log_prior`` [B,Q] (any normalisation) and ``log_likelihood`` [B,Q] (log of the observation's density
     at each grid rotation) on the rows of ``grid`` [Q,3,3] of ``level`` and ``offset``.
     -> dict(posterior [B,Q] float32 with sum_i exp(posterior) / Q = 1, log_evidence [B] float64 = log (1/Q) sum_i predicted_i
     likelihood_i, the log predictive density of the observation, predicted [B,Q] float32, the diffused prior).  The product and its
-    normaliser are formed in fp64 and rounded once."""
+    normaliser are formed in fp64 and rounded once.  ``motion`` [3,3] in place of ``kappa``: the drifting, anisotropic model of
+    ``grid_diffuse_local``."""
     who = "grid_filter_step"
+    kappa, motion = _motion_host(kappa, motion, None, level, radius_deg, who)
     if not isinstance(log_likelihood, torch.Tensor) or tuple(log_likelihood.shape) != tuple(getattr(log_prior, "shape", ())):
         raise ValueError(f"{who}: log_likelihood {tuple(getattr(log_likelihood, 'shape', ()))} for log_prior "
                          f"{tuple(getattr(log_prior, 'shape', ()))} (want the same shape)")
     _local_args(log_prior, grid, who, "log_prior")
     if not log_likelihood.is_cuda:
         raise ValueError(f"{who}: log_likelihood must be on the GPU; rotationnormflow_amd runs on the GPU only (no CPU fallback)")
-    predicted = grid_diffuse_local(log_prior, grid, level, kappa, radius_deg, offset)
+    predicted = grid_diffuse_local(log_prior, grid, level, kappa, radius_deg, offset, _motion_plan(motion, grid, level, radius_deg, offset, who))
     joint = predicted.to(torch.float64) + log_likelihood.detach().to(torch.float64)
     log_evidence = torch.logsumexp(joint, dim=1) - float(np.log(grid.shape[0]))
     return dict(posterior=(joint - log_evidence[:, None]).to(torch.float32), log_evidence=log_evidence, predicted=predicted)
 
 
 def grid_pose_filter(flow: Flow, features: torch.Tensor = None, kappa: float = None, recursion_level: int = 4, radius_deg: float = None, offset=None,
-                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None) -> dict:
+                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None, motion=None) -> dict:
     """A Bayes filter over a SEQUENCE of frames of one object: ``features`` [T,F], one row per frame (for an unconditional flow, the T rows
     of ``base``).  Each frame's log-density on the level-``recursion_level`` grid -- the launches of ``grid_estimate_rotations`` -- is the
     frame's likelihood; between frames the posterior is diffused by the motion kernel ``kappa`` (``grid_filter_step``).  Frame 0 starts
     from ``log_prior`` [Q] (None: uniform, and no diffusion before it: its posterior is its normalised likelihood, its estimate that of
     ``grid_estimate_rotations``).  ``offset`` as ``grid_estimate_rotations``.  Flows with batch-coupled layers are refused.
     -> dict(est [T,3,3] the posterior's arg-max rotation per frame, index [T], log_evidence [T] float64 (the log predictive density of
-    each frame given the earlier ones), posterior [Q] float32 after the last frame (sum exp / Q = 1), grid [Q,3,3], offset [3,3])."""
+    each frame given the earlier ones), posterior [Q] float32 after the last frame (sum exp / Q = 1), grid [Q,3,3], offset [3,3]).
+    ``motion`` in place of ``kappa`` (exactly one of the two): one matrix [3,3] (``grid_diffuse_local``), or [T-1,3,3], one per frame
+    after the first -- the step into frame t uses ``motion[t-1]``; a ``log_prior`` is taken through ``motion[0]``."""
     who = "grid_pose_filter"
-    if kappa is None:
+    if kappa is None and motion is None:
         raise ValueError(f"{who}: kappa is required")
+    if kappa is not None and motion is not None:
+        raise ValueError(f"{who}: give exactly one of kappa and motion")
     _refuse_batch_coupled(flow, who, ", so a frame's likelihood would depend on the frames that share its launch")
     gf, level, offset = _grid_inputs(flow, features, None, recursion_level, offset, base, who)
     with torch.no_grad():
         grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
         Q = grid.shape[0]
+        kappa, mo = _motion_host(kappa, motion, gf.B - 1, level, radius_deg, who)
+        mo = _motion_plan(mo, grid, level, radius_deg, offset, who)
+        if isinstance(mo, _MotionStep):
+            mo = _Motions(mo.A, 0, grid, level, radius_deg, offset, who, mo)
+        if mo is not None and log_prior is not None and gf.B == 1 and mo.A.ndim == 3:
+            raise ValueError(f"{who}: a log_prior is taken through motion[0], but motion holds no matrix")
         post = None
         if log_prior is not None:
             if not isinstance(log_prior, torch.Tensor) or tuple(log_prior.shape) != (Q,):
@@ -945,7 +1107,8 @@ def grid_pose_filter(flow: Flow, features: torch.Tensor = None, kappa: float = N
                     ev = torch.logsumexp(ll64, dim=1) - float(np.log(Q))
                     post = (ll64 - ev[:, None]).to(torch.float32)
                 else:
-                    step = grid_filter_step(post, ll, grid, level, kappa, radius_deg, offset)
+                    step = grid_filter_step(post, ll, grid, level, kappa, radius_deg, offset,
+                                            None if mo is None else mo.step(max(b0 + k - 1, 0)))
                     post, ev = step["posterior"], step["log_evidence"]
                 indices.append(torch.argmax(post[0]).reshape(1))
                 evidences.append(ev)
@@ -984,8 +1147,8 @@ def _recentre(delta):
     return (delta - top[:, None]).to(torch.float32), top
 
 
-def grid_viterbi(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None,
-                 log_prior: torch.Tensor = None) -> dict:
+def grid_viterbi(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float = None, radius_deg: float = None, offset=None,
+                 log_prior: torch.Tensor = None, motion=None) -> dict:
     """The most probable JOINT sequence of grid rows under the model ``grid_pose_filter`` implies (Viterbi): per-frame arg-maxes are not
     a path -- on a symmetric object they hop between equivalent modes -- this is one.  ``log_likelihood`` [T,Q] or [B,T,Q]: each frame's
     log-likelihood on the rows of ``grid`` [Q,3,3] of ``level`` and ``offset``.  The model: a step j -> i has the mass
@@ -998,23 +1161,36 @@ def grid_viterbi(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, k
     its maximum every frame and the offsets are summed in fp64.  Ties go to the smallest row.  The back-pointers are kept as int32
     [T,B,Q] -- 4 T B Q bytes, 9.4 MB per frame and sequence at level 5 -- and followed by T device-side gathers: no host synchronisation.
     -> dict(index [B,T] int64 the path's rows, est [B,T,3,3] its rotations, log_joint [B] float64 = log p(path, y)); without the B
-    axis where ``log_likelihood`` came without it.  T = 1 gives the arg-max of pi_0 l_0."""
+    axis where ``log_likelihood`` came without it.  T = 1 gives the arg-max of pi_0 l_0.
+    ``motion`` in place of ``kappa`` (exactly one of the two): one matrix [3,3] (``grid_diffuse_local``) or [T-1,3,3], the step t-1 -> t
+    using ``motion[t-1]`` (a ``log_prior`` is taken through ``motion[0]``).  The step j -> i then has the mass k(C_j, R_i) / (Z_j Q) with the
+    shifted rows C_j = R_j Delta, the max-plus pass runs over the rows C with the grid rows as queries, and its arg is the source row j."""
     from .utils.kde import so3_grid_local_log_max, so3_grid_local_log_sum
     who = "grid_viterbi"
+    kappa, mo = _motion_host(kappa, motion, _steps_of(log_likelihood), level, radius_deg, who)
     ll, batched, prior = _sequence_args(log_likelihood, grid, level, log_prior, who)
     B, T, Q = ll.shape
     log_q = float(np.log(Q))
+    mo = _motion_plan(mo, grid, level, radius_deg, offset, who)
+    if isinstance(mo, _MotionStep):
+        mo = _Motions(mo.A, 0, grid, level, radius_deg, offset, who, mo)
+    if mo is not None and prior is not None and T == 1 and mo.A.ndim == 3:
+        raise ValueError(f"{who}: a log_prior is taken through motion[0], but motion holds no matrix")
     with torch.no_grad():
         delta = ll[:, 0].to(torch.float64) - log_q
         if prior is not None:
-            delta = delta + grid_diffuse_local(prior, grid, level, kappa, radius_deg, offset).to(torch.float64)
+            delta = delta + grid_diffuse_local(prior, grid, level, kappa, radius_deg, offset, None if mo is None else mo.step(0)).to(torch.float64)
         delta, log_joint = _recentre(delta)
         back = torch.empty(T, B, Q, dtype=torch.int32, device=ll.device)
-        if T > 1:
+        if T > 1 and mo is None:
             lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64) - log_q    # log Z_j
         for t in range(1, T):
-            lw = (delta.to(torch.float64) - lz).to(torch.float32)
-            best, arg = so3_grid_local_log_max(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
+            if mo is not None:
+                step = mo.step(t - 1)
+                best, arg = step.best(step.minus_log_z(delta.to(torch.float64), log_q))
+            else:
+                lw = (delta.to(torch.float64) - lz).to(torch.float32)
+                best, arg = so3_grid_local_log_max(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
             back[t] = arg
             delta, top = _recentre(ll[:, t].to(torch.float64) + best.to(torch.float64) - log_q)
             log_joint = log_joint + top
@@ -1029,8 +1205,8 @@ def grid_viterbi(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, k
     return dict(index=index, est=est, log_joint=log_joint)
 
 
-def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float, radius_deg: float = None, offset=None,
-                log_prior: torch.Tensor = None) -> dict:
+def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, kappa: float = None, radius_deg: float = None, offset=None,
+                log_prior: torch.Tensor = None, motion=None) -> dict:
     """Fixed-interval smoothing on the SO(3) grid: every frame of a recorded sequence judged with all of it, p(x_t | y_0..T-1), by the
     forward-backward recursion on the model of ``grid_viterbi`` (same arguments).  Forward: the ``grid_filter_step`` chain itself, frame 0
     from ``log_prior`` (None: uniform, and as in ``grid_pose_filter`` nothing is diffused before it: its posterior is its normalised
@@ -1041,12 +1217,22 @@ def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, ka
     b = 0 exactly, is the filtered one bit for bit).
     -> dict(smoothed [B,T,Q] and filtered [B,T,Q] float32 log-densities with sum exp / Q = 1, log_evidence [B,T] float64 as
     ``grid_filter_step``'s, backward [B,T,Q] float32 the b_t, index [B,T] and est [B,T,3,3] the smoothed arg-max); without the B axis
-    where ``log_likelihood`` came without it.  Three [B,T,Q] float32 arrays are kept."""
+    where ``log_likelihood`` came without it.  Three [B,T,Q] float32 arrays are kept.
+    ``motion`` in place of ``kappa`` (exactly one of the two): as in ``grid_viterbi``.  The backward step of t uses ``motion[t]``:
+        b_t(j) = log sum_{i in N(j)} k(C_j, R_i) l_{t+1}(i) exp b_{t+1}(i) - log Z_j - log Q - log_evidence_{t+1},
+    the sum over the grid rows with the shifted rows C as queries; a source row with Z_j = 0 has b = -inf.  A time-varying motion
+    rebuilds each distinct matrix's rows and Z on the way back."""
     from .utils.kde import so3_grid_local_log_sum
     who = "grid_smooth"
+    kappa, mo = _motion_host(kappa, motion, _steps_of(log_likelihood), level, radius_deg, who)
     ll, batched, prior = _sequence_args(log_likelihood, grid, level, log_prior, who)
     B, T, Q = ll.shape
     log_q = float(np.log(Q))
+    mo = _motion_plan(mo, grid, level, radius_deg, offset, who)
+    if isinstance(mo, _MotionStep):
+        mo = _Motions(mo.A, 0, grid, level, radius_deg, offset, who, mo)
+    if mo is not None and prior is not None and T == 1 and mo.A.ndim == 3:
+        raise ValueError(f"{who}: a log_prior is taken through motion[0], but motion holds no matrix")
     with torch.no_grad():
         filtered = torch.empty(B, T, Q, dtype=torch.float32, device=ll.device)
         evidence = torch.empty(B, T, dtype=torch.float64, device=ll.device)
@@ -1057,18 +1243,24 @@ def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, ka
                 ev = torch.logsumexp(ll64, dim=1) - log_q
                 post = (ll64 - ev[:, None]).to(torch.float32)
             else:
-                step = grid_filter_step(post, ll[:, t], grid, level, kappa, radius_deg, offset)
+                step = grid_filter_step(post, ll[:, t], grid, level, kappa, radius_deg, offset, None if mo is None else mo.step(max(t - 1, 0)))
                 post, ev = step["posterior"], step["log_evidence"]
             filtered[:, t], evidence[:, t] = post, ev
         backward = torch.zeros(B, T, Q, dtype=torch.float32, device=ll.device)
         smoothed = torch.empty_like(filtered)
         smoothed[:, T - 1] = filtered[:, T - 1]
-        if T > 1:
+        if T > 1 and mo is None:
             lz = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, offset=offset).to(torch.float64)    # log Z_j + log Q
         for t in range(T - 2, -1, -1):
             lw = (ll[:, t + 1].to(torch.float64) + backward[:, t + 1].to(torch.float64)).to(torch.float32)
-            s = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
-            backward[:, t] = (s.to(torch.float64) - lz - evidence[:, t + 1, None]).to(torch.float32)
+            if mo is not None:
+                step = mo.step(t)
+                s, lzq = step.backward(lw).to(torch.float64), step.log_zq()
+                b = torch.where(torch.isneginf(lzq), torch.full_like(s, -float("inf")), s - lzq - evidence[:, t + 1, None])
+                backward[:, t] = b.to(torch.float32)
+            else:
+                s = so3_grid_local_log_sum(grid, level, kappa, radius_deg=radius_deg, log_weights=lw, offset=offset)
+                backward[:, t] = (s.to(torch.float64) - lz - evidence[:, t + 1, None]).to(torch.float32)
             both = filtered[:, t].to(torch.float64) + backward[:, t].to(torch.float64)
             smoothed[:, t] = (both - (torch.logsumexp(both, dim=1, keepdim=True) - log_q)).to(torch.float32)
         index = torch.argmax(smoothed, dim=2)
@@ -1078,24 +1270,30 @@ def grid_smooth(log_likelihood: torch.Tensor, grid: torch.Tensor, level: int, ka
 
 
 def grid_pose_smooth(flow: Flow, features: torch.Tensor = None, kappa: float = None, recursion_level: int = 4, radius_deg: float = None, offset=None,
-                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None) -> dict:
+                     base=None, images_per_launch: int = None, log_prior: torch.Tensor = None, motion=None) -> dict:
     """``grid_pose_filter`` for a RECORDED sequence: the frames' grid log-densities -- collected on the launches of
     ``grid_estimate_rotations``, one row per frame of ``features`` [T,F] -- are judged together, by ``grid_smooth`` (each frame's marginal
     given the whole clip) and by ``grid_viterbi`` (the most probable joint path; on a symmetric object it stays on one branch where the
     per-frame arg-max hops).  Arguments as ``grid_pose_filter``; ``log_prior`` [Q] or None.  T Q floats are kept for the likelihoods, and
     what the two recursions keep.  Flows with batch-coupled layers are refused.
     -> dict(est_smoothed [T,3,3], index_smoothed [T], est_path [T,3,3], index_path [T], log_evidence [T] float64, log_joint float64 [],
-    smoothed [T,Q], grid [Q,3,3], offset [3,3])."""
+    smoothed [T,Q], grid [Q,3,3], offset [3,3]).  ``motion`` in place of ``kappa``: [3,3] or [T-1,3,3], as in ``grid_pose_filter``."""
     who = "grid_pose_smooth"
-    if kappa is None:
+    if kappa is None and motion is None:
         raise ValueError(f"{who}: kappa is required")
+    if kappa is not None and motion is not None:
+        raise ValueError(f"{who}: give exactly one of kappa and motion")
     _refuse_batch_coupled(flow, who, ", so a frame's likelihood would depend on the frames that share its launch")
     gf, level, offset = _grid_inputs(flow, features, None, recursion_level, offset, base, who)
     with torch.no_grad():
         grid = sd.generate_healpix_grid(level, device=gf.dev, offset=offset)
         ll = torch.cat([lp.to(torch.float32).clone() for _, _, lp in gf.images(grid, images_per_launch, who)])
-        smooth = grid_smooth(ll, grid, level, kappa, radius_deg, offset, log_prior)
-        path = grid_viterbi(ll, grid, level, kappa, radius_deg, offset, log_prior)
+        kappa, mo = _motion_host(kappa, motion, ll.shape[0] - 1, level, radius_deg, who)
+        mo = _motion_plan(mo, grid, level, radius_deg, offset, who)             # built once: both recursions share the rows C and Z
+        if isinstance(mo, _MotionStep):
+            mo = _Motions(mo.A, 0, grid, level, radius_deg, offset, who, mo)
+        smooth = grid_smooth(ll, grid, level, kappa, radius_deg, offset, log_prior, mo)
+        path = grid_viterbi(ll, grid, level, kappa, radius_deg, offset, log_prior, mo)
     return dict(est_smoothed=smooth["est"], index_smoothed=smooth["index"], est_path=path["est"], index_path=path["index"],
                 log_evidence=smooth["log_evidence"], log_joint=path["log_joint"], smoothed=smooth["smoothed"], grid=grid, offset=offset)
 

@@ -150,8 +150,103 @@ def local_default_d2_cut(kappa: float) -> float:
     return 8.0 if k * 8.0 <= 2.0 * LOCAL_NATS else 2.0 * LOCAL_NATS / k
 
 
-def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
-                           offset=None, return_count: bool = False):
+LOCAL_MAX_CONCENTRATION = 3.0e4                     # the largest |eigenvalue| rnf_so3_grid_local_fisher takes (include/rnf_hip.h)
+LOCAL_FLOOR_SPACINGS = 1.25                         # the floor of a drifting model's cut, in grid spacings 360 / (6 2^level) degrees
+
+
+def _matrix33(x, name: str, who: str):
+    """A 3x3 matrix given as nested sequences, a numpy array or a tensor -> float64 numpy [3,3]; a GPU tensor is read back (a host
+    synchronisation)."""
+    import numpy as np
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().to(torch.float64).numpy()
+    a = np.asarray(x, dtype=np.float64)
+    if a.shape != (3, 3):
+        raise ValueError(f"{who}: {name} {a.shape}, expected [3,3]")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{who}: {name} holds a non-finite entry")
+    return a
+
+
+def motion_factors(A):
+    """The drift and the concentration of a matrix-Fisher motion model x' = x E, E ~ MF(A): with the proper SVD A = U diag(s) V^T
+    (U, V rotations, s1 >= s2 >= |s3|, s3 with the sign of det A),
+        drift Delta = U V^T (a rotation: the mode of the step),   concentration K = V diag(s) V^T (symmetric),   A = Delta K.
+    ``A`` [3,3]: nested sequences, a numpy array or a tensor -- a GPU tensor is READ BACK to the host (a synchronisation); a non-finite
+    ``A`` is refused.  -> (drift [3,3] float64, concentration [3,3] float64, s [3] float64), numpy arrays."""
+    import numpy as np
+    a = _matrix33(A, "A", "motion_factors")
+    U, s, Vt = np.linalg.svd(a)
+    V = Vt.T
+    s = s.copy()
+    if np.linalg.det(U) < 0.0:
+        U = U * np.array([1.0, 1.0, -1.0])
+        s[2] = -s[2]
+    if np.linalg.det(V) < 0.0:
+        V = V * np.array([1.0, 1.0, -1.0])
+        s[2] = -s[2]
+    K = (V * s) @ V.T
+    return U @ V.T, 0.5 * (K + K.T), s
+
+
+def motion_matrix(drift=None, sigma_deg=(5.0, 5.0, 5.0), axes=None):
+    """A motion model written in degrees -> A [3,3] float64 (numpy) for the ``motion`` arguments of ``grid_pose``.  ``drift`` [3,3]: the
+    mean step, a rotation (None: none).  ``sigma_deg`` (sx, sy, sz): the standard deviations of the step's small-angle rotation vector
+    about the principal axes, the columns of ``axes`` [3,3] (a rotation; None: the body axes x, y, z).  For MF(A) the rotation-vector
+    variance about principal axis k is 1 / (s_i + s_j) of the OTHER two proper singular values, so with p_k = 1 / sigma_k^2 (radians)
+        s_k = (p_x + p_y + p_z - 2 p_k) / 2,      A = drift  axes diag(s) axes^T.
+    Every pair sum s_i + s_j = p_k is positive; one s_k is negative where one axis is much tighter than the other two.  The passes take
+    |s_k| up to 3e4 (sigma down to about 0.25 degrees)."""
+    import numpy as np
+    who = "motion_matrix"
+    sig = np.asarray(sigma_deg, dtype=np.float64).reshape(-1)
+    if sig.shape != (3,) or not (np.isfinite(sig).all() and (sig > 0.0).all()):
+        raise ValueError(f"{who}: sigma_deg={sigma_deg}, expected three positive finite angles")
+    p = 1.0 / np.radians(sig) ** 2
+    sv = 0.5 * (p.sum() - 2.0 * p)
+    V = np.eye(3) if axes is None else _matrix33(axes, "axes", who)
+    D = np.eye(3) if drift is None else _matrix33(drift, "drift", who)
+    for name, R in (("axes", V), ("drift", D)):
+        if np.abs(R.T @ R - np.eye(3)).max() > 1e-6 or np.linalg.det(R) < 0.0:
+            raise ValueError(f"{who}: {name} is not a rotation")
+    return D @ (V * sv) @ V.T
+
+
+def local_floor_d2_cut(level: int) -> float:
+    """The smallest cut of a DRIFTING model at ``level``: the chord of 1.25 grid spacings.  A shifted row C_j = G_j Delta is no grid row,
+    so its nearest row is not at distance 0; the largest angle from 20 000 uniform rotations to their nearest row is 0.81 to 0.89
+    spacings at levels 0 to 3."""
+    return 4.0 * (1.0 - math.cos(math.radians(LOCAL_FLOOR_SPACINGS * 360.0 / (6 * 2 ** int(level)))))
+
+
+def local_default_d2_cut_fisher(s, level: int, drifting: bool) -> float:
+    """The default cut of the anisotropic passes: the exponent is bounded by -(s2 + s3)/4 d^2 with the two SMALLEST proper singular
+    values, so the 18 nats of ``local_default_d2_cut`` are reached at d^2 = 72 / (s2 + s3) (36 / kappa for K = kappa I), capped at 8
+    (180 degrees; 8 where s2 + s3 <= 9) and, where the model drifts, not below ``local_floor_d2_cut(level)``."""
+    v = sorted(float(x) for x in s)
+    pair = v[0] + v[1]
+    cut = 8.0 if pair * 8.0 <= 4.0 * LOCAL_NATS else 4.0 * LOCAL_NATS / pair
+    return min(8.0, max(cut, local_floor_d2_cut(level))) if drifting else cut
+
+
+def _concentration(concentration, who: str):
+    """-> (K float64 numpy [3,3], its eigenvalues in decreasing order, kappa where K is exactly kappa I else None)"""
+    import numpy as np
+    K = _matrix33(concentration, "concentration", who)
+    norm = float(np.linalg.norm(K))
+    if float(np.linalg.norm(K - K.T)) > 1e-9 * norm:
+        raise ValueError(f"{who}: concentration is not symmetric")
+    ev = np.linalg.eigvalsh(0.5 * (K + K.T))[::-1]
+    if ev[1] + ev[2] < -1e-9 * norm:
+        raise ValueError(f"{who}: concentration has two eigenvalues with a negative sum; it is not the symmetric factor of a proper SVD")
+    if np.abs(ev).max() > LOCAL_MAX_CONCENTRATION:
+        raise ValueError(f"{who}: concentration has an eigenvalue beyond 3e4 in magnitude")
+    kappa = float(K[0, 0]) if np.array_equal(K, K[0, 0] * np.eye(3)) and K[0, 0] >= 0.0 else None
+    return K, ev, kappa
+
+
+def so3_grid_local_log_sum(grid, level: int, kappa: float = None, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
+                           offset=None, return_count: bool = False, concentration=None):
     """The neighbour-limited kernel sum over the rows of the SO(3) grid on the device (``rnf_so3_grid_local_sum``,
     csrc/so3_grid_local.h): out[g][i] = log sum_{j: d^2(G_j, Q_i) <= cut} exp(log_weights[g][j]) k_kappa(G_j, Q_i) with the kernel of
     ``so3_kernel_log_density`` and d^2 = |G_j - Q_i|_F^2 = 4 (1 - cos angle).  The log-weights are NOT normalised.
@@ -161,12 +256,17 @@ def so3_grid_local_log_sum(grid, level: int, kappa: float, radius_deg: float = N
     -> float32 [m] or [G,m] (with ``return_count`` also int32 [m], the rows within the cut).  An empty or massless neighbourhood gives -inf,
     a row with log-weight -inf drops out, a NaN log-weight inside a query's neighbourhood gives NaN, a non-finite query NaN and count 0.
     A result is bit-identical from run to run and however the call is tiled, so the tiling of queries and groups is invisible.
-    Stream-ordered, no host synchronisation, no workspace, no gradient."""
-    return _grid_local_pass("so3_grid_local_log_sum", False, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count)
+    Stream-ordered, no host synchronisation, no workspace, no gradient.
+    ``concentration`` [3,3] in place of ``kappa`` (exactly one of the two): the anisotropic kernel
+    k_K(G_j, Q_i) = exp(-1/2 tr((Q_i - G_j) K (Q_i - G_j)^T) - l(K)) of ``rnf_so3_grid_local_fisher``, K symmetric with eigenvalue pair
+    sums >= 0 and |eigenvalues| <= 3e4 (``motion_factors``); the default cut is then ``local_default_d2_cut_fisher`` without the floor.
+    A concentration that is exactly kappa I runs the isotropic entry point: the bits of ``kappa=kappa``."""
+    return _grid_local_pass("so3_grid_local_log_sum", False, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count,
+                            concentration)
 
 
-def so3_grid_local_log_max(grid, level: int, kappa: float, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
-                           offset=None, return_count: bool = False):
+def so3_grid_local_log_max(grid, level: int, kappa: float = None, radius_deg: float = None, d2_cut: float = None, queries=None, log_weights=None,
+                           offset=None, return_count: bool = False, concentration=None):
     """The max-plus pass over the neighbourhoods of ``so3_grid_local_log_sum`` on the device (``rnf_so3_grid_local_max``,
     csrc/so3_grid_local.h): out[g][i] = max_{j: d^2(G_j, Q_i) <= cut} (log_weights[g][j] - (kappa/2) d^2(G_j, Q_i)) - l(kappa), the largest
     TERM of that sum, and arg[g][i] = the smallest grid row j attaining it -- the step of a Viterbi recursion (``grid_pose.grid_viterbi``).
@@ -174,12 +274,17 @@ def so3_grid_local_log_max(grid, level: int, kappa: float, radius_deg: float = N
     -> (float32 [m] or [G,m], int64 of the same shape) (with ``return_count`` also int32 [m]).  An empty neighbourhood, or one whose rows
     all have log-weight -inf, gives -inf and arg -1; a NaN log-weight inside a query's neighbourhood gives NaN and -1, a non-finite query
     NaN, -1 and count 0.  The maximum and the tie are decided on the kernel's fp32 term.  A result is bit-identical from run to run and
-    however the call is tiled.  Stream-ordered, no host synchronisation, no workspace, no gradient."""
-    return _grid_local_pass("so3_grid_local_log_max", True, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count)
+    however the call is tiled.  Stream-ordered, no host synchronisation, no workspace, no gradient.
+    ``concentration`` [3,3] in place of ``kappa``: as in ``so3_grid_local_log_sum``; the term is lw - 1/2 tr((Q_i - G_j) K (Q_i - G_j)^T)."""
+    return _grid_local_pass("so3_grid_local_log_max", True, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count,
+                            concentration)
 
 
-def _grid_local_pass(who: str, with_arg: bool, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count):
+def _grid_local_pass(who: str, with_arg: bool, grid, level, kappa, radius_deg, d2_cut, queries, log_weights, offset, return_count,
+                     concentration=None):
     """The argument checks and the tiling the two neighbour-limited passes share; ``with_arg``: the max pass, -> (out, arg int64[, count])"""
+    if (kappa is None) == (concentration is None):
+        raise ValueError(f"{who}: give exactly one of kappa and concentration")
     if not isinstance(grid, torch.Tensor) or grid.dim() != 3 or tuple(grid.shape[-2:]) != (3, 3):
         raise ValueError(f"{who}: grid {tuple(getattr(grid, 'shape', ()))}, expected [Q,3,3]")
     level = int(level)
@@ -190,13 +295,20 @@ def _grid_local_pass(who: str, with_arg: bool, grid, level, kappa, radius_deg, d
         raise ValueError(f"{who}: grid holds {grid.shape[0]} rows, level {level} has {Q}")
     Gr = _rotations(grid, "grid", who)
     dev = Gr.device
-    (k,), scalar = _kappas(kappa, who)
-    if not scalar:
-        raise ValueError(f"{who}: kappa is one concentration, not a sequence")
+    K = None
+    if concentration is not None:
+        K, ev, kappa = _concentration(concentration, who)                    # kappa: where K is exactly kappa I, the isotropic entry
+    if kappa is not None:
+        K = None
+        (k,), scalar = _kappas(kappa, who)
+        if not scalar:
+            raise ValueError(f"{who}: kappa is one concentration, not a sequence")
     if radius_deg is not None and d2_cut is not None:
         raise ValueError(f"{who}: give radius_deg or d2_cut, not both")
-    cut = local_default_d2_cut(k) if radius_deg is None and d2_cut is None else (
-        local_radius_to_d2_cut(radius_deg) if radius_deg is not None else float(d2_cut))
+    if radius_deg is None and d2_cut is None:
+        cut = local_default_d2_cut(k) if K is None else local_default_d2_cut_fisher(ev, level, False)
+    else:
+        cut = local_radius_to_d2_cut(radius_deg) if radius_deg is not None else float(d2_cut)
     if not (math.isfinite(cut) and 0.0 <= cut <= 8.0):
         raise ValueError(f"{who}: d2_cut={cut} outside 0..8")
     Qr = Gr if queries is None or queries is grid else _rotations(queries, "queries", who)
@@ -235,15 +347,23 @@ def _grid_local_pass(who: str, with_arg: bool, grid, level, kappa, radius_deg, d
             tile = None if all_rows else _aligned(Qr[i0:i1])
             common = dict(level=level, offset=None if off is None else off.data_ptr(), grid=Gr.data_ptr(),
                           queries=None if all_rows else tile.data_ptr(), log_weights=lw[g0:g1].data_ptr() if lw is not None else None,
-                          m=i1 - i0, G=g1 - g0, kappa=k, d2_cut=cut, out=dst.data_ptr(),
+                          m=i1 - i0, G=g1 - g0, d2_cut=cut, out=dst.data_ptr(),
                           count=count[i0:i1].data_ptr() if return_count and g0 == 0 else None)
+            if K is None:
+                common["kappa"] = k
+            else:
+                common["concentration"] = (C.c_double * 9)(*[float(x) for x in K.reshape(9)])
+            adst = None
             if with_arg:
                 adst = arg[g0:g1, i0:i1] if whole else torch.empty(g1 - g0, i1 - i0, dtype=torch.int32, device=dev)
+            if K is not None:
+                _lib.call("so3_grid_local_fisher", _lib.So3GridLocalFisher(arg=adst.data_ptr() if with_arg else None, **common), dev)
+            elif with_arg:
                 _lib.call("so3_grid_local_max", _lib.So3GridLocalMax(arg=adst.data_ptr(), **common), dev)
-                if not whole:
-                    arg[g0:g1, i0:i1].copy_(adst)
             else:
                 _lib.call("so3_grid_local_sum", _lib.So3GridLocalSum(**common), dev)
+            if with_arg and not whole:
+                arg[g0:g1, i0:i1].copy_(adst)
             if not whole:
                 part.copy_(dst)
     out = out if grouped else out[0]

@@ -8,8 +8,11 @@ and alone where it cannot.  One process, the arms alternating step by step, medi
   level4, level5           grid_diffuse_local alone, 4 images, default radius 15 degrees (294 912 and 2 359 296 rows): its time, the time
                            of its unweighted pass (log Z) alone, terms per second, the share of enumerated rows that pass the membership
                            test (from the host build's census of 256 queries) and the unweighted pass's share of its issue bound
+  level4_fisher            the anisotropic pass (rnf_so3_grid_local_fisher, concentration=V diag(s) V^T with s2 + s3 = 2 kappa) against the
+                           isotropic pass of the same build at the same cut, level 4, 15 degrees: unweighted, 4 images as groups, and the
+                           max-plus pass; the arms alternate, median
 
-    python tools/bench_so3_grid_local.py [--steps 5] [--only level3_r15,level3_r30,level4,level5] [--clock-seconds 3]
+    python tools/bench_so3_grid_local.py [--steps 5] [--only level3_r15,level3_r30,level4,level5,level4_fisher] [--clock-seconds 3]
 
 A term is one (query, member, image) of a sum.  The issue bound of the unweighted pass: vector-issue slots over 256 CUs x 4 SIMDs x 32 lanes
 per cycle at the shader clock observed while the pass runs back to back (tools/bench_so3_kde.py observed_clock_ghz); from the gfx950
@@ -62,7 +65,7 @@ def visited_share(grid, level, kappa, samples=256):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--only", default="level3_r15,level3_r30,level4,level5")
+    ap.add_argument("--only", default="level3_r15,level3_r30,level4,level5,level4_fisher")
     ap.add_argument("--clock-ghz", type=float, default=2.4, help="stands in where the clock cannot be observed")
     ap.add_argument("--clock-seconds", type=float, default=3.0, help="how long the unweighted pass runs for the clock samples (0: skip)")
     a = ap.parse_args()
@@ -83,6 +86,28 @@ def main():
                                   kappa=kappa, radius_deg=radius, steps=a.steps, local_ms=ms["local"], dense_ms=ms["dense"],
                                   dense_over_local=ms["dense"] / ms["local"], mean_neighbours=float(count.double().mean()),
                                   max_abs_log_difference=float(diff[torch.isfinite(diff)].max()), max_total_variation=float(tv))), flush=True)
+            continue
+        if name == "level4_fisher":
+            level, images, radius = 4, 4, 15.0
+            kappa, cut = kappa_for_radius(radius), kde.local_radius_to_d2_cut(radius)
+            axes = torch.linalg.qr(torch.randn(3, 3, dtype=torch.float64, generator=torch.Generator().manual_seed(1)))[0].numpy()
+            K = (axes * np.array([4.0 * kappa, 1.5 * kappa, 0.5 * kappa])) @ axes.T                  # the same loosest-axis bound: s2 + s3 = 2 kappa
+            K = 0.5 * (K + K.T)
+            grid = sd.generate_healpix_grid(level, device="cuda")
+            lw = torch.log_softmax(posterior(grid, images, level), dim=1)
+            arms = {"iso_unweighted": lambda: kde.so3_grid_local_log_sum(grid, level, kappa, d2_cut=cut),
+                    "fisher_unweighted": lambda: kde.so3_grid_local_log_sum(grid, level, concentration=K, d2_cut=cut),
+                    "iso_weighted": lambda: kde.so3_grid_local_log_sum(grid, level, kappa, d2_cut=cut, log_weights=lw),
+                    "fisher_weighted": lambda: kde.so3_grid_local_log_sum(grid, level, concentration=K, d2_cut=cut, log_weights=lw),
+                    "iso_max": lambda: kde.so3_grid_local_log_max(grid, level, kappa, d2_cut=cut, log_weights=lw),
+                    "fisher_max": lambda: kde.so3_grid_local_log_max(grid, level, concentration=K, d2_cut=cut, log_weights=lw)}
+            ms, _ = median_ms(arms, a.steps)
+            count = kde.so3_grid_local_log_sum(grid, level, kappa, d2_cut=cut, return_count=True)[1]
+            line = dict(metric="anisotropic against isotropic neighbour-limited pass on SO(3)", case=name, level=level, rows=grid.shape[0],
+                        images=images, kappa=kappa, radius_deg=radius, steps=a.steps, mean_neighbours=float(count.double().mean()))
+            line.update({k + "_ms": v for k, v in ms.items()})
+            line.update({"fisher_over_iso_" + k: ms["fisher_" + k] / ms["iso_" + k] for k in ("unweighted", "weighted", "max")})
+            print(json.dumps(line), flush=True)
             continue
         level, images, radius = int(name[-1]), 4, 15.0
         kappa = kappa_for_radius(radius)
